@@ -5,13 +5,21 @@
 Default workload = BASELINE.json configs[1]: Q8_0 weights N_out=4096 x K=4096, M_tok=128
 fp16 activations on one MI355X.  One "step" = one drop-in call: q8_1 quantization of the
 activations + the MMQ over one weight matrix (gq_mmq).  Inputs are resident in HBM before
-timing.  K steps are captured into a hipGraph; ceil(copies / K) such graphs together cycle
-over >= 1 GiB of distinct weight copies (rotation_plan), whatever K is, and are replayed
+timing.  L = min(K, 200) steps are captured into a hipGraph; ceil(copies / L) such graphs together
+cycle over >= 1 GiB of distinct weight copies (rotation_plan), whatever L is, and are replayed
 round robin, so every timed replay finds its weights evicted from the 256 MB Infinity Cache by
-the >= 1 GiB read since.  Time = HIP events around one replay (K steps), bracketed by barrier +
-synchronize; the MEDIAN over the replays is reported.
+the >= 1 GiB read since.  Time = HIP events around one replay (L steps), bracketed by barrier +
+synchronize; the MEDIAN over the replays is reported.  The headline times exactly K steps
+(Runner.timed_steps: K // L whole replays and one graph of the K % L steps left), after W warm-up
+steps and a quarter of a second of untimed rounds of the graphs (SETTLE_S).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--strong] [--quick] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
+                  [--full [--quick] [--no-cpu] [--detail FILE]] [--strong]
+
+A plain N = 1 run does only what the headline needs: set-up, warm-up, the K timed steps, the
+outputs (--dump-outputs DIR: what the last timed step returned, DIR/C.npy, float32 (M_tok, N_out);
+the inputs are seeded, so two builds can be compared output for output) and the result line.
+Everything else listed under "Extra JSON fields" is measured with --full only.
 
 N > 1 (torch.distributed.run, one rank per GPU, RCCL): the row-sharded matmul of
 dist/row_shard.py (RowShardedMMQ: local MMQ on the rank's rows, RCCL all_gather of the fp16
@@ -22,7 +30,7 @@ output slabs over xGMI, overlapped with the next step's compute, assembled to (N
             split over the N ranks, compute-only and end-to-end.
   --strong  the headline itself is the strong-scaling Q6_K 28672x8192 (M_tok 128) run.
 
-Extra JSON fields: roofline (dominant kernel = the MMQ launch, timed alone with HIP events
+Extra JSON fields (--full): roofline (dominant kernel = the MMQ launch, timed alone with HIP events
 in its own graph), cpu_baseline (oracle/ C restatement of kernels/cpu_impls, rank 0 at N=1
 only: all host cores (row slices), plus the 1-thread literal port and the product's own
 vectorised CPU MMQ in cpu_baseline_variants), sweep (every GGUF type at M=1 and M=128 on the
@@ -47,6 +55,11 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec (MI355X_MICROARCH.md)
 MFMA_F16_PEAK_TF = 2500.0  # dense fp16/bf16 MFMA spec
 ROTATE_BYTES = 1 << 30     # >= 4x the 256 MiB Infinity Cache
+GRAPH_STEPS = 200          # most steps captured into one graph (the default --steps)
+DUMP_BYTES = 64 << 20      # most bytes --dump-outputs writes
+# untimed replays before the headline's timed steps: with one untimed round only, a single 200-step
+# replay right after set-up read 16.9 us per step where the median of later replays reads 15.8
+SETTLE_S = 0.25
 
 # name -> (fmt, N_out (weight rows), K, M_tok)
 CONFIGS = {
@@ -193,6 +206,40 @@ class Runner:
         t = timed_rotation(gs, self.dev) / len(self.plans[0])
         del gs
         return t
+
+    def timed_steps(self, fn, steps):
+        """Exactly `steps` timed steps of fn: the rotation's graphs (L steps each) replayed round
+        robin, steps // L times in all, then one graph of the steps % L that remain (the next
+        graph's first copies); every replay is timed alone (timed_replay), after SETTLE_S
+        seconds of untimed rounds of all of them and with the output buffers zeroed.  -> (median
+        seconds per step over the replays, the output buffer the last timed step wrote)."""
+        gs = self.graphs(fn)
+        L = len(self.plans[0])
+        whole, rest = divmod(steps, L)
+        tail = self.capture(fn, self.plans[whole % len(gs)][:rest]) if rest else None
+        t0 = time.perf_counter()
+        while time.perf_counter() - t0 < SETTLE_S:
+            for g in gs + [tail] * bool(rest):
+                g.replay()
+            torch.cuda.synchronize(self.dev)
+        for c in self.C:
+            c.zero_()
+        ts = [timed_replay(gs[i % len(gs)], self.dev) / L for i in range(whole)]
+        if rest:
+            ts.append(timed_replay(tail, self.dev) / rest)
+        return float(np.median(ts)), self.C[((rest or L) - 1) & 1]
+
+
+def dump_outputs(path, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: every array as path/<name>.npy in float32, `limit` bytes at most in all; a
+    larger array is cut to a fixed (seed 0) sorted sample of its flattened elements."""
+    os.makedirs(path, exist_ok=True)
+    each = limit // max(1, len(arrays)) // 4
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > each:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, each, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def timed_replay(graph, dev, dist_on=False) -> float:
@@ -731,10 +778,55 @@ def bench_config(name, steps, warmup, dev):
     torch.cuda.synchronize(dev)
     del gw
     per_step = r.timed(r.step)
-    # dominant kernel: decode (N <= 4) -- the step IS one launch (fused quantizer + weight
-    # stream), so its time is the step's; GEMM -- the MMQ call alone (gemm_kernel [+ split-K
-    # reduce]) with the activations prepared once, K launches per graph, the same rotation
+    out = config_record(name, r, per_step)
+    out["roofline"] = kernel_roofline(name, r, per_step)
+    del r
+    torch.cuda.empty_cache()
+    return out
+
+
+def bench_head(name, steps, warmup, dev, full=False, dump=None):
+    """The headline config: `warmup` steps in a graph of their own, then exactly `steps` timed
+    steps (Runner.timed_steps; graphs of at most GRAPH_STEPS steps) and, if asked for, the last
+    step's output written to dump/C.npy.  full: the dominant kernel's roofline as well, which
+    takes a timed run of its own."""
+    fmt, M, K, N = CONFIGS[name]
+    r = Runner(fmt, M, K, N, dev, min(steps, GRAPH_STEPS))
+    gw = r.capture(r.step, [i % r.ncopies for i in range(max(1, warmup))])
+    gw.replay()
+    torch.cuda.synchronize(dev)
+    del gw
+    per_step, C = r.timed_steps(r.step, steps)
+    if dump:
+        dump_outputs(dump, {"C": C})
+    out = config_record(name, r, per_step)
+    out["roofline"] = kernel_roofline(name, r, per_step) if full else None
+    del r
+    torch.cuda.empty_cache()
+    return out
+
+
+def config_record(name, r, per_step):
+    fmt, M, K, N = CONFIGS[name]
+    wbytes, _, flops = model(fmt, M, K, N)
+    return {
+        "config": name, "fmt": fmt, "N_out": M, "K": K, "M_tok": N,
+        "ms_per_step": per_step * 1e3,
+        "tflops": flops / per_step / 1e12,
+        "weight_GBps": wbytes / per_step / 1e9,
+        "weight_copies": r.ncopies,
+        "weight_bytes_rotated": r.rotated,
+        "graphs_rotated": len(r.plans),
+    }
+
+
+def kernel_roofline(name, r, per_step):
+    """The roofline record of the config's dominant kernel: decode (N <= 4) -- the step IS one
+    launch (fused quantizer + weight stream), so its time is the step's; GEMM -- the MMQ call
+    alone (gemm_kernel [+ split-K reduce]) with the activations prepared once, the launches per
+    graph and the rotation of Runner r."""
     import kernels._lib as kl
+    fmt, M, K, N = CONFIGS[name]
     if N <= 4:
         t_k = per_step
         kname = kl.route_name(kl.TYPES[fmt], M, N, K) + " (fused q8_1 + decode)"
@@ -742,20 +834,7 @@ def bench_config(name, steps, warmup, dev):
         r.prepare()
         t_k = r.timed(r.kernel)
         kname = kl.route_name(kl.TYPES[fmt], M, N, K, prepared=True)  # (the library's own routing)
-    wbytes, alg_bytes, flops = model(fmt, M, K, N)
-    out = {
-        "config": name, "fmt": fmt, "N_out": M, "K": K, "M_tok": N,
-        "ms_per_step": per_step * 1e3,
-        "tflops": flops / per_step / 1e12,
-        "weight_GBps": wbytes / per_step / 1e9,
-        "roofline": dict(roofline(fmt, M, K, N, t_k, load_traffic(name)), kernel=kname),
-        "weight_copies": r.ncopies,
-        "weight_bytes_rotated": r.rotated,
-        "graphs_rotated": len(r.plans),
-    }
-    del r
-    torch.cuda.empty_cache()
-    return out
+    return dict(roofline(fmt, M, K, N, t_k, load_traffic(name)), kernel=kname)
 
 
 def bench_layer(Ns, acts, steps, warmup, dev, fuse=True, grouped="auto", gemm_grouped_min=None):
@@ -919,16 +998,23 @@ def single_line(args, name, head, sweep, cpu_b, cpu_var, eager, eager_host):
         "config": {"workload": name, "gguf_type": fmt, "N_out": M, "K": K, "M_tok": N, "parallelism": "single",
                    "weight_copies": head["weight_copies"], "weight_bytes_rotated": head["weight_bytes_rotated"],
                    "graphs_rotated": head["graphs_rotated"],
-                   "timing": "median of round-robin replays of the rotation's graphs, K steps each"},
+                   "timing": f"the {args.steps} timed steps as round-robin replays of the rotation's graphs "
+                             f"({min(args.steps, GRAPH_STEPS)} steps each, the last one the steps left over), "
+                             "each replay timed alone; median per-step time over the replays"},
         "weight_GBps": round(head["weight_GBps"], 1),
+        "full": args.full,
         "roofline": head["roofline"],
         "cpu_baseline": cpu_b,
-        "eager_us": eager,
-        "eager_us_is": "median of 1000 eager kernels.mmq_q4_k.mmq_q4_k(A, B, 4096, 1, 4096) calls, each synchronized",
-        "eager_host_us": eager_host,
-        "eager_host_us_is": "the same call 1000 times back to back, one synchronize at the end, / 1000 (the "
-                            "per-call host cost when the kernel is shorter)",
     }
+    if eager is not None:
+        line.update({
+            "eager_us": eager,
+            "eager_us_is": "median of 1000 eager kernels.mmq_q4_k.mmq_q4_k(A, B, 4096, 1, 4096) calls, each "
+                           "synchronized",
+            "eager_host_us": eager_host,
+            "eager_host_us_is": "the same call 1000 times back to back, one synchronize at the end, / 1000 (the "
+                                "per-call host cost when the kernel is shorter)",
+        })
     if cpu_var:
         line["cpu_baseline_variants"] = [{k: v[k] for k in ("value", "unit", "cores", "kind", "sample")} for v in cpu_var]
     if sweep:
@@ -1019,13 +1105,24 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default=DEFAULT, choices=sorted(CONFIGS))
     ap.add_argument("--strong", action="store_true", help="the N > 1 line (Q6_K 28672x8192 row-sharded) at any N")
-    ap.add_argument("--quick", action="store_true", help="headline only: no per-type sweep")
-    ap.add_argument("--sweep", action="store_true", help="(the default; kept for old command lines)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--detail", default=None, help="also write the full per-config records to this JSON file")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: also the headline kernel's roofline, the per-type sweep, the eager-call times and "
+                         "the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: write what the last timed step returned to DIR/C.npy (float32)")
+    ap.add_argument("--quick", action="store_true", help="with --full: no per-type sweep")
+    ap.add_argument("--sweep", action="store_true", help="(kept for old command lines)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--detail", default=None,
+                    help="with --full: also write the full per-config records to this JSON file")
     ap.add_argument("--layer-only", action="store_true",
                     help="print only the Q4_K_M layer sweep (fused and unfused), one JSON line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.gpus > 1 or args.strong or args.layer_only or
+                              os.environ.get("BENCH_FORCE_DIST") == "1"):
+        ap.error("--dump-outputs writes the N = 1 headline step's output only")
 
     # --gpus N > 1 outside torch.distributed: the N ranks run as a child process
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1073,8 +1170,12 @@ def main():
         return
     name = args.config
     fmt, M, K, N = CONFIGS[name]
-    sweep_steps = max(20, args.steps // 4)
-    head = bench_config(name, args.steps, args.warmup, dev)
+    head = bench_head(name, args.steps, args.warmup, dev, full=args.full, dump=args.dump_outputs)
+    if not args.full:  # the plain run: the headline alone
+        print(json.dumps(single_line(args, name, head, [], None, None, None, None), separators=(",", ":")), flush=True)
+        return
+    # --full: graphs of the sweep's configs hold a quarter of the headline's steps per graph
+    sweep_steps = max(20, min(args.steps, GRAPH_STEPS) // 4)
     sweep = []
     if not args.quick:
         for sname in CONFIGS:

@@ -12,13 +12,14 @@
 #   bash tools/gpu.sh dist                  bench.py's N > 1 path at world 1 over RCCL (BENCH_FORCE_DIST)
 #   bash tools/gpu.sh round                 round-end measurements: FETCH_SIZE traffic per config (read by
 #                                           bench.py into roofline.traffic), the PMC passes of the shipping
-#                                           kernels, the default bench line, and rocprofv3 stats of that command
+#                                           kernels, the bench --full line, and rocprofv3 stats of that command
 #
 # Every GPU step runs under its own timeout; a failing step ends the script.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
 mkdir -p gpurun_out
+RES="$ROOT/$_"  # (the results folder just made)
 cmd=${1:-tests}; shift || true
 case "$cmd" in
 tests)
@@ -70,10 +71,10 @@ round)
   timeout -k 10 600 python3 tools/pmc_traffic.py $TCFGS > gpurun_out/round_traffic.log 2>&1 &&
   PASSES="FETCH_SIZE|SQ_VALU_MFMA_BUSY_CYCLES,SQ_BUSY_CYCLES,GRBM_GUI_ACTIVE|TA_BUSY_avr,TCC_HIT_sum,TCC_MISS_sum|SQ_INSTS_LDS,SQ_INSTS_VMEM_RD,SQ_INSTS_VALU,SQ_INSTS_MFMA" \
     bash tools/gpu.sh pmc $PCFGS > gpurun_out/round_pmc.log 2>&1 &&
-  timeout -k 10 600 python3 -u bench.py --detail gpurun_out/round_detail.json > gpurun_out/round_bench.json 2> gpurun_out/round_bench.err &&
+  timeout -k 10 600 python3 -u bench.py --full --detail "$RES/round_detail.json" > "$RES/round_bench.json" 2> "$RES/round_bench.err" &&
   mkdir -p gpurun_out/round_prof && cd /tmp && export TMPDIR=/tmp &&
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/gpurun_out/round_prof" -o run -- \
-    python3 "$ROOT/bench.py" > "$ROOT/gpurun_out/round_prof/bench.json" 2> "$ROOT/gpurun_out/round_prof/bench.err" &&
+    python3 "$ROOT/bench.py" --full > "$RES/round_prof/bench.json" 2> "$RES/round_prof/bench.err" &&
   python3 "$ROOT/tools/kstats.py" "$ROOT/gpurun_out/round_prof/run_kernel_stats.csv" > "$ROOT/gpurun_out/round_prof/kstats.txt" &&
   # the per-dispatch CSVs are summarized above (summary.txt, pmc_*.json, kstats.txt): drop them so
   # gpurun_out stays under the copy-back limit
