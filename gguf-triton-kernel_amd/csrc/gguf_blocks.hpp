@@ -6,6 +6,9 @@
 //                           w = d*sc_j*q - dmin*m_j   (sub-block j = e/32)
 //   Q6_K 256 elems /210 B : [0:128] ql | [128:192] qh | [192:208] int8 sc x16 | [208:210] d
 //                           w = d*sc_{e/16}*(q - 32)
+//   Q5_K 256 elems /176 B : [0:2] d | [2:4] dmin | [4:16] 6-bit sc/m x8 (Q4_K's) | [16:48] qh |
+//                           [48:176] qs nibbles;  q = nibble + 16*((qh[e%32] >> e/32) & 1)
+//                           w = d*sc_j*q - dmin*m_j   (sub-block j = e/32)
 //   Q8_1 (activations) 36 B: [0:2] d | [2:4] s = d*sum(q) | [4:36] qs int8[32]
 // Reference: block docs in kernels/mmq_q4_k.py:1-16, kernels/mmq_q6_k.py:1-14,
 // utils/quantize/q8_1.py:1-11; unpack rules kernels/mmq_q4_k.py:30-114, mmq_q6_k.py:28-68.
@@ -20,12 +23,15 @@
 
 namespace gq {
 
-enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2 };
+enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3 };
 
 template <int F> struct Layout;
 template <> struct Layout<Q8_0> { static constexpr int QK = 32, BYTES = 34; };
 template <> struct Layout<Q4_K> { static constexpr int QK = 256, BYTES = 144; };
 template <> struct Layout<Q6_K> { static constexpr int QK = 256, BYTES = 210; };
+template <> struct Layout<Q5_K> { static constexpr int QK = 256, BYTES = 176; };
+// Q4_K's header and q8_1 arithmetic (6-bit scales and mins, the activation block's s in the min term)
+constexpr bool has_mins(int f) { return f == Q4_K || f == Q5_K; }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

@@ -4,6 +4,7 @@
 //   Q8_0 : dA*dB*sum(qA*qB)                                  mmq_q8_0_q8_1_cpu.py:37-54
 //   Q4_K : d*sc*dB*sum(q*qB) - dmin*m*sB                     mmq_q4_k_q8_1_cpu.py:94-117
 //   Q6_K : dB*(d*sc1*sum((q-32)*qB)_lo + d*sc2*sum(...)_hi)  mmq_q6_k_q8_1_cpu.py:117-150
+//   Q5_K : Q4_K's expression, q = 0..31
 // with exact int32 dot products (v_dot4_i32_i8) and fp32 accumulation.
 #pragma once
 #include "gguf_blocks.hpp"
@@ -15,7 +16,7 @@ template <int F, int NT>
 struct Act {
     uint32_t q[NT][16]; // int8 codes of the two activation blocks
     float d[NT][2];
-    float s[NT][2];  // q8_1 s (Q4_K min term)
+    float s[NT][2];  // q8_1 s (Q4_K / Q5_K min term)
     int sum[NT][4];  // sum of codes per 16-element quarter (Q6_K -32 offset)
 };
 
@@ -43,7 +44,7 @@ __device__ __forceinline__ void load_act(Act<F, NT> &a, const int8_t *__restrict
         a.q[t][12] = c3.x; a.q[t][13] = c3.y; a.q[t][14] = c3.z; a.q[t][15] = c3.w;
         a.d[t][0] = xd[tok * nb + b0];
         a.d[t][1] = has1 ? xd[tok * nb + b1] : 0.f;
-        if constexpr (F == Q4_K) {
+        if constexpr (has_mins(F)) {
             a.s[t][0] = xs[tok * nb + b0];
             a.s[t][1] = has1 ? xs[tok * nb + b1] : 0.f;
         }
@@ -86,7 +87,20 @@ __device__ __forceinline__ void dot_unit(const UnitRaw<F> &r, const Act<F, NT> &
             acc[t] += r.ds0 * a.d[t][0] * (float)i0 - r.dm0 * a.s[t][0] + r.ds1 * a.d[t][1] * (float)i1 -
                       r.dm1 * a.s[t][1];
         }
+    } else if constexpr (F == Q5_K) { // Q4_K's expression with the 5-bit codes 0..31
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            int i0 = 0, i1 = 0;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                i0 = dot4(r.c0[i], a.q[t][i], i0);
+                i1 = dot4(r.c1[i], a.q[t][8 + i], i1);
+            }
+            acc[t] += r.ds0 * a.d[t][0] * (float)i0 - r.dm0 * a.s[t][0] + r.ds1 * a.d[t][1] * (float)i1 -
+                      r.dm1 * a.s[t][1];
+        }
     } else {
+        static_assert(F == Q6_K, "dot_unit: unlisted format");
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             int a1 = 0, a2 = 0, b1 = 0, b2 = 0;
@@ -135,6 +149,7 @@ __device__ __forceinline__ uint32_t n02(uint32_t v) { return (v & 0x000f000fu) |
 template <int F, int NT, bool NS = false>
 __device__ __forceinline__ void dot_unit_h(const UnitRaw<F> &r, const ActH<NT> &a, float (&acc)[NT])
 {
+    static_assert(F == Q8_0 || F == Q4_K || F == Q6_K, "the fp8 variant has no Q5_K form");
     typedef _Float16 hb2 __attribute__((ext_vector_type(2)));
     auto unbias = [](uint32_t v, float b) {
         const hb2 bb = {(_Float16)b, (_Float16)b};
@@ -306,7 +321,7 @@ __device__ __forceinline__ void load_act_lds(Act<F, NT> &a, const uint8_t *codes
         a.q[t][12] = c3.x; a.q[t][13] = c3.y; a.q[t][14] = c3.z; a.q[t][15] = c3.w;
         a.d[t][0] = sd[t * nb + b0];
         a.d[t][1] = has1 ? sd[t * nb + b1] : 0.f;
-        if constexpr (F == Q4_K) {
+        if constexpr (has_mins(F)) {
             a.s[t][0] = ss[t * nb + b0];
             a.s[t][1] = has1 ? ss[t * nb + b1] : 0.f;
         }

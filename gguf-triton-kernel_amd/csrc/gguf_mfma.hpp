@@ -102,6 +102,33 @@ __device__ __forceinline__ void q4k_frags(const uint8_t *hdrp, const uint8_t *w3
                         __builtin_elementwise_fma(pair13(x1) + bias, ds, ndm));
     }
 }
+// Q5_K sub-stage q: Q4_K's (the same header, nibbles of qs bytes 32q..+32 at w32) plus the code's
+// fifth bit: bit 2q + n of the 32 qh bytes at qhp (byte l = element l of every sub-block).  Codes
+// 0..31, 1024 + code exact in fp16; the same fp16 fma per weight as Q4_K.
+__device__ __forceinline__ void q5k_frags(const uint8_t *hdrp, const uint8_t *qhp, const uint8_t *w32, int g, int q,
+                                          f16x8 (&frag)[2])
+{
+    const u32x4 hdr = *(const u32x4 *)hdrp;
+    const float d = h2f(hdr.x & 0xffffu), dmin = h2f(hdr.x >> 16);
+    const uint32_t sc = q < 2 ? (hdr.y & 0x3f3f3f3fu) : ((hdr.w & 0x0f0f0f0fu) | ((hdr.y >> 2) & 0x30303030u));
+    const uint32_t mn = q < 2 ? (hdr.z & 0x3f3f3f3fu) : (((hdr.w >> 4) & 0x0f0f0f0fu) | ((hdr.z >> 2) & 0x30303030u));
+    const int sh = 16 * (q & 1);
+    const u32x2 w = *(const u32x2 *)(w32 + 8 * g);
+    const u32x2 hb = *(const u32x2 *)(qhp + 8 * g);
+    const h2 bias = splat(-1024.f);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) { // n = 0: low nibbles (sub-block 2q), 1: high (2q+1)
+        const h2 ds = splat(d * (float)((sc >> (sh + 8 * n)) & 0xffu));
+        const h2 ndm = splat(-(dmin * (float)((mn >> (sh + 8 * n)) & 0xffu)));
+        const int hs = 2 * q + n;
+        const uint32_t x0 = ((w.x >> (4 * n)) & 0x0f0f0f0fu) | (((hb.x >> hs) & 0x01010101u) << 4);
+        const uint32_t x1 = ((w.y >> (4 * n)) & 0x0f0f0f0fu) | (((hb.y >> hs) & 0x01010101u) << 4);
+        frag[n] = frag4(__builtin_elementwise_fma(pair02(x0) + bias, ds, ndm),
+                        __builtin_elementwise_fma(pair13(x0) + bias, ds, ndm),
+                        __builtin_elementwise_fma(pair02(x1) + bias, ds, ndm),
+                        __builtin_elementwise_fma(pair13(x1) + bias, ds, ndm));
+    }
+}
 template <>
 __device__ __forceinline__ void stage_frags<Q4_K>(const uint8_t *wr, int g, int q, f16x8 (&frag)[2], int)
 {

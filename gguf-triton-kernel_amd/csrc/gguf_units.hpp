@@ -3,6 +3,7 @@
 // A unit is 64 weights of one row that one lane owns: unit u of a row covers
 //   Q8_0 : blocks 2u, 2u+1 (bytes 68u .. 68u+67 of the row)
 //   Q4_K : super-block u/4, sub-blocks 2(u%4), 2(u%4)+1 (qs bytes 32(u%4)..+31, both nibbles)
+//   Q5_K : as Q4_K (qs bytes 32(u%4)..+31 of the 176-byte super-block) + its 32 qh bytes
 //   Q6_K : super-block u/4, half h=(u>>1)&1, v=u&1: elements 128h+32v+[0,32) ("A") and
 //          128h+64+32v+[0,32) ("B") -- ql bytes 64h+32v..+31 (both nibbles), qh 32h..+31
 // so two consecutive units (2c, 2c+1) tile K-chunk c of 128 elements.  Every unit needs
@@ -139,6 +140,50 @@ template <> struct UnitRaw<Q4_K> {
         r.dm1 = dmin * (float)m1;
         r.w[0] = l.qa.x; r.w[1] = l.qa.y; r.w[2] = l.qa.z; r.w[3] = l.qa.w;
         r.w[4] = l.qb.x; r.w[5] = l.qb.y; r.w[6] = l.qb.z; r.w[7] = l.qb.w;
+        return r;
+    }
+};
+
+// ---- Q5_K: one quarter of a super-block (Q4_K's unit + the 32 qh bytes, bits 2q and 2q+1) ----
+template <> struct UnitLoad<Q5_K> {
+    u32x4 hdr, qa, qb, ha, hb;
+    __device__ __forceinline__ void load(const uint8_t *__restrict__ rowp, int u, int64_t /*nb32*/)
+    {
+        const int sb = u >> 2, q = u & 3;
+        const uint8_t *p = rowp + 176 * (int64_t)sb;
+        hdr = ld16(p);
+        ha = ld16(p + 16);
+        hb = ld16(p + 32);
+        qa = ld16(p + 48 + 32 * q);
+        qb = ld16(p + 64 + 32 * q);
+    }
+};
+
+template <> struct UnitRaw<Q5_K> {
+    float ds0, dm0, ds1, dm1; // d*sc and dmin*m of the two sub-blocks
+    uint32_t c0[8], c1[8];    // 5-bit codes (0..31) of sub-blocks 2q and 2q+1, one per byte
+
+    __device__ __forceinline__ static UnitRaw from(const UnitLoad<Q5_K> &l, int u, int64_t /*nb32*/)
+    {
+        UnitRaw r;
+        const int q = u & 3;
+        const float d = h2f(l.hdr.x & 0xffffu), dmin = h2f(l.hdr.x >> 16);
+        const uint32_t sw[3] = {l.hdr.y, l.hdr.z, l.hdr.w};
+        int sc0, m0, sc1, m1;
+        q4k_sc_m(sw, 2 * q, sc0, m0);
+        q4k_sc_m(sw, 2 * q + 1, sc1, m1);
+        r.ds0 = d * (float)sc0;
+        r.dm0 = dmin * (float)m0;
+        r.ds1 = d * (float)sc1;
+        r.dm1 = dmin * (float)m1;
+        const uint32_t qs[8] = {l.qa.x, l.qa.y, l.qa.z, l.qa.w, l.qb.x, l.qb.y, l.qb.z, l.qb.w};
+        const uint32_t qh[8] = {l.ha.x, l.ha.y, l.ha.z, l.ha.w, l.hb.x, l.hb.y, l.hb.z, l.hb.w};
+        const int sh = 2 * q;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            r.c0[i] = (qs[i] & 0x0f0f0f0fu) | (((qh[i] >> sh) & 0x01010101u) << 4);
+            r.c1[i] = ((qs[i] >> 4) & 0x0f0f0f0fu) | (((qh[i] >> (sh + 1)) & 0x01010101u) << 4);
+        }
         return r;
     }
 };

@@ -152,7 +152,8 @@ int fail(int code, const char *fmt, ...)
 }
 
 int block_elems(int t) { return t == GQ_Q8_0 ? 32 : 256; }
-int block_bytes(int t) { return t == GQ_Q8_0 ? 34 : (t == GQ_Q4_K ? 144 : 210); }
+int block_bytes(int t) { return t == GQ_Q8_0 ? 34 : (t == GQ_Q4_K ? 144 : (t == GQ_Q5_K ? 176 : 210)); }
+bool known_type(int t) { return t == GQ_Q8_0 || t == GQ_Q4_K || t == GQ_Q6_K || t == GQ_Q5_K; }
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -210,7 +211,7 @@ constexpr int64_t kSkinnyMinTokens = 5, kSkinnyMaxTokens = 16, kSkinnyForcedMax 
 bool use_skinny(int t, int form, int64_t N, int act = GQ_ACT_Q8_1)
 {
     const int sk = gq::tuning().skinny;
-    if (form != gq::AF_F16 || sk == 0) return false;
+    if (form != gq::AF_F16 || sk == 0 || t == GQ_Q5_K) return false; // (Q5_K: the streaming GEMM only)
     if (sk == 1) return N <= kSkinnyForcedMax;
     // the fp8 variant has no decode kernel: its 1..4 tokens take the skinny kernel too
     const int64_t lo = act == GQ_ACT_FP8_E4M3 ? 1 : kSkinnyMinTokens;
@@ -240,6 +241,7 @@ bool gemm_knob_pinned()
 bool use_rgemm(int t, int form, int64_t M, int64_t N, int64_t K)
 {
     const int rg = gq::tuning().rgemm;
+    if (t == GQ_Q5_K) return false; // (no resident form: the streaming GEMM, whatever GQ_RGEMM says)
     if (rg == 0 || form != gq::AF_F16 || use_gemv(N, K) || use_blas(N, K) || K % 256 != 0) return false;
     if (gemm_rows_per_launch(t, M, K) < M || gemm_toks_per_launch(N, K) < N) return false;
     const gq::RGemmPlan p = gq::plan_rgemm(M, N, K);
@@ -322,6 +324,11 @@ constexpr int64_t kSgemmMinTokens = 17, kSgemmQ6MinTokens = 5;
 bool use_sgemm(int t, int form, int64_t M, int64_t N, int64_t K)
 {
     const int sg = gq::tuning().sgemm;
+    // Q5_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
+    // knob of the other GEMMs says; rows over the per-launch limit are cut into chunks (compute())
+    if (t == GQ_Q5_K)
+        return form == gq::AF_F16 && !use_gemv(N, K) && !use_blas(N, K) && K % 256 == 0 && M > 0 &&
+               gemm_toks_per_launch(N, K) >= N && 256 * row_bytes_of(t, K) < ((int64_t)1 << 31);
     if (sg == 0 || form != gq::AF_F16 || use_gemv(N, K) || use_blas(N, K) || K % 256 != 0) return false;
     if (gemm_rows_per_launch(t, M, K) < M || gemm_toks_per_launch(N, K) < N) return false;
     if (!gq::plan_sgemm(M, N, K, gq::tuning().sgemm_splits).ok) return false;
@@ -348,6 +355,20 @@ size_t sgemm_partial_bytes(int t, int64_t M, int64_t N, int64_t K)
     gq::SGroupItem it;
     gq::SGroupPlan g;
     return sgemm_streamk(t, M, N, K, it, g) ? g.partial_bytes : sgemm_plan(M, N, K).partial_bytes;
+}
+
+// Q5_K on the GEMM token counts: the streaming GEMM per chunk of gemm_rows_per_launch rows (rows
+// are independent); its partials are the largest chunk shape's
+size_t q5k_partial_bytes(int64_t M, int64_t N, int64_t K)
+{
+    const int64_t mr = gemm_rows_per_launch(GQ_Q5_K, M, K);
+    size_t p = 0;
+    for (int64_t mc : {mr, M % mr})
+        if (mc > 0) {
+            const size_t q = sgemm_partial_bytes(GQ_Q5_K, mc, N, K);
+            p = q > p ? q : p;
+        }
+    return p;
 }
 
 bool use_i8(int t, int64_t N, int64_t K)
@@ -419,7 +440,9 @@ size_t ws_bytes(int t, int act, int64_t M, int64_t N, int64_t K)
     const Route r = route(t, act, N, K);
     size_t b = act_bytes(act, N, K);
     if (r.blas) b += align_up((size_t)M * K * 2) + gq::blas_workspace_bytes(); // fp16 W + hipBLASLt
-    else if (!r.gemv && gq::gemm_supported(t, K) && M > 0 && N > 0) {
+    else if (!r.gemv && t == GQ_Q5_K) {
+        if (M > 0 && N > 0 && use_sgemm(t, r.form, M, N, K)) b += align_up(q5k_partial_bytes(M, N, K));
+    } else if (!r.gemv && gq::gemm_supported(t, K) && M > 0 && N > 0) {
         // split-K partials of the largest need over the launch shapes (full and remainder chunks)
         // (the kernel is chosen by the call's token count, so every chunk runs the same arithmetic)
         const bool sk = use_skinny(t, r.form, N, act);
@@ -567,11 +590,18 @@ size_t gq_mmq_workspace_size(gq_type t, int64_t M, int64_t N, int64_t K)
 
 static int check_common(gq_type t, int64_t M, int64_t N, int64_t K)
 {
-    if (t != GQ_Q8_0 && t != GQ_Q4_K && t != GQ_Q6_K) return fail(GQ_EUNSUPPORTED, "unknown gguf type %d", (int)t);
+    if (!known_type(t)) return fail(GQ_EUNSUPPORTED, "unknown gguf type %d", (int)t);
     if (M < 0 || N < 0 || K < 0)
         return fail(GQ_EINVAL, "negative size M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
     const int qk = block_elems(t);
     if (K % qk != 0) return fail(GQ_EINVAL, "K=%lld is not a multiple of %d", (long long)K, qk);
+    return GQ_OK;
+}
+
+// Q5_K runs with q8_1 activations only
+static int check_pair(gq_type t, int act)
+{
+    if (t == GQ_Q5_K && act == GQ_ACT_FP8_E4M3) return fail(GQ_EUNSUPPORTED, "Q5_K has no fp8-activation form");
     return GQ_OK;
 }
 
@@ -667,6 +697,30 @@ static int compute(gq_type t, int act, const void *A, void *workspace, size_t wo
     hipError_t e;
     if (r.gemv) {
         e = gq::launch_gemv(t, (const uint8_t *)A, c.xq, c.xd, c.xs, (uint16_t *)C, M, N, K, ldc, s);
+    } else if (t == GQ_Q5_K) {
+        // the streaming GEMM and nothing else; row chunks under the per-launch byte limit
+        if (!use_sgemm(t, r.form, M, N, K))
+            return fail(GQ_EUNSUPPORTED, "Q5_K: not a streaming-GEMM shape (M=%lld N=%lld K=%lld)", (long long)M,
+                        (long long)N, (long long)K);
+        const int64_t mr = gemm_rows_per_launch(t, M, K);
+        gq::SGroupItem it;
+        gq::SGroupPlan g;
+        e = hipSuccess;
+        if (mr >= M && sgemm_streamk(t, M, N, K, it, g)) {
+            it.A = (const uint8_t *)A;
+            it.X = c.xdeq;
+            it.C = (uint16_t *)C;
+            it.ldc = ldc;
+            e = gq::launch_sgemm_grouped(&it, 1, N, g, c.partials, s);
+        } else {
+            for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += mr) {
+                const int64_t mc = M - m0 < mr ? M - m0 : mr;
+                e = gq::launch_sgemm(t, (const uint8_t *)A + m0 * row_bytes_of(t, K), c.xdeq, (uint16_t *)C + m0,
+                                     c.partials, sgemm_plan(mc, N, K), mc, N, K, ldc, s);
+            }
+        }
+        if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (sgemm): %s", hipGetErrorString(e));
+        return GQ_OK;
     } else {
         // chunks of < 2 GiB of weights and of activations per launch (32-bit buffer offsets)
         // (the kernel is chosen by the call's token count: every chunk runs the same arithmetic)
@@ -731,6 +785,7 @@ int gq_mmq_ex(gq_type t, gq_act act, const void *A, const void *B, void *C, int6
     int rc = check_common(t, M, N, K);
     if (rc != GQ_OK) return rc;
     if ((rc = check_act(act, K)) != GQ_OK) return rc;
+    if ((rc = check_pair(t, act)) != GQ_OK) return rc;
     if (M == 0 || N == 0) return GQ_OK;
     if (K == 0) return fail(GQ_EINVAL, "K must be positive");
     if (!A || !B || !C) return fail(GQ_EINVAL, "null pointer (A=%p B=%p C=%p)", A, B, C);
@@ -768,7 +823,10 @@ int gq_mmq_ex(gq_type t, gq_act act, const void *A, const void *B, void *C, int6
         if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (rgemm): %s", hipGetErrorString(e));
         return GQ_OK;
     }
-    if (!r.gemv && !r.blas && act == GQ_ACT_Q8_1 && r.form == gq::AF_F16 && !use_skinny(t, r.form, N) &&
+    if (!r.gemv && !r.blas && t == GQ_Q5_K && !use_sgemm(t, r.form, M, N, K)) // (before any launch)
+        return fail(GQ_EUNSUPPORTED, "Q5_K: not a streaming-GEMM shape (M=%lld N=%lld K=%lld)", (long long)M,
+                    (long long)N, (long long)K);
+    if (!r.gemv && !r.blas && t != GQ_Q5_K && act == GQ_ACT_Q8_1 && r.form == gq::AF_F16 && !use_skinny(t, r.form, N) &&
         !use_sgemm(t, r.form, M, N, K) &&
         gemm_rows_per_launch(t, M, K) >= M &&
         gemm_toks_per_launch(N, K) >= N) {
@@ -880,6 +938,7 @@ int gq_mmq_prepared_ex(gq_type t, gq_act act, const void *A, void *workspace, si
     int rc = check_common(t, M, N, K);
     if (rc != GQ_OK) return rc;
     if ((rc = check_act(act, K)) != GQ_OK) return rc;
+    if ((rc = check_pair(t, act)) != GQ_OK) return rc;
     if (M == 0 || N == 0) return GQ_OK;
     if (K == 0) return fail(GQ_EINVAL, "K must be positive");
     return compute(t, act, A, workspace, workspace_bytes, C, M, N, K, ldc, (hipStream_t)stream);
@@ -921,6 +980,7 @@ int gq_quantize_q8_1(const void *X, void *Y, int64_t rows, int64_t K, int64_t ld
 int gq_quantize_weights(gq_type t, const void *X, void *Y, int64_t n, void *stream)
 {
     g_err.clear();
+    if (t == GQ_Q5_K) return fail(GQ_EUNSUPPORTED, "Q5_K has no device quantizer (gq_quantize_q5_k on the host)");
     if (t != GQ_Q8_0 && t != GQ_Q4_K && t != GQ_Q6_K) return fail(GQ_EUNSUPPORTED, "unknown gguf type %d", (int)t);
     if (n < 0) return fail(GQ_EINVAL, "negative size");
     const int qk = block_elems(t);
@@ -996,6 +1056,7 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
         int rc = check_common(it.type, it.M, N, it.K);
         if (rc != GQ_OK) return rc;
         if ((rc = check_act(act, it.K)) != GQ_OK) return rc;
+        if ((rc = check_pair(it.type, act)) != GQ_OK) return rc;
         if (it.M == 0 || N == 0) continue;
         if (it.K == 0) return fail(GQ_EINVAL, "item %d: K must be positive", i);
         if (!it.A || !it.B || !it.C) return fail(GQ_EINVAL, "item %d: null pointer", i);
@@ -1044,6 +1105,7 @@ static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int6
         int rc = check_common(it.type, it.M, N, it.K);
         if (rc != GQ_OK) return rc;
         if ((rc = check_act(act, it.K)) != GQ_OK) return rc;
+        if ((rc = check_pair(it.type, act)) != GQ_OK) return rc;
         if (it.K % 256 != 0 || it.K == 0) return fail(GQ_EUNSUPPORTED, "item %d: K=%lld is not a multiple of 256", i, (long long)it.K);
         if (it.M > 0 && (!it.A || !it.ws || !it.C)) return fail(GQ_EINVAL, "item %d: null pointer", i);
         if (it.ldc < it.M) return fail(GQ_EINVAL, "item %d: ldc=%lld < M=%lld", i, (long long)it.ldc, (long long)it.M);
@@ -1167,7 +1229,7 @@ int gq_mmq_sharded(gq_type t, const void *A_shard, const void *B, void *C, int64
 const char *gq_debug_route(gq_type t, gq_act act, int64_t M, int64_t N, int64_t K, int prepared)
 {
     // the same decisions, in the same order, as gq_mmq_ex (prepared = 0) and compute()
-    if (check_common(t, M, N, K) != GQ_OK || check_act(act, K) != GQ_OK || M <= 0 || N <= 0 || K <= 0) return "none";
+    if (check_common(t, M, N, K) != GQ_OK || check_act(act, K) != GQ_OK || check_pair(t, act) != GQ_OK || M <= 0 || N <= 0 || K <= 0) return "none";
     g_err.clear();
     const Route r = route(t, act, N, K);
     if (fused_decode_route(t, act, N, K) && (!prepared || prep_raw(act, N, K))) return "stream_decode_kernel";
@@ -1189,5 +1251,6 @@ const char *gq_debug_route(gq_type t, gq_act act, int64_t M, int64_t N, int64_t 
         return p.splits == 1 ? "sgemm_kernel"
                : gq::sgemm_ilc(p) ? "sgemm_kernel (in-launch split-K sum)" : "sgemm_kernel + gemm_reduce_f16_kernel";
     }
+    if (t == GQ_Q5_K) return "none"; // (Q5_K never reaches the LDS-DMA GEMM: GQ_EUNSUPPORTED)
     return "gemm_kernel + gemm_reduce_f16_kernel";
 }

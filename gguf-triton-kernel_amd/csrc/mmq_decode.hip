@@ -156,7 +156,7 @@ __device__ __forceinline__ void act_from_lds(Act<F, NT> &a, const uint8_t *codes
         a.q[t][12] = c3.x; a.q[t][13] = c3.y; a.q[t][14] = c3.z; a.q[t][15] = c3.w;
         a.d[t][0] = sd[t * nb + b0];
         a.d[t][1] = has1 ? sd[t * nb + b1] : 0.f;
-        if constexpr (F == Q4_K) {
+        if constexpr (has_mins(F)) {
             a.s[t][0] = sx[t * nb + b0];
             a.s[t][1] = has1 ? sx[t * nb + b1] : 0.f;
         }
@@ -203,8 +203,9 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     uint8_t *ring = smem + wave * (NS * SLOT);
     uint8_t *codes = smem + RING;
     float *sd = (float *)(codes + NT * kp * (FP8 ? 2 : 1)); // FP8: quarter sums [NT][2*nb]
-    float *sx = sd + NT * nb; // Q4_K: s [NT][nb] (float); Q6_K: code sums [NT][2*nb] (int)
+    float *sx = sd + NT * nb; // Q4_K / Q5_K: s [NT][nb] (float); Q6_K: code sums [NT][2*nb] (int)
     static_assert(!FP8 || NT == 1 || ITC == 0, "fp8 decode: cached activations at one token only");
+    static_assert(!FP8 || F != Q5_K, "the fp8 variant has no Q5_K form");
     // FP8 at 2+ tokens: exact code pairs, no quarter sums (gguf_dot.hpp dot_unit_h NS; act_lds)
     constexpr bool F8NS = FP8 && NT >= 2;
     // FP8: x~ 16-byte piece P of a token row at piece P ^ ((P >> 4) & 7) (the lanes of a unit
@@ -322,7 +323,7 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
             if ((lane & 1) == 0) ((int *)sx)[t * 2 * nb + 2 * j + ((lane >> 1) & 1)] = qq.s4;
         if ((lane & 3) == 0) {
             sd[t * nb + j] = qq.d;
-            if constexpr (F == Q4_K) sx[t * nb + j] = h2f(qq.sbits);
+            if constexpr (has_mins(F)) sx[t * nb + j] = h2f(qq.sbits);
         }
     };
     auto store_f = [&](int b, const F8Quad &f, float ls) { // FP8: x~ and the lane pair's quarter sum
@@ -522,8 +523,8 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
         ((uint32_t *)&l)[0] = (uint32_t)(uintptr_t)rowp + u;
         ((uint32_t *)&l)[3] = (uint32_t)u * 77u;
 #else
-        // Q8_0: dword-aligned reads and a 2-byte shift (4096^2 decode 6.6 -> 5.6 us); Q4_K
-        // blocks are 16-byte aligned in the ring; Q6_K: see above
+        // Q8_0: dword-aligned reads and a 2-byte shift (4096^2 decode 6.6 -> 5.6 us); Q4_K and
+        // Q5_K blocks are 16-byte aligned in the ring; Q6_K: see above
         if constexpr (F == Q8_0) l.load_lds(rowp, u, nb);
         else if constexpr (IMG) l.load_img(rowp, u);
         else l.load(rowp, u, nb);
@@ -689,7 +690,8 @@ size_t act_lds(int fmt, int nt, int64_t K, bool fp8 = false)
     const int64_t kp = (K + 63) / 64 * 64, nb = K / 32;
     if (fp8) // x~ + quarter sums (2+ tokens: Q4_K's block sums only, gguf_dot.hpp dot_unit_h NS)
         return (size_t)nt * kp * 2 + (nt == 1 ? (size_t)nt * nb * 2 * 4 : (fmt == Q4_K ? (size_t)nt * nb * 4 : 0));
-    return (size_t)nt * kp + (size_t)nt * nb * 4 * (fmt == Q8_0 ? 1 : (fmt == Q4_K ? 2 : 3));
+    // codes + d (+ Q4_K / Q5_K: s; Q6_K: the two 16-element code sums)
+    return (size_t)nt * kp + (size_t)nt * nb * 4 * (fmt == Q8_0 ? 1 : (fmt == Q4_K || fmt == Q5_K ? 2 : 3));
 }
 
 // the largest cached-chunk count ITC instantiated for (format, token tile); the fp8 form caches
@@ -697,14 +699,16 @@ size_t act_lds(int fmt, int nt, int64_t K, bool fp8 = false)
 int fp8_itc_max(int fmt, int nt) { return nt == 1 ? (fmt == Q6_K ? 1 : 2) : 0; }
 int itc_max(int fmt, int nt)
 {
-    if (nt == 1) return fmt == Q6_K ? 4 : 7;
+    // (Q5_K: twice Q4_K's code registers per unit -- 7 cached units at one token spill)
+    if (nt == 1) return fmt == Q6_K ? 4 : (fmt == Q5_K ? 6 : 7);
     if (nt == 2) return fmt == Q6_K ? 1 : 4;
     return 1;
 }
 
+bool known_fmt(int fmt) { return fmt == Q8_0 || fmt == Q4_K || fmt == Q6_K || fmt == Q5_K; }
 int64_t row_bytes(int fmt, int64_t K)
 {
-    return fmt == Q8_0 ? K / 32 * 34 : (fmt == Q4_K ? K / 256 * 144 : K / 256 * 210);
+    return fmt == Q8_0 ? K / 32 * 34 : K / 256 * (fmt == Q4_K ? 144 : (fmt == Q5_K ? 176 : 210));
 }
 
 // wgs: the workgroups the matrix gets (0: a launch of its own, the whole chip; a grouped launch
@@ -713,6 +717,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
 {
     // at most 4 tokens per workgroup (NT = 8 spills registers); N = 5..8 runs two token groups,
     // whose second pass over the weights is served largely by the Infinity Cache
+    if (!known_fmt(fmt) || (p.fp8 && fmt == Q5_K)) return false; // (no Q5_K form of the fp8 variant)
     const int nts[3] = {1, 2, 4};
     p.nt = 4;
     for (int i = 0; i < 3; ++i)
@@ -756,7 +761,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
         while ((1 << lp2) < cpr && lp2 < 6) ++lp2;
         g.lp2 = lp2;
     } else {
-        const int64_t unit64 = fmt == Q8_0 ? 64 * 68 : (fmt == Q4_K ? 64 * 36 : 64 * (img ? kImgSB : 210) / 4);
+        const int64_t unit64 = fmt == Q8_0 ? 64 * 68 : (fmt == Q4_K ? 64 * 36 : (fmt == Q5_K ? 64 * 44 : 64 * (img ? kImgSB : 210) / 4));
         if (cap < unit64) return false; // a 64-unit segment must fit one task (tuning builds with small NI)
         g.G = 1;
         g.segu = (int)(64 * (cap / unit64));
@@ -769,7 +774,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
     const int64_t itc = (cpr + (1 << g.lp2) - 1) >> g.lp2, units = itc * (upr / cpr);
     p.itc = ((p.nt <= 2 && units <= (fmt == Q6_K ? 2 : 4)) || (p.nt == 1 && units <= 8)) ? (int)itc : 0;
     // only the instantiated chunk counts (launch_f, stream_decode_grouped_kernel): one token
-    // 0..7 (Q6_K 0..4), two 0..4 (Q6_K 0..1), four 0..1 -- e.g. K = 29568 at one token gives 8
+    // 0..7 (Q6_K 0..4, Q5_K 0..6), two 0..4 (Q6_K 0..1), four 0..1 -- e.g. K = 29568 at one token gives 8
     if (p.itc > itc_max(fmt, p.nt)) p.itc = 0;
     // four tokens, one unit per lane (K <= 4096): cached too (Q6_K 14336x4096 x4 27.7 -> 20.7 us,
     // profiles/r02/decode_nt4_cache_ab.txt)
@@ -807,7 +812,9 @@ hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *
 {
 #define GQ_LT(nt, itc) launch_t<F, nt, itc>(A, X, ldx, C, M, N, K, ldc, p, s)
 #define GQ_LTI(nt, itc) launch_t<F, nt, itc, 1>(A, X, ldx, C, M, N, K, ldc, p, s)
-    if (p.fp8) { // (itc: one token only, fp8_itc_max)
+    if constexpr (F == Q5_K)
+        if (p.fp8) return hipErrorInvalidValue;
+    if constexpr (F != Q5_K) if (p.fp8) { // (itc: one token only, fp8_itc_max)
         if (p.nt == 1 && p.itc == 1) {
             if constexpr (F == Q6_K)
                 if (p.img) return launch_t<F, 1, 1, 1, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
@@ -862,7 +869,9 @@ hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *
         case 12: return GQ_LT(1, 4);
         case 13: return GQ_LT(1, 5);
         case 14: return GQ_LT(1, 6);
-        case 15: return GQ_LT(1, 7);
+        case 15:
+            if constexpr (F != Q5_K) return GQ_LT(1, 7);
+            return hipErrorInvalidValue; // (itc_max: Q5_K caches at most 6 units)
 
         case 16: return GQ_LT(2, 0);
         case 17: return GQ_LT(2, 1);
@@ -899,9 +908,15 @@ struct GroupedArgs {
     GroupedProblem p[kMaxGroup];
 };
 
-template <int NT, int FP8 = 0>
+// Q5 = 1: the launch holds a Q5_K item.  A kernel of its own, so that the other formats' grouped
+// launches keep their case set (and register allocation) exactly; at one token it carries every
+// format's cases up to kQ5GroupItc cached chunks only -- with all of them the allocator spills
+// (kernel-resource-usage) -- and decode_grouped_ok refuses a mixed launch beyond that.
+constexpr int kQ5GroupItc = 4;
+template <int NT, int FP8 = 0, int Q5 = 0>
 __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const GroupedArgs args)
 {
+    static_assert(!(FP8 && Q5), "the fp8 variant has no Q5_K form");
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
     const int b = (int)blockIdx.x;
     int i = 0;
@@ -931,6 +946,14 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GF(Q8_0, 0, 0) GQ_GF(Q4_K, 0, 0) GQ_GF(Q6_K, 0, 0) GQ_GF(Q6_K, 0, 1)
         default: return;
         }
+    } else if constexpr (NT == 1 && Q5) { // (kQ5GroupItc)
+        switch (q.code) {
+            GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q8_0, 2) GQ_GB(Q8_0, 3) GQ_GB(Q8_0, 4) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1)
+            GQ_GB(Q4_K, 2) GQ_GB(Q4_K, 3) GQ_GB(Q4_K, 4) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GB(Q6_K, 2) GQ_GB(Q6_K, 3)
+            GQ_GB(Q6_K, 4) GQ_GBI(0) GQ_GBI(1) GQ_GBI(2) GQ_GBI(3) GQ_GBI(4)
+            GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1) GQ_GB(Q5_K, 2) GQ_GB(Q5_K, 3) GQ_GB(Q5_K, 4)
+        default: return;
+        }
     } else if constexpr (NT == 1) {
         switch (q.code) {
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q8_0, 2) GQ_GB(Q8_0, 3) GQ_GB(Q8_0, 4) GQ_GB(Q8_0, 5) GQ_GB(Q8_0, 6)
@@ -943,12 +966,20 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
         switch (q.code) {
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q8_0, 2) GQ_GB(Q8_0, 3) GQ_GB(Q8_0, 4) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1)
             GQ_GB(Q4_K, 2) GQ_GB(Q4_K, 3) GQ_GB(Q4_K, 4) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GBI(0) GQ_GBI(1)
-        default: return;
+        default: break;
+        }
+        if constexpr (Q5) switch (q.code) {
+            GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1) GQ_GB(Q5_K, 2) GQ_GB(Q5_K, 3) GQ_GB(Q5_K, 4)
+        default: break;
         }
     } else {
         switch (q.code) {
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GBI(0) GQ_GBI(1)
-        default: return;
+        default: break;
+        }
+        if constexpr (Q5) switch (q.code) {
+            GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1)
+        default: break;
         }
     }
 #undef GQ_GB
@@ -956,17 +987,17 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
 #undef GQ_GF
 }
 
-template <int NT, int FP8 = 0>
+template <int NT, int FP8 = 0, int Q5 = 0>
 hipError_t launch_grouped_nt(GroupedArgs &a, int blocks, size_t lds, hipStream_t s)
 {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_grouped_kernel<NT, FP8>,
+        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_grouped_kernel<NT, FP8, Q5>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    stream_decode_grouped_kernel<NT, FP8><<<dim3((unsigned)blocks), dim3(DW * 64), lds, s>>>(a);
+    stream_decode_grouped_kernel<NT, FP8, Q5><<<dim3((unsigned)blocks), dim3(DW * 64), lds, s>>>(a);
     return hipGetLastError();
 }
 
@@ -987,6 +1018,7 @@ bool decode_fused_ok(int fmt, int64_t N, int64_t K, bool fp8)
 hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, int64_t M,
                                int64_t N, int64_t K, int64_t ldc, hipStream_t s, bool fp8)
 {
+    if (!known_fmt(fmt)) return hipErrorInvalidValue;
     const int64_t RB = row_bytes(fmt, K);
     const int64_t max_rows = ((int64_t)1 << 31) / RB - 1; // rows per launch under 2 GiB
     for (int64_t m0 = 0; m0 < M; m0 += max_rows) {
@@ -998,7 +1030,9 @@ hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int
         switch (fmt) {
         case Q8_0: e = launch_f<Q8_0>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
         case Q4_K: e = launch_f<Q4_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        default: e = launch_f<Q6_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
+        case Q6_K: e = launch_f<Q6_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
+        case Q5_K: e = launch_f<Q5_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
+        default: return hipErrorInvalidValue;
         }
         if (e != hipSuccess) return e;
     }
@@ -1012,6 +1046,17 @@ bool decode_grouped_ok(const DecodeItem *items, int n, int64_t N, bool fp8)
         const DecodeItem &it = items[i];
         if (it.M < 1 || !decode_fused_ok(it.fmt, N, it.K, fp8)) return false;
         if (it.M * row_bytes(it.fmt, it.K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets
+    }
+    // a one-token launch with a Q5_K item: every item within the cached chunks its kernel carries
+    bool q5 = false;
+    for (int i = 0; i < n; ++i) q5 = q5 || items[i].fmt == Q5_K;
+    if (q5) {
+        if (fp8) return false;
+        for (int i = 0; i < n; ++i) {
+            Pick p;
+            if (!pick(items[i].fmt, items[i].M, N, items[i].K, p)) return false;
+            if (p.nt == 1 && p.itc > kQ5GroupItc) return false;
+        }
     }
     return true;
 }
@@ -1111,7 +1156,16 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
             blocks += p.grid;
         }
         a.n = np;
-        hipError_t e = fp8       ? (nt == 1 ? launch_grouped_nt<1, 1>(a, blocks, lds, s) : launch_grouped_nt<2, 1>(a, blocks, lds, s))
+        bool q5 = false;
+        for (int j = 0; j < np; ++j) q5 = q5 || items[pi[j]].fmt == Q5_K;
+        if (q5 && nt == 1)
+            for (int j = 0; j < np; ++j)
+                if (a.p[j].code % 8 > kQ5GroupItc) return hipErrorInvalidValue; // (decode_grouped_ok)
+        hipError_t e = q5        ? (fp8 ? hipErrorInvalidValue
+                                        : nt == 1 ? launch_grouped_nt<1, 0, 1>(a, blocks, lds, s)
+                                        : nt == 2 ? launch_grouped_nt<2, 0, 1>(a, blocks, lds, s)
+                                                  : launch_grouped_nt<4, 0, 1>(a, blocks, lds, s))
+                       : fp8       ? (nt == 1 ? launch_grouped_nt<1, 1>(a, blocks, lds, s) : launch_grouped_nt<2, 1>(a, blocks, lds, s))
                        : nt == 1 ? launch_grouped_nt<1>(a, blocks, lds, s)
                        : nt == 2 ? launch_grouped_nt<2>(a, blocks, lds, s)
                                  : launch_grouped_nt<4>(a, blocks, lds, s);

@@ -4,6 +4,7 @@
 //   Q8_0 w = d*q                                   (utils/quantize/q8_0.py:52-100)
 //   Q4_K w = d*sc_j*q - dmin*m_j                   (q4_k_ref.c:358-364, q4_k.py:125-158)
 //   Q6_K w = d*sc_{e/16}*(q - 32)                  (q6_k_ref.c:320-336, q6_k.py:117-159)
+//   Q5_K w = (d*sc_j)*q - (dmin*m_j), q = 0..31    (no reference: include/gguf_quant.h)
 // one thread per 32-element sub-block, 4 x 16-byte stores.  PERM stores each 4-element group
 // in the order (0,2,1,3) -- the order act_quant's DEQ form uses for x~ -- so a GEMM over
 // (W_perm, x~) sums the same products as over the natural order.
@@ -75,7 +76,29 @@ __global__ __launch_bounds__(256) void dequant_kernel(const uint8_t *__restrict_
         const int sh = 4 * (s & 1);
 #pragma unroll
         for (int i = 0; i < 32; ++i) w[i] = ds * (float)((byte_of(qw[i >> 2], i & 3) >> sh) & 0xf) - dm;
+    } else if constexpr (F == Q5_K) {
+        // sub-block s of the super-block: nibble 4*(s & 1) of qs bytes 32*(s >> 1).., bit s of qh
+        const uint8_t *b = rowp + 176 * (j >> 3);
+        const int s = (int)(j & 7);
+        const u32x4 hdr = ld16(b);
+        const float d = h2f(hdr.x & 0xffffu), dmin = h2f(hdr.x >> 16);
+        const uint32_t sw[3] = {hdr.y, hdr.z, hdr.w};
+        int sc, m;
+        q4k_sc_m(sw, s, sc, m);
+        const float ds = d * (float)sc, dm = dmin * (float)m;
+        const u32x4 h0 = ld16(b + 16), h1 = ld16(b + 32);
+        const u32x4 q0 = ld16(b + 48 + 32 * (s >> 1)), q1 = ld16(b + 64 + 32 * (s >> 1));
+        const uint32_t hw[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        const int sh = 4 * (s & 1);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const int lo = (byte_of(qw[i >> 2], i & 3) >> sh) & 0xf;
+            const int hi = (byte_of(hw[i >> 2], i & 3) >> s) & 1;
+            w[i] = ds * (float)(lo | (hi << 4)) - dm;
+        }
     } else {
+        static_assert(F == Q6_K, "dequant_kernel: unlisted format");
         // run jj = j & 7 of the super-block: elements 32*jj + i, i < 32 -> half h = jj >> 2,
         // ql bytes 64h + 32*(jj & 1) (nibble 4*((jj >> 1) & 1)), qh bytes 32h (bits 2*(jj & 3))
         const uint8_t *b = rowp + 210 * (j >> 3);
@@ -107,7 +130,9 @@ hipError_t dequant_perm(int fmt, const uint8_t *A, uint16_t *W, int64_t M, int64
     switch (fmt) {
     case Q8_0: dequant_kernel<Q8_0, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     case Q4_K: dequant_kernel<Q4_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    default: dequant_kernel<Q6_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
+    case Q6_K: dequant_kernel<Q6_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
+    case Q5_K: dequant_kernel<Q5_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
+    default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }

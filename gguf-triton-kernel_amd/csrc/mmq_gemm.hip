@@ -930,7 +930,8 @@ hipError_t launch_gemm(int fmt, const uint8_t *A, const GemmAct &x, uint16_t *C,
     switch (fmt) {
     case Q8_0: return launch_fmt<Q8_0>(A, x, C, P, plan, M, N, K, ldc, s);
     case Q4_K: return launch_fmt<Q4_K>(A, x, C, P, plan, M, N, K, ldc, s);
-    default: return launch_fmt<Q6_K>(A, x, C, P, plan, M, N, K, ldc, s);
+    case Q6_K: return launch_fmt<Q6_K>(A, x, C, P, plan, M, N, K, ldc, s);
+    default: return hipErrorInvalidValue; // (Q5_K has no LDS-DMA GEMM form: the streaming GEMM takes it)
     }
 }
 

@@ -75,6 +75,10 @@ constexpr int kSpol = 16; // split-K partial stores write-through (sc1)
 // hsrc<F>(h, pc):
 //   Q8_0  9 pieces from byte 128h (blocks 4h..4h+3 at image byte 8h..; 8 bytes of overlap)
 //   Q4_K  5 pieces: the 16-byte header, then qs bytes 64h..64h+63
+//   Q5_K  7 pieces: the header, the 32 qh bytes, then qs bytes 64h..64h+63 (streaming GEMM only).
+//         The 112-B stride is 28 dwords: the 16 rows of a fragment read start on banks 28r mod 64
+//         = {0, 4, ..., 60}, and a lane pair's two 8-byte reads (or one 16-byte header read) cover
+//         the 4 banks from there -- all 64 banks once, as Q4_K's 80-B stride (20 dwords): no padding
 //   Q6_K  8 pieces: ql 64h.. (4), qh 128+32h.. (2), bytes 192..207 (scales), 194..209 (d at image
 //         byte 126); a 128-B stride is 2 bank sets, so row r's pieces are XOR-permuted by r & 7
 //         (hpos_swz).  (Until round 5 a ninth padding piece made the stride 144 B instead; the 8
@@ -82,6 +86,7 @@ constexpr int kSpol = 16; // split-K partial stores write-through (sc1)
 template <int F> struct HImg;
 template <> struct HImg<Q8_0> { static constexpr int NPH = 9; };
 template <> struct HImg<Q4_K> { static constexpr int NPH = 5; };
+template <> struct HImg<Q5_K> { static constexpr int NPH = 7; };
 #ifndef GQ_Q6_NPH
 #define GQ_Q6_NPH 8 // (-DGQ_Q6_NPH=9: the padded image, A/B builds)
 #endif
@@ -96,6 +101,7 @@ template <int F> __device__ __forceinline__ uint32_t hsrc(int h, int pc)
 {
     if constexpr (F == Q8_0) return 128u * h + 16u * pc;
     if constexpr (F == Q4_K) return pc == 0 ? 0u : 16u + 64u * h + 16u * (pc - 1);
+    if constexpr (F == Q5_K) return pc < 3 ? 16u * pc : 48u + 64u * h + 16u * (pc - 3);
     return pc < 4 ? 64u * h + 16u * pc : (pc < 6 ? 128u + 32u * h + 16u * (pc - 4) : (pc == 6 ? 192u : 194u));
 }
 
@@ -162,6 +168,7 @@ template <int F> __device__ __forceinline__ void half_frags(const uint8_t *img, 
     const int h = u >> 1;
     if constexpr (F == Q8_0) stage_frags<Q8_0>(img - 128 * h, g, u, frag, 0); // (16-byte aligned: HRB = 144)
     else if constexpr (F == Q4_K) q4k_frags(img, img + 16 + 32 * (u & 1), g, u, frag);
+    else if constexpr (F == Q5_K) q5k_frags(img, img + 16, img + 48 + 32 * (u & 1), g, u, frag);
     else if constexpr (HImg<F>::NPH == 8) q6k_half_frags_swz(img, g, h, u & 1, hpos_swz<F>(r), frag);
     else q6k_half_frags(img, g, h, u & 1, frag);
 }
@@ -926,6 +933,7 @@ __global__ __launch_bounds__(64 * RW) void sgemm_kernel(const uint8_t *__restric
 template <int NB> constexpr int max_slds()
 {
     constexpr int a = SCfg<Q8_0, NB>::LDS, b = sgemm_lds<Q4_K, NB>(), c = SCfg<Q6_K, NB>::LDS;
+    static_assert(SCfg<Q5_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q5_K within the others' LDS");
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
@@ -953,7 +961,9 @@ __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
             }
             sgemm_body<Q4_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
             return;
-        default: sgemm_body<Q6_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
+        case Q6_K: sgemm_body<Q6_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
+        case Q5_K: sgemm_body<Q5_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
+        default: return; // (plan_sgemm_grouped admits the four formats only)
         }
     };
     if (!a.streamk) { // tile-granular splits: workgroup = (part, tile, split)
@@ -1199,7 +1209,8 @@ int rgemm_per_cu(int fmt, int nb)
     switch (fmt) {
     case Q8_0: GQ_RPC(Q8_0)
     case Q4_K: GQ_RPC(Q4_K)
-    default: GQ_RPC(Q6_K)
+    case Q6_K: GQ_RPC(Q6_K)
+    default: return 0; // (no resident form: Q5_K)
     }
 #undef GQ_RPC
 }
@@ -1266,7 +1277,9 @@ hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *
     switch (fmt) {
     case Q8_0: GQ_SG_NB(Q8_0)
     case Q4_K: GQ_SG_NB(Q4_K)
-    default: GQ_SG_NB(Q6_K)
+    case Q6_K: GQ_SG_NB(Q6_K)
+    case Q5_K: GQ_SG_NB(Q5_K)
+    default: return hipErrorInvalidValue;
     }
 #undef GQ_SG_NB
 }
@@ -1280,6 +1293,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
     int64_t units = 0, Lmax = 1;
     for (int i = 0; i < n; ++i) {
         if (items[i].M < 1 || items[i].K < 256 || items[i].K % 256 != 0) return g;
+        if (items[i].fmt != Q8_0 && items[i].fmt != Q4_K && items[i].fmt != Q6_K && items[i].fmt != Q5_K) return g;
         g.tiles_m[i] = (int)((items[i].M + RBM - 1) / RBM);
         const int64_t t = (int64_t)g.tiles_m[i] * tn, nsb = items[i].K / 256;
         units += t * nsb;
@@ -1310,7 +1324,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
         // (profiles/r05/sgemm_grouped_cost_ab.txt; -55, the K-chunked stream's best, 74.6 / 76.1 / 99.2)
         int64_t ctot = 0;
         for (int i = 0; i < n; ++i) {
-            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : 210);
+            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : (items[i].fmt == Q5_K ? 176 : 210));
             g.cstart[i] = (int)ctot;
             ctot += (int64_t)g.tiles_m[i] * tn * (items[i].K / 256) * g.cost[i];
         }
@@ -1437,7 +1451,8 @@ hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, in
     switch (fmt) {
     case Q8_0: GQ_RG_AQ(Q8_0)
     case Q4_K: GQ_RG_AQ(Q4_K)
-    default: GQ_RG_AQ(Q6_K)
+    case Q6_K: GQ_RG_AQ(Q6_K)
+    default: return hipErrorInvalidValue; // (no resident form: Q5_K)
     }
 #undef GQ_RG_AQ
 }

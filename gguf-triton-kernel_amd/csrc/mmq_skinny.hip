@@ -234,6 +234,10 @@ SkinnyPlan plan_skinny(int fmt, int64_t M, int64_t N, int64_t K, int rg, int d)
     SkinnyPlan p;
     p.nb = N <= 16 ? 1 : 2;
     p.d = 2;
+    if (fmt != Q8_0 && fmt != Q4_K && fmt != Q6_K) { // no plan: launch_skinny refuses rg = 0
+        p.rg = 0;
+        return p;
+    }
     // A unit (16*rg rows) reads all of x~ (N x K fp16): at 16 tokens 2-4x one fragment's weight
     // bytes, so more rows per unit cut the x~ traffic (L2), while the persistent grid's busiest
     // workgroup takes ceil(units / 256) units.  Cost of that workgroup in fragment-streams:
@@ -260,11 +264,12 @@ SkinnyPlan plan_skinny(int fmt, int64_t M, int64_t N, int64_t K, int rg, int d)
 hipError_t launch_skinny(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *C, const SkinnyPlan &plan, int64_t M,
                          int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    if (N < 1 || N > 32 || K % 256 != 0 || M < 1) return hipErrorInvalidValue;
+    if (N < 1 || N > 32 || K % 256 != 0 || M < 1 || plan.rg < 1) return hipErrorInvalidValue;
     switch (fmt) {
     case Q8_0: return launch_fmt<Q8_0>(A, X, C, plan, M, N, K, ldc, s);
     case Q4_K: return launch_fmt<Q4_K>(A, X, C, plan, M, N, K, ldc, s);
-    default: return launch_fmt<Q6_K>(A, X, C, plan, M, N, K, ldc, s);
+    case Q6_K: return launch_fmt<Q6_K>(A, X, C, plan, M, N, K, ldc, s);
+    default: return hipErrorInvalidValue; // (no Q5_K form)
     }
 }
 

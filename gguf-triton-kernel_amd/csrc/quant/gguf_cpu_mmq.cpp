@@ -9,6 +9,7 @@
 // and the fp16/fp32 roundings of that chain, and this file keeps both:
 //   Q8_0: term = fp16(fp16(dA*dB) * idot)                 (fp16 tensor * int32 tensor)
 //   Q4_K: term = ((d*sc)*dB)*idot - (dmin*m)*sB  in fp32   (the scalar is cast to fp16 first)
+//   Q5_K: Q4_K's term over codes 0..31 (no reference counterpart)
 //   Q6_K: term = dB*((d*sc_lo)*dot_lo + (d*sc_hi)*dot_hi) in fp32
 //   C = fp16(float(C) + float(fp16(term)))
 // (build with -ffp-contract=off: no fused multiply-adds).
@@ -96,6 +97,33 @@ void unpack_q4_k(const uint8_t *row, int64_t K, Row &r)
     }
 }
 
+// Q5_K: Q4_K's header, codes 0..31 (bit 4 of sub-block j's element i in bit j of qh[i])
+void unpack_q5_k(const uint8_t *row, int64_t K, Row &r)
+{
+    const auto &T = half_table();
+    for (int64_t sb = 0; sb < K / 256; ++sb) {
+        const uint8_t *b = row + 176 * sb;
+        const float d = T.v[ld16(b)], dmin = T.v[ld16(b + 2)];
+        const uint8_t *s = b + 4, *qh = b + 16, *qs = b + 48;
+        for (int j = 0; j < 8; ++j) {
+            int sc, mn;
+            if (j < 4) {
+                sc = s[j] & 63;
+                mn = s[j + 4] & 63;
+            } else {
+                sc = (s[j + 4] & 0x0f) | ((s[j - 4] >> 6) << 4);
+                mn = (s[j + 4] >> 4) | ((s[j] >> 6) << 4);
+            }
+            r.c0[8 * sb + j] = d * (float)sc;
+            r.c1[8 * sb + j] = dmin * (float)mn;
+            const uint8_t *src = qs + 32 * (j >> 1);
+            int8_t *dst = &r.q[256 * sb + 32 * j];
+            for (int i = 0; i < 32; ++i)
+                dst[i] = (int8_t)(((src[i] >> (4 * (j & 1))) & 0x0f) + 16 * ((qh[i] >> j) & 1));
+        }
+    }
+}
+
 void unpack_q6_k(const uint8_t *row, int64_t K, Row &r)
 {
     const auto &T = half_table();
@@ -165,16 +193,19 @@ void rows_q8_0(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N
     }
 }
 
+// (Q5 = true: Q5_K rows -- the same terms and fp16 running sum over 5-bit codes)
+template <bool Q5 = false>
 void rows_q4_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N, int64_t K, uint16_t *C)
 {
     const auto &T = half_table();
-    const int64_t nb = K / 32, row_bytes = (K / 256) * 144;
+    const int64_t nb = K / 32, row_bytes = (K / 256) * (Q5 ? 176 : 144);
     Row r;
     r.q.resize((size_t)K);
     r.c0.resize((size_t)nb);
     r.c1.resize((size_t)nb);
     for (int64_t m = m0; m < m1; ++m) {
-        unpack_q4_k(A + m * row_bytes, K, r);
+        if (Q5) unpack_q5_k(A + m * row_bytes, K, r);
+        else unpack_q4_k(A + m * row_bytes, K, r);
         for (int64_t n = 0; n < N; ++n) {
             const int8_t *xq = &x.q[n * K];
             const uint16_t *xd = &x.d[n * nb], *xs = &x.s[n * nb];
@@ -219,18 +250,19 @@ void rows_q6_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N
 extern "C" {
 
 // C (M, N) fp16 bits = the reference CPU MMQ of packed weights A (type 0 Q8_0, 1 Q4_K,
-// 2 Q6_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
+// 2 Q6_K, 3 Q5_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
 // Returns 0, or -1 for an unknown type / K not a whole number of blocks.
 int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int64_t K, uint16_t *C, int threads)
 {
     const int qk = type == 0 ? 32 : 256;
-    if (type < 0 || type > 2 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
+    if (type < 0 || type > 3 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
     if (M == 0 || N == 0) return 0;
     half_table();
     const Act x = unpack_act((const uint8_t *)B, N, K);
     auto run = [&](int64_t m0, int64_t m1) {
         if (type == 0) rows_q8_0((const uint8_t *)A, x, m0, m1, N, K, C);
-        else if (type == 1) rows_q4_k((const uint8_t *)A, x, m0, m1, N, K, C);
+        else if (type == 1) rows_q4_k<false>((const uint8_t *)A, x, m0, m1, N, K, C);
+        else if (type == 3) rows_q4_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);
         else rows_q6_k((const uint8_t *)A, x, m0, m1, N, K, C);
     };
     int64_t nt = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());

@@ -65,6 +65,14 @@ void gq_quantize_q4_k(const float *x, void *y, int64_t n)
     });
 }
 
+// x: n fp32 values (n % 256 == 0), y: n/256 * 176 bytes (Q5_K: include/gguf_quant.h).
+void gq_quantize_q5_k(const float *x, void *y, int64_t n)
+{
+    parallel_blocks(n / QK, [&](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) q5k_block(x + b * QK, (uint8_t *)y + b * 176);
+    });
+}
+
 // x: n fp32 values (n % 256 == 0), y: n/256 * 210 bytes.
 void gq_quantize_q6_k(const float *x, void *y, int64_t n)
 {
@@ -126,6 +134,31 @@ void gq_dequantize_q4_k(const void *y, float *out, int64_t nblocks)
             for (int i = 0; i < 32; ++i) {
                 uint8_t byte = qs[32 * (j >> 1) + i];
                 int q = (j & 1) ? (byte >> 4) : (byte & 0x0f);
+                out[256 * b + 32 * j + i] = ds * (float)q - dm;
+            }
+        }
+    }
+}
+
+// (d*sc_j)*q - (dmin*m_j) in fp32, in that order
+void gq_dequantize_q5_k(const void *y, float *out, int64_t nblocks)
+{
+    const uint8_t *p = (const uint8_t *)y;
+    for (int64_t b = 0; b < nblocks; ++b, p += 176) {
+        float d = h2f(get16(p)), dmin = h2f(get16(p + 2));
+        const uint8_t *sc = p + 4, *qh = p + 16, *qs = p + 48;
+        for (int j = 0; j < 8; ++j) {
+            int s6, m6;
+            if (j < 4) {
+                s6 = sc[j] & 63;
+                m6 = sc[j + 4] & 63;
+            } else {
+                s6 = (sc[j + 4] & 0x0f) | ((sc[j - 4] >> 6) << 4);
+                m6 = (sc[j + 4] >> 4) | ((sc[j] >> 6) << 4);
+            }
+            float ds = d * (float)s6, dm = dmin * (float)m6;
+            for (int i = 0; i < 32; ++i) {
+                int q = ((qs[32 * (j >> 1) + i] >> (4 * (j & 1))) & 0x0f) + 16 * ((qh[i] >> j) & 1);
                 out[256 * b + 32 * j + i] = ds * (float)q - dm;
             }
         }

@@ -7,6 +7,7 @@
 //
 //   q4k_block  <- (GGML) quantize_row_q4_K_ref / make_qkx2_quants, q4_k_ref.c:188-368
 //   q6k_block  <- (GGML) quantize_row_q6_K_ref / make_qx_quants, q6_k_ref.c:153-340
+//   q5k_block  (no reference; host only) q4k_block's search with 31 levels, Q5_K packing
 //   q8_block   <- utils/quantize/q8_0.py:4-49 (Q8_0), utils/quantize/q8_1.py:18-70 (Q8_1)
 #pragma once
 #include <algorithm>
@@ -54,9 +55,11 @@ GQ_QHD inline uint16_t get16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] 
 // ---------------- Q4_K ----------------
 // Weighted fit of x ~ scale * L + min over L in [0, nmax] (GGML make_qkx2_quants with
 // rmin=-1, rdelta=0.1, nstep=20, squared error).  Returns scale, writes -min to *neg_min.
+// NMAX: the largest code (15: Q4_K, 31: Q5_K).
+template <int NMAX = 15>
 GQ_QHD inline float fit_scale_min(const float *x, const float *w, uint8_t *L, uint8_t *Ltmp, float *neg_min)
 {
-    constexpr int n = 32, nmax = 15, nstep = 20;
+    constexpr int n = 32, nmax = NMAX, nstep = 20;
     constexpr float rmin = -1.f, rdelta = 0.1f;
     float lo = x[0], hi = x[0];
     float sw = w[0];
@@ -176,6 +179,73 @@ GQ_QHD inline void q4k_block(const float *x, uint8_t *blk)
     uint8_t *qs = blk + 16;
     for (int c = 0; c < 4; ++c)
         for (int l = 0; l < 32; ++l) qs[32 * c + l] = (uint8_t)(L[64 * c + l] | (L[64 * c + 32 + l] << 4));
+}
+
+// ---------------- Q5_K ----------------
+// Q4_K's producer with codes 0..31: the same per-sub-block scale / min search (fit_scale_min<31>),
+// the same 6-bit scale / min packing and header; the codes' low nibbles in qs [48:176] as Q4_K's,
+// bit 4 of sub-block j's element l in bit j of qh[l] [16:48].
+GQ_QHD inline void q5k_block(const float *x, uint8_t *blk)
+{
+    uint8_t L[QK], Ltmp[32];
+    float w[32], sub_scale[8], sub_min[8];
+    float max_scale = 0, max_min = 0;
+    for (int j = 0; j < 8; ++j) {
+        const float *xs = x + 32 * j;
+        float ss = 0;
+        for (int l = 0; l < 32; ++l) ss += xs[l] * xs[l];
+        float rms = std::sqrt(ss / 32);
+        for (int l = 0; l < 32; ++l) w[l] = rms + std::fabs(xs[l]);
+        sub_scale[j] = fit_scale_min<31>(xs, w, L + 32 * j, Ltmp, &sub_min[j]);
+        if (sub_scale[j] > max_scale) max_scale = sub_scale[j];
+        if (sub_min[j] > max_min) max_min = sub_min[j];
+    }
+    float inv_s = max_scale > 0 ? 63.f / max_scale : 0.f;
+    float inv_m = max_min > 0 ? 63.f / max_min : 0.f;
+    uint8_t *sc = blk + 4;
+    __builtin_memset(sc, 0, 12);
+    for (int j = 0; j < 8; ++j) {
+        uint8_t ls = (uint8_t)round_magic(inv_s * sub_scale[j]);
+        uint8_t lm = (uint8_t)round_magic(inv_m * sub_min[j]);
+        ls = std::min<uint8_t>(63, ls);
+        lm = std::min<uint8_t>(63, lm);
+        if (j < 4) {
+            sc[j] = ls;
+            sc[j + 4] = lm;
+        } else {
+            sc[j + 4] = (uint8_t)((ls & 0x0f) | ((lm & 0x0f) << 4));
+            sc[j - 4] |= (uint8_t)((ls >> 4) << 6);
+            sc[j] |= (uint8_t)((lm >> 4) << 6);
+        }
+    }
+    uint16_t dh = f2h(max_scale / 63.f), mh = f2h(max_min / 63.f);
+    put16(blk, dh);
+    put16(blk + 2, mh);
+    for (int j = 0; j < 8; ++j) {
+        int s6, m6;
+        if (j < 4) {
+            s6 = sc[j] & 63;
+            m6 = sc[j + 4] & 63;
+        } else {
+            s6 = (sc[j + 4] & 0x0f) | ((sc[j - 4] >> 6) << 4);
+            m6 = (sc[j + 4] >> 4) | ((sc[j] >> 6) << 4);
+        }
+        float d = h2f(dh) * s6;
+        if (!d) continue;
+        float dm = h2f(mh) * m6;
+        for (int i = 0; i < 32; ++i) {
+            int l = round_magic((x[32 * j + i] + dm) / d);
+            L[32 * j + i] = (uint8_t)std::max(0, std::min(31, l));
+        }
+    }
+    uint8_t *qh = blk + 16, *qs = blk + 48;
+    __builtin_memset(qh, 0, 32);
+    for (int c = 0; c < 4; ++c)
+        for (int l = 0; l < 32; ++l) {
+            const uint8_t a = L[64 * c + l], b = L[64 * c + 32 + l];
+            qs[32 * c + l] = (uint8_t)((a & 0x0f) | ((b & 0x0f) << 4));
+            qh[l] |= (uint8_t)(((a >> 4) << (2 * c)) | ((b >> 4) << (2 * c + 1)));
+        }
 }
 
 // ---------------- Q6_K ----------------

@@ -1,4 +1,4 @@
-"""The Q4_K_M layer-type mix of a Llama block (BASELINE.json configs[4]).
+"""The Q4_K_M (and Q5_K_M) layer-type mix of a Llama block (BASELINE.json configs[4]).
 
 llama.cpp's Q4_K_M recipe (not in the reference): every weight Q4_K except attn_v and
 ffn_down, which are Q6_K on a subset of layers -- the first eighth, the last eighth and every
@@ -20,3 +20,9 @@ def q4_k_m_layer_types(layer: int, n_layers: int = 32):
     """{projection: gguf type} of layer `layer` of an n_layers model under Q4_K_M."""
     hi = "q6_k" if _more_bits(layer, n_layers) else "q4_k"
     return {name: (hi if name in ("attn_v", "ffn_down") else "q4_k") for name in LLAMA_LAYER_SHAPES}
+
+
+def q5_k_m_layer_types(layer: int, n_layers: int = 32):
+    """{projection: gguf type} of layer `layer` under Q5_K_M: Q4_K_M's rule with q5_k as the base type."""
+    hi = "q6_k" if _more_bits(layer, n_layers) else "q5_k"
+    return {name: (hi if name in ("attn_v", "ffn_down") else "q5_k") for name in LLAMA_LAYER_SHAPES}

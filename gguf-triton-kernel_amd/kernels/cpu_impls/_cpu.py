@@ -1,4 +1,4 @@
-"""Shared body of the three cpu_impls functions (ctypes -> gq_cpu_mmq)."""
+"""Shared body of the cpu_impls functions (ctypes -> gq_cpu_mmq)."""
 from __future__ import annotations
 
 import ctypes
@@ -8,8 +8,8 @@ import torch
 
 from utils.quantize._qlib import lib as _qlib
 
-_BYTES = {0: 34, 1: 144, 2: 210}
-_QK = {0: 32, 1: 256, 2: 256}
+_BYTES = {0: 34, 1: 144, 2: 210, 3: 176}
+_QK = {0: 32, 1: 256, 2: 256, 3: 256}
 
 
 def cpu_mmq(gtype: int, A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, threads: int = 0) -> torch.Tensor:

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import numpy as np
 
-BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210)}
+BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176)}
 
 
 def _scales(rng, n):
@@ -28,7 +28,7 @@ def random_blocks(fmt: str, M: int, K: int, seed: int = 0) -> np.ndarray:
         d = _scales(rng, nb)
         u16[:, 0] = d & 0xFF
         u16[:, 1] = d >> 8
-    elif fmt == "q4_k":
+    elif fmt in ("q4_k", "q5_k"):
         d, dm = _scales(rng, nb), _scales(rng, nb)
         u16[:, 0], u16[:, 1] = d & 0xFF, d >> 8
         u16[:, 2], u16[:, 3] = dm & 0xFF, dm >> 8

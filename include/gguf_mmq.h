@@ -30,7 +30,15 @@
 extern "C" {
 #endif
 
-typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2 } gq_type;
+/* GQ_Q5_K (GGML type 13; the reference has none): 256 weights in 176 bytes, little endian --
+ *   [0:2] d fp16 | [2:4] dmin fp16 | [4:16] 12 scale bytes (Q4_K's 6-bit sc_j / m_j, get_scale_min_k4)
+ *   | [16:48] qh[32] | [48:176] qs[128];  element e, j = e / 32, l = e % 32:
+ *   q = ((qs[32*(j/2) + l] >> 4*(j&1)) & 15) + 16*((qh[l] >> j) & 1),  w = d*sc_j*q - dmin*m_j.
+ * q8_1 activations only: the fp8 variant (gq_*_ex with GQ_ACT_FP8_E4M3), gq_quantize_weights and
+ * gq_mmq_grouped[_ex] at 5..32 tokens answer GQ_EUNSUPPORTED for it and launch nothing.
+ * gq_version() did not change with it: a caller detects Q5_K by gq_block_bytes(GQ_Q5_K) == 176
+ * (a library without it answers 210). */
+typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3 } gq_type;
 
 /* How the activations are quantized before the matmul.
  *   GQ_ACT_Q8_1      the reference's semantics: q8_1 (int8 per 32 elements, utils/quantize/q8_1.py).
@@ -49,7 +57,7 @@ enum {
     GQ_EUNSUPPORTED = 3 /* valid but not implemented (unknown type) */
 };
 
-/* Elements per block (32 / 256 / 256) and bytes per block (34 / 144 / 210). */
+/* Elements per block (32 / 256 / 256 / 256) and bytes per block (34 / 144 / 210 / 176). */
 int gq_block_elems(gq_type t);
 int gq_block_bytes(gq_type t);
 
@@ -128,6 +136,7 @@ int gq_act_prepare_grouped(gq_act act, const gq_prep_item *items, int n, void *s
 /*
  * Dequantize packed `t` weights to fp16: W[m * ldw + k] = w (the reference's block formulas,
  * utils/quantize/{q8_0,q4_k,q6_k}.py dequantize, evaluated in fp32, rounded once to fp16).
+ * GQ_Q5_K: (d*sc_j)*q - (dmin*m_j), the formula above, in that order.
  * M rows of K (a multiple of the block) elements.  gq_mmq uses the same kernel for its
  * library-GEMM path (N >= a few hundred tokens: fp16 W + hipBLASLt).
  */
@@ -152,6 +161,7 @@ int gq_quantize_fp8(const void *X, void *codes, void *scales, int64_t rows, int6
  *   GQ_Q8_0: X = n fp16 values (n % 32 == 0)  -> Y = n/32 blocks of 34 bytes (quantize_to_q8_0)
  *   GQ_Q4_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 144 bytes (quantize_to_q4_k)
  *   GQ_Q6_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 210 bytes (quantize_to_q6_k)
+ * GQ_Q5_K: GQ_EUNSUPPORTED (host only: include/gguf_quant.h gq_quantize_q5_k).
  * X is read as flat blocks (a row-major (M, K) matrix gives the packed A of gq_mmq).  One thread
  * per block runs the host producer's exact code; no host sync.
  */
