@@ -194,6 +194,23 @@ struct DecodeItem {
 bool decode_grouped_ok(const DecodeItem *items, int n, int64_t N, bool fp8 = false);
 hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipStream_t s, bool fp8 = false);
 
+// Expert-indexed decode (mmq_decode.hip; llama.cpp's mul_mat_id at decode): pairs = N*S (token,
+// slot) pairs, pair p = n*S + s multiplying expert ids[p] (int32 in device memory, read by the
+// kernel) of the E packed M x K matrices at A by the fp16 row B + n*ldb + s*ldb_slot into
+// C + p*ldc; each pair's M outputs are the bits of its own one-token launch_decode_fused, an id
+// outside [0, E) gives M zeros.  One launch, q8_1 activations only, no workspace.
+// kMaxIdPairs: every pair streams its expert's weights on its own share of the chip, so two pairs
+// that pick one expert read it twice; up to 8 tokens x top-8 that costs less than sorting the
+// pairs would, beyond it pairs sharing an expert should share one weight stream (a sorted GEMM,
+// not this kernel).  decode_id_ok: pairs <= kMaxIdPairs, the one-token fused decode fits
+// (decode_fused_ok(fmt, 1, K)) and one expert is < 2 GiB (32-bit buffer offsets; the whole tensor
+// may be larger) -- else the caller falls back.
+constexpr int kMaxIdPairs = 64;
+bool decode_id_ok(int fmt, int64_t M, int64_t pairs, int64_t K);
+hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const uint16_t *B, uint16_t *C, int64_t E,
+                            int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc,
+                            hipStream_t s);
+
 // K-chunked streaming MMQ (mmq_kstream.hip, 5..32 tokens): x~ in VGPRs (each of a workgroup's
 // 8 waves one K chunk), weights streamed per wave through private LDS rings, the waves' tiles
 // summed in LDS: one launch, no partials for K <= 4096.  A longer K is cut into ranges of 16

@@ -1094,6 +1094,35 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
     return GQ_OK;
 }
 
+int gq_mmq_id(gq_type t, const void *A, const int32_t *ids, const void *B, void *C, int64_t E, int64_t M, int64_t N,
+              int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc, void *stream)
+{
+    g_err.clear();
+    int rc = check_common(t, M, N, K);
+    if (rc != GQ_OK) return rc;
+    if ((rc = check_pair(t, GQ_ACT_Q8_1)) != GQ_OK) return rc;
+    if (S < 0 || E < 0) return fail(GQ_EINVAL, "negative size S=%lld E=%lld", (long long)S, (long long)E);
+    if (M == 0 || N == 0 || S == 0) return GQ_OK;
+    if (K == 0) return fail(GQ_EINVAL, "K must be positive");
+    if (E == 0) return fail(GQ_EINVAL, "E must be positive");
+    if (!A || !ids || !B || !C) return fail(GQ_EINVAL, "null pointer (A=%p ids=%p B=%p C=%p)", A, (const void *)ids, B, C);
+    if (ldc < M) return fail(GQ_EINVAL, "ldc=%lld < M=%lld", (long long)ldc, (long long)M);
+    if (ldb < K) return fail(GQ_EINVAL, "ldb=%lld < K=%lld", (long long)ldb, (long long)K);
+    if (ldb_slot != 0 && ldb_slot < K)
+        return fail(GQ_EINVAL, "ldb_slot=%lld is neither 0 (shared row) nor >= K=%lld", (long long)ldb_slot, (long long)K);
+    // (activation rows: no alignment beyond fp16's -- the decode prologue's 16-byte loads take any
+    // address, and gq_mmq_ex's fused-decode route asks none)
+    if (N > gq::kMaxIdPairs || S > gq::kMaxIdPairs || !gq::decode_id_ok(t, M, N * S, K) || E > INT32_MAX)
+        return fail(GQ_EUNSUPPORTED,
+                    "not an expert-indexed decode shape (N=%lld x S=%lld pairs, at most %d; K=%lld must fit the "
+                    "one-token decode; one expert < 2 GiB)",
+                    (long long)N, (long long)S, gq::kMaxIdPairs, (long long)K);
+    hipError_t e = gq::launch_decode_id(t, (const uint8_t *)A, ids, (const uint16_t *)B, (uint16_t *)C, E, M, N, S, K, ldb,
+                                        ldb_slot, ldc, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (id decode): %s", hipGetErrorString(e));
+    return GQ_OK;
+}
+
 // gq_mmq_grouped_prepared: the items as the grouped streaming GEMM takes them, or a GQ_* error
 static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int64_t N, gq::SGroupItem *out)
 {

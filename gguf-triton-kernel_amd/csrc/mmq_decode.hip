@@ -1001,6 +1001,88 @@ hipError_t launch_grouped_nt(GroupedArgs &a, int blocks, size_t lds, hipStream_t
     return hipGetLastError();
 }
 
+// ---- expert-indexed decode (mul_mat_id): P = N*S (token, slot) pairs of one type, M and K ----
+// Pair p = n*S + s multiplies expert ids[p]'s matrix (E of them back to back at A, expert_bytes
+// apart) by its activation row B + n*ldb + s*ldb_slot into C + p*ldc.  Every pair gets gx
+// workgroups and the same geometry; the expert index is read on the device (workgroup-uniform: a
+// scalar load), so the host never sees it.  The body is the one-token decode's -- the row's
+// activations q8_1-quantized in the workgroup's prologue, no workspace -- and a row's arithmetic
+// depends on F, NT and K only, so a pair's outputs are the bits of its own one-token launch.
+// An id outside [0, E) reads no weights: the pair's workgroups write its M zeros.
+// One kernel per (F, ITC, IM) -- a switch over the cases in one kernel spills (kQ5GroupItc).
+struct IdArgs {
+    const uint8_t *A;
+    const int32_t *ids;
+    const uint16_t *B;
+    uint16_t *C;
+    int64_t expert_bytes, ldb, ldb_slot, ldc;
+    int E, M, K, S, gx;
+    DecodeGeom geo;
+};
+
+template <int F, int ITC, int IM>
+__global__ __launch_bounds__(DW * 64) void stream_decode_id_kernel(const IdArgs a)
+{
+    extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
+    const int p = (int)blockIdx.x / a.gx, bx = (int)blockIdx.x - p * a.gx;
+    const int e = __builtin_amdgcn_readfirstlane(a.ids[p]);
+    uint16_t *Cp = a.C + (int64_t)p * a.ldc;
+    if (e < 0 || e >= a.E) {
+        for (int m = bx * (DW * 64) + (int)threadIdx.x; m < a.M; m += a.gx * (DW * 64)) Cp[m] = 0;
+        return;
+    }
+    const int n = p / a.S, s = p - n * a.S;
+    decode_body<F, 1, ITC, IM>(a.A + (int64_t)e * a.expert_bytes, a.B + (int64_t)n * a.ldb + (int64_t)s * a.ldb_slot,
+                               a.ldb, Cp, a.M, 1, a.K, a.ldc, a.geo, bx, a.gx, 0, smem);
+}
+
+template <int F, int ITC, int IM = 0>
+hipError_t launch_id_t(const IdArgs &a, int pairs, size_t lds, hipStream_t s)
+{
+    static bool attr = false; // raise the dynamic LDS limit once per instantiation
+    if (!attr) {
+        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_id_kernel<F, ITC, IM>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    stream_decode_id_kernel<F, ITC, IM><<<dim3((unsigned)(pairs * a.gx)), dim3(DW * 64), lds, s>>>(a);
+    return hipGetLastError();
+}
+
+// launch_f's one-token cases (itc_max: Q8_0 / Q4_K 0..7, Q5_K 0..6, Q6_K 0..4 packed and image)
+template <int F>
+hipError_t launch_id_f(const IdArgs &a, int pairs, const Pick &p, hipStream_t s)
+{
+#define GQ_LID(itc, im) launch_id_t<F, itc, im>(a, pairs, p.lds, s)
+    if constexpr (F == Q6_K) {
+        if (p.img) switch (p.itc) {
+            case 0: return GQ_LID(0, 1);
+            case 1: return GQ_LID(1, 1);
+            case 2: return GQ_LID(2, 1);
+            case 3: return GQ_LID(3, 1);
+            case 4: return GQ_LID(4, 1);
+            default: return hipErrorInvalidValue;
+            }
+    }
+    switch (p.itc) {
+    case 0: return GQ_LID(0, 0);
+    case 1: return GQ_LID(1, 0);
+    case 2: return GQ_LID(2, 0);
+    case 3: return GQ_LID(3, 0);
+    case 4: return GQ_LID(4, 0);
+    default: break;
+    }
+    if constexpr (F != Q6_K) {
+        if (p.itc == 5) return GQ_LID(5, 0);
+        if (p.itc == 6) return GQ_LID(6, 0);
+        if constexpr (F != Q5_K)
+            if (p.itc == 7) return GQ_LID(7, 0);
+    }
+#undef GQ_LID
+    return hipErrorInvalidValue; // (pick() caps itc at itc_max)
+}
+
 } // namespace
 
 bool decode_fused_ok(int fmt, int64_t N, int64_t K, bool fp8)
@@ -1172,6 +1254,51 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+bool decode_id_ok(int fmt, int64_t M, int64_t pairs, int64_t K)
+{
+    if (pairs < 1 || pairs > kMaxIdPairs || M < 1 || !known_fmt(fmt)) return false;
+    if (M * row_bytes(fmt, K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets within one expert
+    return decode_fused_ok(fmt, 1, K);
+}
+
+hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const uint16_t *B, uint16_t *C, int64_t E,
+                            int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc,
+                            hipStream_t s)
+{
+    const int64_t pairs = N * S;
+    if (!decode_id_ok(fmt, M, pairs, K) || E < 1 || E > INT32_MAX) return hipErrorInvalidValue;
+    // the chip's workgroups shared evenly by the pairs (the grouped launcher's budget; every pair
+    // streams the same bytes), one workgroup each at least; the tile is the one-token launch's
+    Pick solo, p;
+    if (!pick(fmt, M, 1, K, solo)) return hipErrorInvalidValue;
+    const int per_cu = (int)(LDS_CAP / solo.lds) > 0 ? (int)(LDS_CAP / solo.lds) : 1;
+    const int64_t budget = (int64_t)num_cus() * per_cu;
+    const int wgs = (int)(budget / pairs > 1 ? budget / pairs : 1);
+    if (!pick(fmt, M, 1, K, p, wgs) || p.nt != 1 || p.itc != solo.itc || p.img != solo.img) return hipErrorInvalidValue;
+    IdArgs a{};
+    a.A = A;
+    a.ids = ids;
+    a.B = B;
+    a.C = C;
+    a.expert_bytes = M * row_bytes(fmt, K);
+    a.ldb = ldb;
+    a.ldb_slot = ldb_slot;
+    a.ldc = ldc;
+    a.E = (int)E;
+    a.M = (int)M;
+    a.K = (int)K;
+    a.S = (int)S;
+    a.gx = p.grid;
+    a.geo = p.geo;
+    switch (fmt) {
+    case Q8_0: return launch_id_f<Q8_0>(a, (int)pairs, p, s);
+    case Q4_K: return launch_id_f<Q4_K>(a, (int)pairs, p, s);
+    case Q6_K: return launch_id_f<Q6_K>(a, (int)pairs, p, s);
+    case Q5_K: return launch_id_f<Q5_K>(a, (int)pairs, p, s);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 } // namespace gq

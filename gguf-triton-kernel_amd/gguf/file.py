@@ -40,7 +40,8 @@ class GGUFTensor:
 
     @property
     def shape(self):
-        """(M, K): rows x elements per row (reverse of the GGUF dims)."""
+        """(M, K): rows x elements per row (reverse of the GGUF dims); a 3-D expert tensor
+        (dims (K, M, E)) gives (E, M, K), expert e's packed M x K matrix at byte e * M * row bytes."""
         return tuple(reversed(self.dims))
 
     def to_device(self, device="cuda"):
@@ -134,7 +135,9 @@ def _w_val(f, v):
 
 
 def write_gguf(path, tensors, metadata=None, alignment=32):
-    """Write a GGUF v3 file.  tensors: {name: (type_name, (M, K), raw bytes ndarray)}."""
+    """Write a GGUF v3 file.  tensors: {name: (type_name, (M, K), raw bytes ndarray)}; a shape
+    (E, M, K) writes the 3-D tensor of E expert matrices back to back (GGUF dims (K, M, E), as
+    blk.L.ffn_*_exps.weight of a mixture-of-experts model)."""
     metadata = dict(metadata or {})
     metadata.setdefault("general.alignment", alignment)
     with open(path, "wb") as f:
@@ -145,13 +148,17 @@ def write_gguf(path, tensors, metadata=None, alignment=32):
             _w_val(f, v)
         off = 0
         blobs = []
-        for name, (tname, (M, K), raw) in tensors.items():
+        for name, (tname, shape, raw) in tensors.items():
+            if len(shape) not in (2, 3):
+                raise ValueError(f"{name}: shape {tuple(shape)} is neither (M, K) nor (E, M, K)")
+            M, K = shape[-2:]
+            E = shape[0] if len(shape) == 3 else 1
             _, qk, bb = GGML_TYPES[TYPE_IDS[tname]]
             raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
-            assert raw.size == M * K // qk * bb, f"{name}: {raw.size} bytes for {tname} {M}x{K}"
+            assert raw.size == E * M * K // qk * bb, f"{name}: {raw.size} bytes for {tname} {'x'.join(map(str, shape))}"
             _w_str(f, name)
-            f.write(struct.pack("<I", 2))
-            f.write(struct.pack("<QQ", K, M))
+            f.write(struct.pack("<I", len(shape)))
+            f.write(struct.pack(f"<{len(shape)}Q", *reversed(shape)))
             f.write(struct.pack("<IQ", TYPE_IDS[tname], off))
             blobs.append((off, raw))
             off = (off + raw.size + alignment - 1) // alignment * alignment

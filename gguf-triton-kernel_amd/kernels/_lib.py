@@ -66,6 +66,7 @@ SIGNATURES = {
     "gq_mmq_sharded": ([_I, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I, _I, _P, _P, _SZ, _P], _I),
     "gq_mmq_grouped": ([ctypes.POINTER(GroupItem), _I, _I64, _P], _I),
     "gq_mmq_grouped_ex": ([_I, ctypes.POINTER(GroupItem), _I, _I64, _P], _I),
+    "gq_mmq_id": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_mmq_grouped_prepared_workspace_size": ([_I, ctypes.POINTER(GemmItem), _I, _I64], _SZ),
@@ -313,6 +314,88 @@ def mmq_grouped(items, N: int, act: str = "q8_1"):
         return None
     _check(rc)
     return outs
+
+
+def pairs_by_expert(ids_np, E: int) -> dict:
+    """{expert: indices of the (token, slot) pairs that chose it, ascending} for the flattened
+    (N, S) id array; experts no pair chose are absent, ids outside [0, E) are dropped."""
+    flat = [int(v) for v in ids_np.reshape(-1)]
+    groups = {}
+    for p, e in enumerate(flat):
+        if 0 <= e < E:
+            groups.setdefault(e, []).append(p)
+    return groups
+
+
+def mmq_id(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: int, M: int, K: int,
+           out: torch.Tensor | None = None) -> torch.Tensor:
+    """Expert-indexed MMQ (gq_mmq_id; llama.cpp's mul_mat_id): A = E packed (M, K) matrices back to
+    back (a GGUF 3-D expert tensor as stored), ids an (N, S) int32 DEVICE tensor of expert choices,
+    B fp16 (N, K) -- the S slots of a token share its row (gate / up) -- or (N, S, K) -- one row
+    per slot (down).  Returns (N, S, M) fp16: row (n, s) is bit-identical to
+    mmq(gtype, A[expert ids[n, s]], that row, M, 1, K); an id outside [0, E) gives a zero row.
+    One launch that reads the ids on the device: no host sync, graph-capturable.
+    When the library refuses the shape (GQ_EUNSUPPORTED: more than 64 pairs, a K whose decode
+    does not fit, an expert of 2 GiB or more) the call falls back to a host-sorted path: the ids
+    are copied to the host (this SYNCHRONISES and cannot be captured in a graph), and every
+    expert some pair chose runs one mmq() over its pairs' gathered rows."""
+    _require_device(A, "A")
+    _require_device(ids, "ids")
+    _require_device(B, "B")
+    qk, bb = BLOCK_ELEMS[gtype], BLOCK_BYTES[gtype]
+    if A.dtype not in (torch.int8, torch.uint8) or not A.is_contiguous():
+        raise RuntimeError("A must be the contiguous packed int8/uint8 expert tensor")
+    ebytes = M * (K // qk) * bb
+    if A.numel() != E * ebytes:
+        raise RuntimeError(f"A has {A.numel()} bytes, expected E*M*K/{qk}*{bb} = {E * ebytes}")
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise RuntimeError("ids must be a contiguous (N, S) int32 tensor")
+    N, S = ids.shape
+    dev = A.device
+    if ids.device != dev or B.device != dev:
+        raise RuntimeError("A, ids and B must share one device")
+    if B.dtype != torch.float16:
+        B = B.to(torch.float16)
+    if B.dim() == 2 and tuple(B.shape) == (N, K):
+        per_slot = False
+    elif B.dim() == 3 and tuple(B.shape) == (N, S, K):
+        per_slot = True
+    else:
+        raise RuntimeError(f"B is {tuple(B.shape)}, expected ({N}, {K}) or ({N}, {S}, {K})")
+    # the ABI's strides: rows of unit element stride, ldb >= K, ldb_slot >= K (or 0: shared)
+    if N * S > 0 and (B.stride(-1) != 1 or (N > 1 and B.stride(0) < K) or
+                      (per_slot and S > 1 and B.stride(1) < K)):
+        B = B.contiguous()
+    ldb = max(B.stride(0), K)
+    ldb_slot = max(B.stride(1), K) if per_slot else 0
+    C = out if out is not None else torch.empty((N, S, M), dtype=torch.float16, device=dev)
+    if C.dtype != torch.float16 or tuple(C.shape) != (N, S, M) or C.device != dev:
+        raise RuntimeError(f"out must be an fp16 ({N}, {S}, {M}) tensor on A's device")
+    if N * S * M == 0:
+        return C
+    # pair p = n*S + s writes at element p*ldc: rows evenly spaced, ldc >= M apart
+    ldc = C.stride(1) if S > 1 else (C.stride(0) if N > 1 else M)
+    if (M > 1 and C.stride(2) != 1) or ldc < M or (S > 1 and N > 1 and C.stride(0) != S * ldc):
+        raise RuntimeError("out rows must have unit element stride and be evenly spaced, at least M apart")
+    with torch.cuda.device(dev):
+        rc = lib().gq_mmq_id(gtype, A.data_ptr(), ids.data_ptr(), B.data_ptr(), C.data_ptr(), E, M, N, S, K, ldb,
+                             ldb_slot, ldc, _stream(dev))
+    if rc != GQ_EUNSUPPORTED:
+        _check(rc)
+        return C
+    # host-sorted fallback (synchronises: ids.cpu())
+    experts = A.reshape(E, ebytes)
+    rows = B.reshape(N * S, K) if per_slot else None
+    flat = C.view(N * S, M) if C.is_contiguous() else None
+    res = flat if flat is not None else torch.empty((N * S, M), dtype=torch.float16, device=dev)
+    res.zero_()  # pairs whose id is out of range
+    for e, pairs in pairs_by_expert(ids.cpu().numpy(), E).items():
+        idx = torch.tensor(pairs, dtype=torch.int64, device=dev)
+        x = rows.index_select(0, idx) if per_slot else B.index_select(0, idx // S)
+        res.index_copy_(0, idx, mmq(gtype, experts[e], x, M, len(pairs), K))
+    if flat is None:
+        C.copy_(res.view(N, S, M))
+    return C
 
 
 def mmq_grouped_prepared(items, N: int, act: str = "q8_1"):

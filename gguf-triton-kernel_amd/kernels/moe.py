@@ -1,0 +1,61 @@
+"""Mixture-of-experts FFN block (Mixtral, Qwen-MoE, DeepSeek GGUF checkpoints) at decode.
+
+A MoE model stores each FFN projection as ONE 3-D tensor of E expert matrices,
+blk.<L>.ffn_{gate,up,down}_exps.weight with GGUF dims (K, M, E): E packed M x K matrices back
+to back.  The router picks S experts per token and leaves the choices in device memory; the
+expert-indexed MMQ (gq_mmq_id, kernels._lib.mmq_id) reads them there, so a block is three
+launches and a little torch glue, with no host sync (graph-capturable up to 64 (token, slot)
+pairs; beyond that mmq_id falls back to a host-sorted path that synchronises).  No reference
+counterpart: the reference multiplies one dense matrix per call.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+
+
+class GGUFExperts:
+    """E packed GGUF weights (M rows of K elements each) on the device, multiplied by index:
+    y[n, s] = x_row(n, s) @ W[ids[n, s]]^T."""
+
+    def __init__(self, type_name: str, A: torch.Tensor, E: int, M: int, K: int):
+        self.type_name, self.gtype = type_name, _lib.TYPES[type_name]
+        self.A, self.E, self.M, self.K = A, E, M, K
+
+    def __call__(self, x: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+        """x (N, K): every slot of token n reads row n; x (N, S, K): one row per slot.
+        ids (N, S) int32 on the device.  Returns (N, S, M) fp16."""
+        return _lib.mmq_id(self.gtype, self.A, ids, x, self.E, self.M, self.K)
+
+
+class MoEFFN:
+    """y[n] = sum_s weights[n, s] * down_e(silu(gate_e(x[n])) * up_e(x[n])), e = ids[n, s]."""
+
+    NAMES = ("ffn_gate_exps", "ffn_up_exps", "ffn_down_exps")
+
+    def __init__(self, gate: GGUFExperts, up: GGUFExperts, down: GGUFExperts):
+        if not (gate.E == up.E == down.E and gate.M == up.M == down.K and gate.K == up.K == down.M):
+            raise ValueError("gate / up are E x (ffn, hidden) and down E x (hidden, ffn) of one block")
+        self.gate, self.up, self.down = gate, up, down
+
+    @classmethod
+    def from_gguf(cls, tensors: dict, layer: int, device="cuda"):
+        """From read_gguf() tensors named blk.<layer>.ffn_{gate,up,down}_exps.weight (3-D)."""
+        parts = []
+        for name in cls.NAMES:
+            t = tensors[f"blk.{layer}.{name}.weight"]
+            if len(t.dims) != 3:
+                raise ValueError(f"{t.name}: expected a 3-D expert tensor, dims {t.dims}")
+            E, M, K = t.shape
+            parts.append(GGUFExperts(t.type_name, t.to_device(device), E, M, K))
+        return cls(*parts)
+
+    def forward(self, x: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor) -> torch.Tensor:
+        """x (N, hidden) fp16, ids (N, S) int32 and weights (N, S) on the device -> (N, hidden)."""
+        g, u = self.gate(x, ids), self.up(x, ids)
+        h = torch.nn.functional.silu(g) * u
+        d = self.down(h, ids)
+        return (weights[..., None] * d).sum(1)
+
+    __call__ = forward

@@ -19,6 +19,7 @@
  * Beyond the reference (no counterpart there):
  *   gq_*_ex(..., GQ_ACT_FP8_E4M3, ...)  the fp8 activation variant (BASELINE.json configs[4])
  *   gq_quantize_fp8                     its activation quantizer
+ *   gq_mmq_id                           expert-indexed MMQ for mixture-of-experts blocks (mul_mat_id)
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -226,6 +227,38 @@ int gq_mmq_grouped(const gq_group_item *items, int n, int64_t N, void *stream);
  * variant: its decode form at N <= 2, the K-chunked stream at 3..32) gives every item
  * gq_mmq_ex(..., GQ_ACT_FP8_E4M3, ...)'s bits on that kernel. */
 int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, void *stream);
+
+/*
+ * Expert-indexed MMQ (llama.cpp's mul_mat_id) for mixture-of-experts blocks at decode: N tokens
+ * each multiply S router-chosen experts out of E, the choices read from DEVICE memory by the
+ * kernel -- no host copy of the ids, so the call keeps this header's promise (asynchronous, no
+ * host sync, no allocation, graph-capturable: a replay follows whatever `ids` holds then).
+ *   A        : E packed M x K matrices of `t` back to back, expert e at byte
+ *              e*M*(K/QK)*block_bytes -- a GGUF 3-D tensor blk.L.ffn_*_exps.weight (dims (K, M, E))
+ *              as stored, no repacking.
+ *   ids      : N*S int32 in device memory; pair p = n*S + s multiplies expert ids[p].
+ *   B        : fp16 activations; pair (n, s) reads the K elements at n*ldb + s*ldb_slot (ldb >= K).
+ *              ldb_slot = 0: the S slots share token n's row (gate / up); ldb_slot >= K: one row
+ *              per slot (down).  No alignment beyond fp16's, as gq_mmq's one-launch decode.
+ *   C        : fp16; pair p's M outputs start at element p*ldc (ldc >= M).
+ * Pair p's outputs are bit-identical to gq_mmq(t, A_e, row, C_p, M, 1, K, ...) on that expert
+ * and row under the default tuning.  An id outside [0, E) reads no weights and gives M zeros.
+ * One launch, every pair on an equal share of the chip; q8_1 activations only (no fp8 form).
+ * M == 0, N == 0 or S == 0: a no-op.  GQ_EINVAL: null pointer, ldb < K, ldc < M, an ldb_slot
+ * that is neither 0 nor >= K.  GQ_EUNSUPPORTED (nothing launched): more than 64 pairs (8 tokens x
+ * top-8: every pair streams its expert's weights itself; beyond that, pairs that share an expert
+ * should share one weight stream -- a sorted GEMM this entry is not), a K whose one-token
+ * activations do not fit the decode's LDS image, or one expert of >= 2 GiB (the whole tensor may
+ * be larger).  The caller then groups the pairs by expert on the host and calls gq_mmq per expert
+ * (kernels/_lib.py mmq_id does).
+ * Like gq_mmq on a row slice, the weight stream reads whole 16-byte pieces from each expert's first
+ * byte: an expert that does not start 16-byte aligned may have up to 15 bytes read (never used)
+ * past its end, so the last expert should not end flush with the end of mapped device memory
+ * (device allocators' granularity guarantees it).
+ * gq_version() did not change with it: a caller detects the entry by its symbol (dlsym).
+ */
+int gq_mmq_id(gq_type t, const void *A, const int32_t *ids, const void *B, void *C, int64_t E, int64_t M, int64_t N,
+              int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE
