@@ -31,6 +31,23 @@
 
 namespace gq {
 
+// The DEQ form of a lane's 8 elements: x~ = fp16(d*q); each 4-element group in the order
+// (0,2,1,3): the order mmq_gemm.hip's packed dequantization produces weight pairs in (its
+// k-permutation; the MFMA k-sum is unchanged)
+__device__ __forceinline__ u32x4 deq_words(const Q81Quad &q)
+{
+    uint32_t o[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float v4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] = q.d * (float)(int8_t)((q.codes[h] >> (8 * i)) & 0xff);
+        o[2 * h] = (uint32_t)f2h_bits(v4[0]) | ((uint32_t)f2h_bits(v4[2]) << 16);
+        o[2 * h + 1] = (uint32_t)f2h_bits(v4[1]) | ((uint32_t)f2h_bits(v4[3]) << 16);
+    }
+    return (u32x4){o[0], o[1], o[2], o[3]};
+}
+
 // workgroup wg of a launch over one (rows, K) activation tensor: blocks 64 wg .. 64 wg + 63
 template <int MODE>
 __device__ __forceinline__ void act_quant_body(const uint16_t *__restrict__ X, int64_t ldx, int64_t rows, int64_t K,
@@ -81,20 +98,41 @@ __device__ __forceinline__ void act_quant_body(const uint16_t *__restrict__ X, i
             if (sout) sout[j * ((rows + 3) & ~(int64_t)3) + row] = h2f(q.sbits); // (the integer-MFMA skinny kernel's s)
         }
     } else {
-        // x~ = fp16(d*q); each 4-element group in the order (0,2,1,3): the order mmq_gemm.hip's
-        // packed dequantization produces weight pairs in (its k-permutation; the MFMA k-sum is
-        // unchanged)
-        uint32_t o[4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            float v4[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v4[i] = q.d * (float)(int8_t)((q.codes[h] >> (8 * i)) & 0xff);
-            o[2 * h] = (uint32_t)f2h_bits(v4[0]) | ((uint32_t)f2h_bits(v4[2]) << 16);
-            o[2 * h + 1] = (uint32_t)f2h_bits(v4[1]) | ((uint32_t)f2h_bits(v4[3]) << 16);
-        }
-        *(u32x4 *)(xdeq + row * K + 32 * j + 8 * sub) = (u32x4){o[0], o[1], o[2], o[3]};
+        *(u32x4 *)(xdeq + row * K + 32 * j + 8 * sub) = deq_words(q);
     }
+}
+
+// The DEQ form with the source row taken through a permutation (the sorted expert GEMM,
+// gq_mmq_id_sorted): sorted row r = pair p = perm[r] = (token n, slot s), read at
+// B + n*ldb + s*ldb_slot (any fp16-aligned address: ld16), written as row r of xdeq -- the bytes
+// act_quant_kernel<ACT_DEQ> writes for that row.  Rows r >= nvalid (hdr[1]) are the pairs whose
+// id is out of range: no x~ (no table entry reads it); their M outputs are zeroed instead, the
+// row's K/8 lanes striding over them.
+__global__ __launch_bounds__(256) void act_quant_gather_kernel(const uint16_t *__restrict__ B, int64_t ldb,
+                                                               int64_t ldb_slot, int S, const int32_t *__restrict__ perm,
+                                                               const int32_t *__restrict__ hdr, int64_t rows, int64_t K,
+                                                               uint16_t *__restrict__ xdeq, uint16_t *__restrict__ C,
+                                                               int64_t M, int64_t ldc)
+{
+    const int64_t nb = K / 32;
+    const int64_t blk = (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
+    const int sub = threadIdx.x & 3;
+    const bool live = blk < rows * nb;
+    const int64_t row = live ? blk / nb : 0;
+    const int64_t j = live ? blk - row * nb : 0;
+    const int p = live ? perm[row] : 0;
+    const int n = p / S, s = p - n * S;
+
+    u32x4 v = {0, 0, 0, 0};
+    if (live) v = ld16(B + n * ldb + s * ldb_slot + 32 * j + 8 * sub);
+    const Q81Quad q = q8_1_quad(v); // (every lane: DPP quad groups)
+    if (!live) return;
+    if (row >= hdr[1]) {
+        uint16_t *c = C + (int64_t)p * ldc;
+        for (int64_t m = 4 * j + sub; m < M; m += K / 8) c[m] = 0;
+        return;
+    }
+    *(u32x4 *)(xdeq + row * K + 32 * j + 8 * sub) = deq_words(q);
 }
 
 template <int MODE>
@@ -138,6 +176,18 @@ hipError_t launch_act_quant_deq_grouped(const DeqSeg *segs, int n, hipStream_t s
     if (wg == 0) return hipSuccess;
     if (mode == ACT_F8DEQ) act_quant_deq_grouped_kernel<ACT_F8DEQ><<<dim3((unsigned)wg), dim3(256), 0, s>>>(a);
     else act_quant_deq_grouped_kernel<ACT_DEQ><<<dim3((unsigned)wg), dim3(256), 0, s>>>(a);
+    return hipGetLastError();
+}
+
+hipError_t launch_act_quant_gather(const uint16_t *B, int64_t ldb, int64_t ldb_slot, int64_t S, const int32_t *perm,
+                                   const int32_t *hdr, int64_t P, int64_t K, uint16_t *xdeq, uint16_t *C, int64_t M,
+                                   int64_t ldc, hipStream_t s)
+{
+    const int64_t nblk = P * (K / 32);
+    if (nblk == 0) return hipSuccess;
+    if (S < 1 || S > INT32_MAX || (nblk + 63) / 64 > INT32_MAX) return hipErrorInvalidValue;
+    act_quant_gather_kernel<<<dim3((unsigned)((nblk + 63) / 64)), dim3(256), 0, s>>>(B, ldb, ldb_slot, (int)S, perm, hdr, P,
+                                                                                     K, xdeq, C, M, ldc);
     return hipGetLastError();
 }
 

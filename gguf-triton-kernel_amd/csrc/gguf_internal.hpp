@@ -211,6 +211,35 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
                             int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc,
                             hipStream_t s);
 
+// Sorted expert GEMM (gq_mmq_id_sorted; any pair count): three launches whose grids depend on
+// host-known sizes only.
+//   launch_id_sort (mmq_idsort.hip): one workgroup; perm[P] = the pair indices grouped by expert
+//     (ascending inside a group, out-of-range ids last), hdr = {T, nvalid, 0, 0}, table[T] =
+//     {expert, first sorted row, rows <= 16*nb, 0} per (expert, token tile).
+//   launch_act_quant_gather (act_quant.hip): sorted row r = act_quant's DEQ x~ of pair perm[r]'s
+//     row B + n*ldb + s*ldb_slot (the bytes gq_act_prepare writes for that row); the M outputs of
+//     the out-of-range pairs (rows >= nvalid) zeroed in C.
+//   launch_sgemm_id (mmq_rgemm.hip): tiles_m x t_max workgroups, workgroup (x, t < T) the
+//     streaming GEMM body on table entry t over the whole K, sorted row r stored to
+//     C + perm[row0 + r]*ldc; t >= T returns at once.
+// t_max = min(E, P) + P / (16*nb) bounds sum_e ceil(c_e / (16*nb)) for any ids (every expert with
+// pairs has at most one partial tile, and the full tiles hold 16*nb pairs each).
+constexpr int kMaxSortExperts = 1024, kMaxSortPairs = 65536;
+struct SortedPlan {
+    bool ok = false;
+    int nb = 1, tiles_m = 0, t_max = 0;
+    size_t perm_off = 0, hdr_off = 0, table_off = 0, bytes = 0; // from the 16-byte aligned workspace (x~ at 0)
+};
+SortedPlan plan_sgemm_id(int64_t E, int64_t M, int64_t P, int64_t K);
+hipError_t launch_id_sort(const int32_t *ids, int64_t P, int64_t E, int nb, int32_t *perm, int32_t *hdr, int32_t *table,
+                          hipStream_t s);
+hipError_t launch_act_quant_gather(const uint16_t *B, int64_t ldb, int64_t ldb_slot, int64_t S, const int32_t *perm,
+                                   const int32_t *hdr, int64_t P, int64_t K, uint16_t *xdeq, uint16_t *C, int64_t M,
+                                   int64_t ldc, hipStream_t s);
+hipError_t launch_sgemm_id(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *C, const int32_t *perm,
+                           const int32_t *hdr, const int32_t *table, const SortedPlan &p, int64_t M, int64_t K, int64_t ldc,
+                           hipStream_t s);
+
 // K-chunked streaming MMQ (mmq_kstream.hip, 5..32 tokens): x~ in VGPRs (each of a workgroup's
 // 8 waves one K chunk), weights streamed per wave through private LDS rings, the waves' tiles
 // summed in LDS: one launch, no partials for K <= 4096.  A longer K is cut into ranges of 16

@@ -1123,6 +1123,64 @@ int gq_mmq_id(gq_type t, const void *A, const int32_t *ids, const void *B, void 
     return GQ_OK;
 }
 
+// gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
+static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
+{
+    gq::SortedPlan none;
+    if (K <= 0 || K % 256 != 0 || E < 1 || E > gq::kMaxSortExperts || M < 1 || N < 1 || S < 1) return none;
+    if (N > gq::kMaxSortPairs || S > gq::kMaxSortPairs || N * S > gq::kMaxSortPairs) return none;
+    if (N * S * K * 2 >= ((int64_t)1 << 32)) return none;        // (sgemm_body's 32-bit descriptor over x~)
+    if (M > INT64_MAX / row_bytes_of(t, K) || M * row_bytes_of(t, K) >= ((int64_t)1 << 31)) return none; // one expert
+    return gq::plan_sgemm_id(E, M, N * S, K);
+}
+
+size_t gq_mmq_id_sorted_workspace_size(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
+{
+    if (!known_type(t)) return 0;
+    const gq::SortedPlan p = sorted_plan(t, E, M, N, S, K);
+    return p.ok ? p.bytes + 15 : 0; // (+15: the entry aligns the workspace to 16 bytes itself)
+}
+
+int gq_mmq_id_sorted(gq_type t, const void *A, const int32_t *ids, const void *B, void *C, int64_t E, int64_t M, int64_t N,
+                     int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc, void *workspace,
+                     size_t workspace_bytes, void *stream)
+{
+    g_err.clear();
+    int rc = check_common(t, M, N, K);
+    if (rc != GQ_OK) return rc;
+    if ((rc = check_pair(t, GQ_ACT_Q8_1)) != GQ_OK) return rc;
+    if (S < 0 || E < 0) return fail(GQ_EINVAL, "negative size S=%lld E=%lld", (long long)S, (long long)E);
+    if (M == 0 || N == 0 || S == 0) return GQ_OK;
+    if (K == 0) return fail(GQ_EINVAL, "K must be positive");
+    if (E == 0) return fail(GQ_EINVAL, "E must be positive");
+    if (!A || !ids || !B || !C) return fail(GQ_EINVAL, "null pointer (A=%p ids=%p B=%p C=%p)", A, (const void *)ids, B, C);
+    if (ldc < M) return fail(GQ_EINVAL, "ldc=%lld < M=%lld", (long long)ldc, (long long)M);
+    if (ldb < K) return fail(GQ_EINVAL, "ldb=%lld < K=%lld", (long long)ldb, (long long)K);
+    if (ldb_slot != 0 && ldb_slot < K)
+        return fail(GQ_EINVAL, "ldb_slot=%lld is neither 0 (shared row) nor >= K=%lld", (long long)ldb_slot, (long long)K);
+    const gq::SortedPlan p = sorted_plan(t, E, M, N, S, K);
+    if (!p.ok)
+        return fail(GQ_EUNSUPPORTED,
+                    "not a sorted expert GEMM shape (K=%lld %% 256 == 0, E=%lld <= %d, N*S=%lld <= %d, N*S*K*2 < 4 GiB, "
+                    "one expert < 2 GiB)",
+                    (long long)K, (long long)E, gq::kMaxSortExperts, (long long)(N * S), gq::kMaxSortPairs);
+    const size_t need = p.bytes + 15;
+    if (!workspace || workspace_bytes < need)
+        return fail(GQ_EINVAL, "workspace %zu bytes < required %zu", workspace ? workspace_bytes : (size_t)0, need);
+    uint8_t *ws = (uint8_t *)(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+    uint16_t *xdeq = (uint16_t *)ws;
+    int32_t *perm = (int32_t *)(ws + p.perm_off), *hdr = (int32_t *)(ws + p.hdr_off), *table = (int32_t *)(ws + p.table_off);
+    const hipStream_t s = (hipStream_t)stream;
+    hipError_t e = gq::launch_id_sort(ids, N * S, E, p.nb, perm, hdr, table, s);
+    if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (id sort): %s", hipGetErrorString(e));
+    e = gq::launch_act_quant_gather((const uint16_t *)B, ldb, ldb_slot, S, perm, hdr, N * S, K, xdeq, (uint16_t *)C, M, ldc,
+                                    s);
+    if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (act gather): %s", hipGetErrorString(e));
+    e = gq::launch_sgemm_id(t, (const uint8_t *)A, xdeq, (uint16_t *)C, perm, hdr, table, p, M, K, ldc, s);
+    if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (sorted GEMM): %s", hipGetErrorString(e));
+    return GQ_OK;
+}
+
 // gq_mmq_grouped_prepared: the items as the grouped streaming GEMM takes them, or a GQ_* error
 static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int64_t N, gq::SGroupItem *out)
 {

@@ -470,6 +470,38 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[RRG][NB], uint16_t
     }
 }
 
+// store_tile's one-split form with the output rows taken through a map (the sorted expert GEMM):
+// token r < N of the tile goes to C + rowmap[r]*ldc -- the same conversions, the same 8-byte
+// stores of four weight rows, one map word per lane and 16-token group.
+template <int NB>
+__device__ __forceinline__ void store_tile_rows(const f32x4 (&acc)[RRG][NB], uint16_t *__restrict__ C,
+                                                const int32_t *__restrict__ rowmap, int64_t M, int64_t N, int64_t ldc,
+                                                const TileId &id)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4, l16 = lane & 15;
+    const int64_t m0 = (int64_t)id.x * RBM;
+#pragma unroll
+    for (int t = 0; t < NB; ++t) {
+        const int tok = 16 * t + l16;
+        if (tok >= N) continue;
+        uint16_t *out = C + (int64_t)rowmap[tok] * ldc;
+#pragma unroll
+        for (int rg = 0; rg < RRG; ++rg) {
+            const int64_t row = m0 + 16 * (RRG * wave + rg) + 4 * g;
+            if (row >= M) continue;
+            const f32x4 v = acc[rg][t];
+            uint16_t *dst = out + row;
+            if (row + 4 <= M) {
+                *(u32x2 *)dst = (u32x2){(uint32_t)f2h_bits(v[0]) | ((uint32_t)f2h_bits(v[1]) << 16),
+                                        (uint32_t)f2h_bits(v[2]) | ((uint32_t)f2h_bits(v[3]) << 16)};
+            } else {
+                for (int i = 0; i < 4 && row + i < M; ++i) dst[i] = f2h_bits(v[i]);
+            }
+        }
+    }
+}
+
 // AQ: 0 = prepared x~ (X = fp16 [N][K], DEQ layout); 1 = raw fp16 [N][ldx], q8_1 in-kernel;
 // 2 = raw fp16, the fp8 variant's e4m3 quantization in-kernel (F8DEQ x~).
 // spol: cache policy of the split-K partial stores (0 plain, 2 nt, 16 sc1; kSpol = sc1, measured
@@ -721,11 +753,13 @@ template <typename Q> __device__ __forceinline__ int sk_owner(const Q &q, int u,
     return sk_first_wg(q.cstart + (u - q.ustart) * q.cost, U, W);
 }
 
-template <int F, int NB>
+// ROWS: the tile's token r is stored to output row rowmap[r] (store_tile_rows: the sorted expert
+// GEMM, one split) instead of row n0 + r (store_tile)
+template <int F, int NB, bool ROWS = false>
 __device__ __forceinline__ void sgemm_body(const uint8_t *__restrict__ A, const uint16_t *__restrict__ X,
                                            uint16_t *__restrict__ C, uint16_t *__restrict__ P, int64_t M, int64_t N,
                                            int64_t K, int64_t ldc, int spol, const TileId &id, int64_t sb0, int64_t sb1,
-                                           uint8_t *lds)
+                                           uint8_t *lds, const int32_t *__restrict__ rowmap = nullptr)
 {
     using G = SCfg<F, NB>;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -783,7 +817,8 @@ __device__ __forceinline__ void sgemm_body(const uint8_t *__restrict__ A, const 
             mul_substage<F, NB>(slot, slot + G::W_BYTES + ul * (G::BN * 128), 2 * h + ul, acc, 32 * wave);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (nothing is in flight here; no DMA outlives the workgroup)
-    store_tile<NB>(acc, C, P, M, N, ldc, spol, id);
+    if constexpr (ROWS) store_tile_rows<NB>(acc, C, rowmap, M, N, ldc, id);
+    else store_tile<NB>(acc, C, P, M, N, ldc, spol, id);
 }
 
 // Q4_K with whole-super-block stages (GQ_SGEMM_FULL; 16 / 32-token tiles; the default for single
@@ -804,11 +839,11 @@ template <int NB> struct SFull {
     static_assert(RBM * NPW % 64 == 0 && NS >= 2 && LDS <= LDS_CAP && (NS - 2) * NPS <= 63, "SFull");
 };
 
-template <int NB>
+template <int NB, bool ROWS = false>
 __device__ __forceinline__ void sgemm_full_body(const uint8_t *__restrict__ A, const uint16_t *__restrict__ X,
                                                 uint16_t *__restrict__ C, uint16_t *__restrict__ P, int64_t M, int64_t N,
                                                 int64_t K, int64_t ldc, int spol, const TileId &id, int64_t sb0, int64_t sb1,
-                                                uint8_t *lds)
+                                                uint8_t *lds, const int32_t *__restrict__ rowmap = nullptr)
 {
     using G = SFull<NB>;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -881,7 +916,8 @@ __device__ __forceinline__ void sgemm_full_body(const uint8_t *__restrict__ A, c
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    store_tile<NB>(acc, C, P, M, N, ldc, spol, id);
+    if constexpr (ROWS) store_tile_rows<NB>(acc, C, rowmap, M, N, ldc, id);
+    else store_tile<NB>(acc, C, P, M, N, ldc, spol, id);
 }
 
 template <int F, int NB> constexpr int sgemm_lds()
@@ -926,6 +962,52 @@ __global__ __launch_bounds__(64 * RW) void sgemm_kernel(const uint8_t *__restric
     }
     if (!done) sgemm_body<F, NB>(A, X, C, P, M, N, K, ldc, sp, id, s0, s1, lds);
     if (ilc && id.gz > 1) ilc_combine<NB>(C, P, M, N, ldc, id, nonce);
+}
+
+// The sorted expert GEMM (gq_mmq_id_sorted): a 1-D grid of tiles_m x t_max workgroups over the
+// tile table the sort launch left (mmq_idsort.hip): workgroup b = (table entry t = b / tiles_m,
+// row tile x = b % tiles_m).  Row tiles of one entry are adjacent, so (i) the workgroups past the
+// table's end (t >= T: they return before any barrier or DMA) are the grid's tail, dispatched
+// after every real one, and (ii) the token tiles of one expert -- neighbouring entries, which
+// stream the same weight rows -- are tiles_m launch indices apart: with 8 | tiles_m (14336- and
+// 4096-row experts) on the same XCD, whose L2 can then serve the second stream (the reverse
+// order was not measured).  A real workgroup
+// runs the streaming body unchanged on expert e's matrix and the entry's rows of the sorted x~,
+// the whole K as one split; only the epilogue differs (store_tile_rows through perm).
+template <int F, int NB>
+__global__ __launch_bounds__(64 * RW) void sgemm_id_kernel(const uint8_t *__restrict__ A, int64_t expert_bytes,
+                                                          const uint16_t *__restrict__ X, uint16_t *__restrict__ C,
+                                                          const int32_t *__restrict__ perm,
+                                                          const int32_t *__restrict__ hdr,
+                                                          const int32_t *__restrict__ table, int64_t M, int64_t K,
+                                                          int64_t ldc, int full, int tiles_m)
+{
+    __shared__ __attribute__((aligned(1024))) uint8_t lds[sgemm_lds<F, NB>()];
+    const int b = (int)blockIdx.x, t = b / tiles_m, x = b - t * tiles_m;
+    if (t >= hdr[0]) return; // (uniform)
+    const int e = __builtin_amdgcn_readfirstlane(table[4 * t]);
+    const int row0 = __builtin_amdgcn_readfirstlane(table[4 * t + 1]);
+    const int n = __builtin_amdgcn_readfirstlane(table[4 * t + 2]);
+    const uint8_t *Ae = A + (int64_t)e * expert_bytes;
+    const uint16_t *Xe = X + (int64_t)row0 * K;
+    const TileId id{x, 0, 0, tiles_m, 1, 1};
+    if constexpr (F == Q4_K && NB <= 2) {
+        if (full) {
+            sgemm_full_body<NB, true>(Ae, Xe, C, nullptr, M, n, K, ldc, 0, id, 0, K / 256, lds, perm + row0);
+            return;
+        }
+    }
+    sgemm_body<F, NB, true>(Ae, Xe, C, nullptr, M, n, K, ldc, 0, id, 0, K / 256, lds, perm + row0);
+}
+
+template <int F, int NB>
+hipError_t launch_sid(const uint8_t *A, const uint16_t *X, uint16_t *C, const int32_t *perm, const int32_t *hdr,
+                      const int32_t *table, const SortedPlan &p, int64_t M, int64_t K, int64_t ldc, hipStream_t s)
+{
+    const int64_t expert_bytes = M * (K / Layout<F>::QK) * Layout<F>::BYTES;
+    sgemm_id_kernel<F, NB><<<dim3((unsigned)((int64_t)p.tiles_m * p.t_max)), dim3(64 * RW), 0, s>>>(
+        A, expert_bytes, X, C, perm, hdr, table, M, K, ldc, tuning().sgemm_full != 0, p.tiles_m);
+    return hipGetLastError();
 }
 
 // ---- several matrices in one launch (gq_mmq_grouped_prepared): part i = one matrix's
@@ -1282,6 +1364,48 @@ hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *
     default: return hipErrorInvalidValue;
     }
 #undef GQ_SG_NB
+}
+
+// NB from host-known sizes only: plan_sgemm's thresholds at the mean pairs per expert that can
+// have any, ceil(P / min(E, P)).  x~ first (16-byte aligned), then perm, hdr and the table.
+SortedPlan plan_sgemm_id(int64_t E, int64_t M, int64_t P, int64_t K)
+{
+    SortedPlan p;
+    if (E < 1 || E > kMaxSortExperts || M < 1 || P < 1 || P > kMaxSortPairs || K < 256 || K % 256 != 0) return p;
+    const int64_t ne = E < P ? E : P, avg = (P + ne - 1) / ne;
+    p.nb = avg > 64 ? 8 : (avg > 32 ? 4 : (avg > 16 ? 2 : 1));
+    p.tiles_m = (int)((M + RBM - 1) / RBM);
+    p.t_max = (int)(ne + P / (16 * p.nb));
+    if ((int64_t)p.tiles_m * p.t_max > INT32_MAX) return p;
+    p.perm_off = (size_t)P * (size_t)K * 2;
+    p.hdr_off = p.perm_off + (((size_t)P * 4 + 15) & ~(size_t)15);
+    p.table_off = p.hdr_off + 16;
+    p.bytes = p.table_off + (size_t)p.t_max * 16;
+    p.ok = true;
+    return p;
+}
+
+hipError_t launch_sgemm_id(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *C, const int32_t *perm,
+                           const int32_t *hdr, const int32_t *table, const SortedPlan &p, int64_t M, int64_t K, int64_t ldc,
+                           hipStream_t s)
+{
+    if (!p.ok) return hipErrorInvalidValue;
+#define GQ_SID_NB(F)                                                                                                   \
+    switch (p.nb) {                                                                                                    \
+    case 1: return launch_sid<F, 1>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
+    case 2: return launch_sid<F, 2>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
+    case 4: return launch_sid<F, 4>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
+    case 8: return launch_sid<F, 8>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
+    default: return hipErrorInvalidValue;                                                                              \
+    }
+    switch (fmt) {
+    case Q8_0: GQ_SID_NB(Q8_0)
+    case Q4_K: GQ_SID_NB(Q4_K)
+    case Q6_K: GQ_SID_NB(Q6_K)
+    case Q5_K: GQ_SID_NB(Q5_K)
+    default: return hipErrorInvalidValue;
+    }
+#undef GQ_SID_NB
 }
 
 SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int splits)

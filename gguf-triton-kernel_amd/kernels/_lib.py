@@ -67,6 +67,8 @@ SIGNATURES = {
     "gq_mmq_grouped": ([ctypes.POINTER(GroupItem), _I, _I64, _P], _I),
     "gq_mmq_grouped_ex": ([_I, ctypes.POINTER(GroupItem), _I, _I64, _P], _I),
     "gq_mmq_id": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_mmq_id_sorted_workspace_size": ([_I, _I64, _I64, _I64, _I64, _I64], _SZ),
+    "gq_mmq_id_sorted": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_mmq_grouped_prepared_workspace_size": ([_I, ctypes.POINTER(GemmItem), _I, _I64], _SZ),
@@ -327,18 +329,10 @@ def pairs_by_expert(ids_np, E: int) -> dict:
     return groups
 
 
-def mmq_id(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: int, M: int, K: int,
-           out: torch.Tensor | None = None) -> torch.Tensor:
-    """Expert-indexed MMQ (gq_mmq_id; llama.cpp's mul_mat_id): A = E packed (M, K) matrices back to
-    back (a GGUF 3-D expert tensor as stored), ids an (N, S) int32 DEVICE tensor of expert choices,
-    B fp16 (N, K) -- the S slots of a token share its row (gate / up) -- or (N, S, K) -- one row
-    per slot (down).  Returns (N, S, M) fp16: row (n, s) is bit-identical to
-    mmq(gtype, A[expert ids[n, s]], that row, M, 1, K); an id outside [0, E) gives a zero row.
-    One launch that reads the ids on the device: no host sync, graph-capturable.
-    When the library refuses the shape (GQ_EUNSUPPORTED: more than 64 pairs, a K whose decode
-    does not fit, an expert of 2 GiB or more) the call falls back to a host-sorted path: the ids
-    are copied to the host (this SYNCHRONISES and cannot be captured in a graph), and every
-    expert some pair chose runs one mmq() over its pairs' gathered rows."""
+def _id_args(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: int, M: int, K: int,
+             out: torch.Tensor | None):
+    """The checks and strides mmq_id and mmq_id_sorted share: (B, N, S, per_slot, ldb, ldb_slot, C,
+    ldc, ebytes), ldc None when there is nothing to compute."""
     _require_device(A, "A")
     _require_device(ids, "ids")
     _require_device(B, "B")
@@ -372,14 +366,67 @@ def mmq_id(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: i
     if C.dtype != torch.float16 or tuple(C.shape) != (N, S, M) or C.device != dev:
         raise RuntimeError(f"out must be an fp16 ({N}, {S}, {M}) tensor on A's device")
     if N * S * M == 0:
-        return C
+        return B, N, S, per_slot, ldb, ldb_slot, C, None, ebytes
     # pair p = n*S + s writes at element p*ldc: rows evenly spaced, ldc >= M apart
     ldc = C.stride(1) if S > 1 else (C.stride(0) if N > 1 else M)
     if (M > 1 and C.stride(2) != 1) or ldc < M or (S > 1 and N > 1 and C.stride(0) != S * ldc):
         raise RuntimeError("out rows must have unit element stride and be evenly spaced, at least M apart")
+    return B, N, S, per_slot, ldb, ldb_slot, C, ldc, ebytes
+
+
+def _id_sorted_call(gtype, A, ids, B, C, E, M, N, S, K, ldb, ldb_slot, ldc) -> int:
+    """gq_mmq_id_sorted with its workspace from torch's allocator (inside a graph capture: the
+    graph's pool); the status, GQ_EUNSUPPORTED when the entry refuses the shape."""
+    need = int(lib().gq_mmq_id_sorted_workspace_size(gtype, E, M, N, S, K))
+    if need == 0:
+        return GQ_EUNSUPPORTED
+    dev = A.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        return lib().gq_mmq_id_sorted(gtype, A.data_ptr(), ids.data_ptr(), B.data_ptr(), C.data_ptr(), E, M, N, S, K,
+                                      ldb, ldb_slot, ldc, ws.data_ptr(), need, _stream(dev))
+
+
+def mmq_id_sorted(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: int, M: int, K: int,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """The sorted expert GEMM (gq_mmq_id_sorted): mmq_id's arguments and result at any pair count
+    the entry admits (K % 256 == 0, E <= 1024, N*S <= 65536).  Three launches -- a device-side sort
+    of the pairs by expert, the activation quantizer gathering through the permutation, the
+    streaming GEMM over the (expert, token tile) table -- with no host sync: graph-capturable, a
+    replay follows the ids.  Row (n, s) is bit-identical to its row of the streaming GEMM on that
+    expert and the expert's gathered rows at one K split, whatever the other ids are; an id
+    outside [0, E) gives a zero row.  Raises when the entry refuses the shape (no fallback here)."""
+    B, N, S, per_slot, ldb, ldb_slot, C, ldc, ebytes = _id_args(gtype, A, ids, B, E, M, K, out)
+    if ldc is None:
+        return C
+    _check(_id_sorted_call(gtype, A, ids, B, C, E, M, N, S, K, ldb, ldb_slot, ldc))
+    return C
+
+
+def mmq_id(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: int, M: int, K: int,
+           out: torch.Tensor | None = None) -> torch.Tensor:
+    """Expert-indexed MMQ (llama.cpp's mul_mat_id): A = E packed (M, K) matrices back to back (a
+    GGUF 3-D expert tensor as stored), ids an (N, S) int32 DEVICE tensor of expert choices,
+    B fp16 (N, K) -- the S slots of a token share its row (gate / up) -- or (N, S, K) -- one row
+    per slot (down).  Returns (N, S, M) fp16; an id outside [0, E) gives a zero row.
+    Up to 64 pairs (gq_mmq_id): one launch, row (n, s) bit-identical to
+    mmq(gtype, A[expert ids[n, s]], that row, M, 1, K).  Beyond that, or where gq_mmq_id refuses
+    the shape otherwise (GQ_EUNSUPPORTED), the sorted expert GEMM (gq_mmq_id_sorted, see
+    mmq_id_sorted): pairs that share an expert share one weight stream, at the GEMM paths'
+    tolerance.  Both read the ids on the device: no host sync, graph-capturable.
+    Only when both refuse (K % 256 != 0 beyond 64 pairs, e.g. Q8_0 at K = 1056; more than 1024
+    experts or 65536 pairs) the call falls back to a host-sorted path: the ids are copied to the
+    host (this SYNCHRONISES and cannot be captured in a graph), and every expert some pair chose
+    runs one mmq() over its pairs' gathered rows."""
+    B, N, S, per_slot, ldb, ldb_slot, C, ldc, ebytes = _id_args(gtype, A, ids, B, E, M, K, out)
+    if ldc is None:
+        return C
+    dev = A.device
     with torch.cuda.device(dev):
         rc = lib().gq_mmq_id(gtype, A.data_ptr(), ids.data_ptr(), B.data_ptr(), C.data_ptr(), E, M, N, S, K, ldb,
                              ldb_slot, ldc, _stream(dev))
+    if rc == GQ_EUNSUPPORTED:
+        rc = _id_sorted_call(gtype, A, ids, B, C, E, M, N, S, K, ldb, ldb_slot, ldc)
     if rc != GQ_EUNSUPPORTED:
         _check(rc)
         return C

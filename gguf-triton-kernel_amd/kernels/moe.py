@@ -1,12 +1,15 @@
-"""Mixture-of-experts FFN block (Mixtral, Qwen-MoE, DeepSeek GGUF checkpoints) at decode.
+"""Mixture-of-experts FFN block (Mixtral, Qwen-MoE, DeepSeek GGUF checkpoints), decode and prefill.
 
 A MoE model stores each FFN projection as ONE 3-D tensor of E expert matrices,
 blk.<L>.ffn_{gate,up,down}_exps.weight with GGUF dims (K, M, E): E packed M x K matrices back
 to back.  The router picks S experts per token and leaves the choices in device memory; the
-expert-indexed MMQ (gq_mmq_id, kernels._lib.mmq_id) reads them there, so a block is three
-launches and a little torch glue, with no host sync (graph-capturable up to 64 (token, slot)
-pairs; beyond that mmq_id falls back to a host-sorted path that synchronises).  No reference
-counterpart: the reference multiplies one dense matrix per call.
+expert-indexed MMQ (kernels._lib.mmq_id) reads them there: up to 64 (token, slot) pairs one
+launch per projection (gq_mmq_id), beyond that the device-sorted expert GEMM (gq_mmq_id_sorted:
+sort, gather-quantize, GEMM -- three launches per projection).  Either way a block is a fixed
+sequence of launches and a little torch glue with no host sync: graph-capturable at any pair
+count the sorted entry admits (K % 256 == 0, E <= 1024, up to 65536 pairs); only a shape both
+entries refuse takes mmq_id's host-sorted path, which synchronises.  No reference counterpart:
+the reference multiplies one dense matrix per call.
 """
 from __future__ import annotations
 
@@ -17,7 +20,8 @@ from . import _lib
 
 class GGUFExperts:
     """E packed GGUF weights (M rows of K elements each) on the device, multiplied by index:
-    y[n, s] = x_row(n, s) @ W[ids[n, s]]^T."""
+    y[n, s] = x_row(n, s) @ W[ids[n, s]]^T, at any number of (token, slot) pairs (mmq_id: the
+    one-launch decode up to 64 pairs, the sorted expert GEMM beyond), the ids read on the device."""
 
     def __init__(self, type_name: str, A: torch.Tensor, E: int, M: int, K: int):
         self.type_name, self.gtype = type_name, _lib.TYPES[type_name]
@@ -30,7 +34,9 @@ class GGUFExperts:
 
 
 class MoEFFN:
-    """y[n] = sum_s weights[n, s] * down_e(silu(gate_e(x[n])) * up_e(x[n])), e = ids[n, s]."""
+    """y[n] = sum_s weights[n, s] * down_e(silu(gate_e(x[n])) * up_e(x[n])), e = ids[n, s].
+    No host sync at decode or prefill: forward can be captured in a graph, and a replay follows
+    whatever ids and weights hold then."""
 
     NAMES = ("ffn_gate_exps", "ffn_up_exps", "ffn_down_exps")
 

@@ -20,6 +20,7 @@
  *   gq_*_ex(..., GQ_ACT_FP8_E4M3, ...)  the fp8 activation variant (BASELINE.json configs[4])
  *   gq_quantize_fp8                     its activation quantizer
  *   gq_mmq_id                           expert-indexed MMQ for mixture-of-experts blocks (mul_mat_id)
+ *   gq_mmq_id_sorted                    the same at any pair count: device-sorted expert GEMM (prefill)
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -249,8 +250,8 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
  * top-8: every pair streams its expert's weights itself; beyond that, pairs that share an expert
  * should share one weight stream -- a sorted GEMM this entry is not), a K whose one-token
  * activations do not fit the decode's LDS image, or one expert of >= 2 GiB (the whole tensor may
- * be larger).  The caller then groups the pairs by expert on the host and calls gq_mmq per expert
- * (kernels/_lib.py mmq_id does).
+ * be larger).  The caller then calls gq_mmq_id_sorted (below; kernels/_lib.py mmq_id does), or,
+ * where that refuses too, groups the pairs by expert on the host and calls gq_mmq per expert.
  * Like gq_mmq on a row slice, the weight stream reads whole 16-byte pieces from each expert's first
  * byte: an expert that does not start 16-byte aligned may have up to 15 bytes read (never used)
  * past its end, so the last expert should not end flush with the end of mapped device memory
@@ -259,6 +260,39 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
  */
 int gq_mmq_id(gq_type t, const void *A, const int32_t *ids, const void *B, void *C, int64_t E, int64_t M, int64_t N,
               int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc, void *stream);
+
+/*
+ * Sorted expert GEMM: gq_mmq_id's job at ANY pair count (prefill, batched decode) -- the same
+ * arguments, the same promise (asynchronous, no host sync, no allocation, graph-capturable: a
+ * replay follows whatever `ids` holds then), plus a workspace.  Three launches whose grids depend
+ * on the sizes only, never on the ids:
+ *   1. one workgroup sorts the N*S pairs by expert on the device (a stable counting sort: a
+ *      permutation of the pair indices, ascending inside an expert's group, ids outside [0, E)
+ *      last) and writes a table of (expert, first sorted row, rows) token tiles;
+ *   2. the activation quantizer gathers through the permutation: sorted row r is the fp16 x~ of
+ *      pair perm[r]'s row at n*ldb + s*ldb_slot -- the bytes gq_act_prepare writes for that row
+ *      (no alignment beyond fp16's) -- and zeroes the M outputs of every out-of-range pair;
+ *   3. the streaming GEMM (gq_mmq_prepared's 256-row MFMA kernel body, the whole K in one split)
+ *      runs once per table entry and row tile -- pairs that share an expert share its weight
+ *      stream -- and scatters sorted row r to C + perm[r]*ldc.  Its grid is sized for the worst
+ *      case, ceil(M/256) x (min(E, N*S) + N*S / tile) workgroups; those past the table's end exit.
+ * Pair p's outputs are bit-identical to its row of gq_mmq_prepared on that expert and the
+ * gathered rows with the streaming GEMM pinned to one split (GQ_SGEMM=1, GQ_SGEMM_SPLITS=1), and
+ * do not depend on the other pairs' ids.  q8_1 activations, all four weight types.
+ * M == 0, N == 0 or S == 0: a no-op.  An id outside [0, E) reads no weights and gives M zeros.
+ * GQ_EINVAL: gq_mmq_id's list, and a NULL workspace or one smaller than
+ * gq_mmq_id_sorted_workspace_size(t, E, M, N, S, K) (>= N*S*K*2 bytes: the gathered x~, then the
+ * permutation and the table; 0 for a shape the entry refuses or an empty one).
+ * GQ_EUNSUPPORTED (nothing launched): K % 256 != 0 (the streaming GEMM works in super-blocks:
+ * Q8_0 too), E > 1024, N*S > 65536, N*S*K*2 >= 4 GiB, or one expert of >= 2 GiB.
+ * As gq_mmq_id, the weight stream reads whole 16-byte pieces from each expert's first byte (up to
+ * 15 bytes, never used, past an expert that does not end 16-byte aligned).
+ * gq_version() did not change with it: a caller detects the entry by its symbol (dlsym).
+ */
+size_t gq_mmq_id_sorted_workspace_size(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K);
+int gq_mmq_id_sorted(gq_type t, const void *A, const int32_t *ids, const void *B, void *C, int64_t E, int64_t M, int64_t N,
+                     int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc, void *workspace,
+                     size_t workspace_bytes, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE
