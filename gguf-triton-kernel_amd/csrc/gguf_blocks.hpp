@@ -9,6 +9,9 @@
 //   Q5_K 256 elems /176 B : [0:2] d | [2:4] dmin | [4:16] 6-bit sc/m x8 (Q4_K's) | [16:48] qh |
 //                           [48:176] qs nibbles;  q = nibble + 16*((qh[e%32] >> e/32) & 1)
 //                           w = d*sc_j*q - dmin*m_j   (sub-block j = e/32)
+//   Q3_K 256 elems /110 B : [0:32] hmask | [32:96] qs (2-bit) | [96:108] 6-bit sc x16 | [108:110] d
+//                           q = ((qs[32*(e/128) + e%32] >> 2*((e%128)/32)) & 3)
+//                               + 4*((hmask[e%32] >> e/32) & 1) - 4;  w = d*(sc_{e/16} - 32)*q
 //   Q8_1 (activations) 36 B: [0:2] d | [2:4] s = d*sum(q) | [4:36] qs int8[32]
 // Reference: block docs in kernels/mmq_q4_k.py:1-16, kernels/mmq_q6_k.py:1-14,
 // utils/quantize/q8_1.py:1-11; unpack rules kernels/mmq_q4_k.py:30-114, mmq_q6_k.py:28-68.
@@ -23,7 +26,7 @@
 
 namespace gq {
 
-enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3 };
+enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3, Q3_K = 4 };
 
 template <int F> struct Layout;
 template <> struct Layout<Q8_0> { static constexpr int QK = 32, BYTES = 34; };
@@ -32,6 +35,11 @@ template <> struct Layout<Q6_K> { static constexpr int QK = 256, BYTES = 210; };
 template <> struct Layout<Q5_K> { static constexpr int QK = 256, BYTES = 176; };
 // Q4_K's header and q8_1 arithmetic (6-bit scales and mins, the activation block's s in the min term)
 constexpr bool has_mins(int f) { return f == Q4_K || f == Q5_K; }
+template <> struct Layout<Q3_K> { static constexpr int QK = 256, BYTES = 110; };
+// Q6_K's q8_1 arithmetic (a signed scale per 16 elements, no mins; the codes enter v_dot4 unsigned
+// and the offset -- Q6_K 32, Q3_K 4 -- is taken out with the activations' per-16 code sums)
+constexpr bool has_sums(int f) { return f == Q6_K || f == Q3_K; }
+constexpr int code_offset(int f) { return f == Q3_K ? 4 : 32; }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

@@ -5,6 +5,7 @@
 //   Q4_K : d*sc*dB*sum(q*qB) - dmin*m*sB                     mmq_q4_k_q8_1_cpu.py:94-117
 //   Q6_K : dB*(d*sc1*sum((q-32)*qB)_lo + d*sc2*sum(...)_hi)  mmq_q6_k_q8_1_cpu.py:117-150
 //   Q5_K : Q4_K's expression, q = 0..31
+//   Q3_K : Q6_K's expression with (q-4), the unit's two blocks being 2u and 2u+1
 // with exact int32 dot products (v_dot4_i32_i8) and fp32 accumulation.
 #pragma once
 #include "gguf_blocks.hpp"
@@ -17,7 +18,7 @@ struct Act {
     uint32_t q[NT][16]; // int8 codes of the two activation blocks
     float d[NT][2];
     float s[NT][2];  // q8_1 s (Q4_K / Q5_K min term)
-    int sum[NT][4];  // sum of codes per 16-element quarter (Q6_K -32 offset)
+    int sum[NT][4];  // sum of codes per 16-element quarter (Q6_K -32 / Q3_K -4 offset)
 };
 
 template <int F, int NT>
@@ -48,7 +49,7 @@ __device__ __forceinline__ void load_act(Act<F, NT> &a, const int8_t *__restrict
             a.s[t][0] = xs[tok * nb + b0];
             a.s[t][1] = has1 ? xs[tok * nb + b1] : 0.f;
         }
-        if constexpr (F == Q6_K) {
+        if constexpr (has_sums(F)) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 int acc = 0;
@@ -100,7 +101,8 @@ __device__ __forceinline__ void dot_unit(const UnitRaw<F> &r, const Act<F, NT> &
                       r.dm1 * a.s[t][1];
         }
     } else {
-        static_assert(F == Q6_K, "dot_unit: unlisted format");
+        static_assert(F == Q6_K || F == Q3_K, "dot_unit: unlisted format");
+        constexpr int OFF = code_offset(F);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             int a1 = 0, a2 = 0, b1 = 0, b2 = 0;
@@ -111,10 +113,10 @@ __device__ __forceinline__ void dot_unit(const UnitRaw<F> &r, const Act<F, NT> &
                 b1 = dot4(r.cb[i], a.q[t][8 + i], b1);
                 b2 = dot4(r.cb[4 + i], a.q[t][12 + i], b2);
             }
-            a1 -= 32 * a.sum[t][0];
-            a2 -= 32 * a.sum[t][1];
-            b1 -= 32 * a.sum[t][2];
-            b2 -= 32 * a.sum[t][3];
+            a1 -= OFF * a.sum[t][0];
+            a2 -= OFF * a.sum[t][1];
+            b1 -= OFF * a.sum[t][2];
+            b2 -= OFF * a.sum[t][3];
             acc[t] += a.d[t][0] * (r.fa1 * (float)a1 + r.fa2 * (float)a2) +
                       a.d[t][1] * (r.fb1 * (float)b1 + r.fb2 * (float)b2);
         }
@@ -149,7 +151,7 @@ __device__ __forceinline__ uint32_t n02(uint32_t v) { return (v & 0x000f000fu) |
 template <int F, int NT, bool NS = false>
 __device__ __forceinline__ void dot_unit_h(const UnitRaw<F> &r, const ActH<NT> &a, float (&acc)[NT])
 {
-    static_assert(F == Q8_0 || F == Q4_K || F == Q6_K, "the fp8 variant has no Q5_K form");
+    static_assert(F == Q8_0 || F == Q4_K || F == Q6_K, "the fp8 variant has no Q5_K / Q3_K form");
     typedef _Float16 hb2 __attribute__((ext_vector_type(2)));
     auto unbias = [](uint32_t v, float b) {
         const hb2 bb = {(_Float16)b, (_Float16)b};
@@ -325,7 +327,7 @@ __device__ __forceinline__ void load_act_lds(Act<F, NT> &a, const uint8_t *codes
             a.s[t][0] = ss[t * nb + b0];
             a.s[t][1] = has1 ? ss[t * nb + b1] : 0.f;
         }
-        if constexpr (F == Q6_K) {
+        if constexpr (has_sums(F)) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 int acc = 0;

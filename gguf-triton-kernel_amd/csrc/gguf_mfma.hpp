@@ -156,6 +156,34 @@ __device__ __forceinline__ void q6k_half_frags(const uint8_t *img, int g, int h,
     }
 }
 
+// Q3_K sub-stage u (elements 64u..64u+63) from a half-super-block image (mmq_rgemm.hip, half
+// h = u >> 1): the 32 hmask bytes at 0, qs bytes 32+32h.. at 32, super-block bytes 94..109 at 64
+// (the 12 scale bytes at 66, d at 78).  k-step n = elements 64u+32n+[0,32): 2-bit codes at shift
+// 4(u&1)+2n of the qs bytes, the third bit at bit 2u+n of hmask; sub-block 4u+2n+(g>>1).
+// Q6_K's roundings: fp16 d*sc, times the code (1024 + c - 1028 exact in fp16).
+__device__ __forceinline__ void q3k_frags(const uint8_t *img, int g, int u, f16x8 (&frag)[2])
+{
+    const u32x4 t = *(const u32x4 *)(img + 64);
+    const float d = h2f(t.w >> 16);
+    const uint32_t s01 = __builtin_amdgcn_alignbyte(u & 1 ? t.z : t.y, u & 1 ? t.y : t.x, 2);
+    const uint32_t s2 = __builtin_amdgcn_alignbyte(t.w, t.z, 2);
+    // 6-bit scales of sub-blocks 4u..4u+3, one per byte
+    const uint32_t sc = ((s01 >> (4 * (u >> 1))) & 0x0f0f0f0fu) | (((s2 >> (2 * u)) & 0x03030303u) << 4);
+    const u32x2 hm = *(const u32x2 *)(img + 8 * g);
+    const u32x2 qs = *(const u32x2 *)(img + 32 + 8 * g);
+    const h2 bias = splat(-1028.f); // 1024 + 4
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const float scv = (float)((int)((sc >> (8 * (2 * n + (g >> 1)))) & 0xffu) - 32);
+        const h2 dsc = splat(d * scv);
+        const int sl = 4 * (u & 1) + 2 * n, sh = 2 * u + n;
+        const uint32_t c0 = ((qs.x >> sl) & 0x03030303u) | (((hm.x >> sh) & 0x01010101u) << 2);
+        const uint32_t c1 = ((qs.y >> sl) & 0x03030303u) | (((hm.y >> sh) & 0x01010101u) << 2);
+        frag[n] = frag4((pair02(c0) + bias) * dsc, (pair13(c0) + bias) * dsc, (pair02(c1) + bias) * dsc,
+                        (pair13(c1) + bias) * dsc);
+    }
+}
+
 // Q6_K sub-stage s4 = (h, v): k-step 0 = elements 128h+32v+[0,32) (ql[64h+32v..] low nibbles,
 // qh bits 2v), k-step 1 = 128h+64+32v+[0,32) (same ql bytes, high nibbles; qh bits 4+2v).
 template <>

@@ -6,6 +6,8 @@
 //   Q5_K : as Q4_K (qs bytes 32(u%4)..+31 of the 176-byte super-block) + its 32 qh bytes
 //   Q6_K : super-block u/4, half h=(u>>1)&1, v=u&1: elements 128h+32v+[0,32) ("A") and
 //          128h+64+32v+[0,32) ("B") -- ql bytes 64h+32v..+31 (both nibbles), qh 32h..+31
+//   Q3_K : super-block u/4, elements 64(u%4)+[0,64): all 32 hmask bytes (bits 2(u%4), 2(u%4)+1),
+//          qs bytes 32((u%4)/2)..+31 at shifts 4(u%2) and 4(u%2)+2, the 12 scale bytes and d
 // so two consecutive units (2c, 2c+1) tile K-chunk c of 128 elements.  Every unit needs
 // 16-byte loads only (Q8_0/Q6_K fields are 2-byte aligned: unaligned dwordx4, which
 // gfx950 serves in unaligned mode).  act_blocks() gives the two 32-element activation
@@ -184,6 +186,79 @@ template <> struct UnitRaw<Q5_K> {
             r.c0[i] = (qs[i] & 0x0f0f0f0fu) | (((qh[i] >> sh) & 0x01010101u) << 4);
             r.c1[i] = ((qs[i] >> 4) & 0x0f0f0f0fu) | (((qh[i] >> (sh + 1)) & 0x01010101u) << 4);
         }
+        return r;
+    }
+};
+
+// ---- Q3_K: one quarter of a super-block (elements 64q..64q+63: activation blocks 2u, 2u+1) ----
+// tail = bytes 94..109 of the super-block (the last 16: no load reaches past the block): the 12
+// scale bytes at 2..13, d at 14
+template <> struct UnitLoad<Q3_K> {
+    u32x4 ha, hb, qa, qb;
+    uint32_t s0, s1, s2, dbits; // scale bytes 0..3, 4..7, 8..11; d
+    __device__ __forceinline__ void load(const uint8_t *__restrict__ rowp, int u, int64_t /*nb32*/)
+    {
+        const int sb = u >> 2, h = (u >> 1) & 1;
+        const uint8_t *p = rowp + 110 * (int64_t)sb;
+        ha = ld16(p);
+        hb = ld16(p + 16);
+        qa = ld16(p + 32 + 32 * h);
+        qb = ld16(p + 48 + 32 * h);
+        const u32x4 t = ld16(p + 94);
+        s0 = __builtin_amdgcn_alignbyte(t.y, t.x, 2);
+        s1 = __builtin_amdgcn_alignbyte(t.z, t.y, 2);
+        s2 = __builtin_amdgcn_alignbyte(t.w, t.z, 2);
+        dbits = t.w >> 16;
+    }
+    // from LDS (the decode ring), dword-aligned: super-blocks are 2-byte aligned there, every field
+    // at a multiple of 4 from the block's first byte -- aligned reads and one shift per block
+    // (lds_words).  Measured slower than load() on the ring (mmq_decode.hip GQ_Q3_LDS_PLAIN), as
+    // Q6_K's load_lds was: kept for A/B builds, not the default
+    __device__ __forceinline__ void load_lds(const uint8_t *__restrict__ rowp, int u, int64_t /*nb32*/)
+    {
+        const int sb = u >> 2, h = (u >> 1) & 1;
+        const uint8_t *p = rowp + 110 * sb;
+        uint32_t m[8], q[8], s[3];
+        lds_words<8>(p, m);
+        lds_words<8>(p + 32 + 32 * h, q);
+        lds_words<3>(p + 96, s);
+        ha = (u32x4){m[0], m[1], m[2], m[3]};
+        hb = (u32x4){m[4], m[5], m[6], m[7]};
+        qa = (u32x4){q[0], q[1], q[2], q[3]};
+        qb = (u32x4){q[4], q[5], q[6], q[7]};
+        s0 = s[0];
+        s1 = s[1];
+        s2 = s[2];
+        dbits = *(const uint16_t *)(p + 108);
+    }
+};
+
+// Q6_K's fields: the products are Q6_K's with the code offset 4 (gguf_dot.hpp dot_unit)
+template <> struct UnitRaw<Q3_K> {
+    float fa1, fa2, fb1, fb2; // d*sc of the four 16-element sub-blocks 4q..4q+3
+    uint32_t ca[8], cb[8];     // 3-bit codes (0..7) of elements 64q+[0,32) and 64q+32+[0,32), one per byte
+
+    __device__ __forceinline__ static UnitRaw from(const UnitLoad<Q3_K> &l, int u, int64_t /*nb32*/)
+    {
+        UnitRaw r;
+        const int q = u & 3;
+        const float d = h2f(l.dbits);
+        const uint32_t hm[8] = {l.ha.x, l.ha.y, l.ha.z, l.ha.w, l.hb.x, l.hb.y, l.hb.z, l.hb.w};
+        const uint32_t qs[8] = {l.qa.x, l.qa.y, l.qa.z, l.qa.w, l.qb.x, l.qb.y, l.qb.z, l.qb.w};
+        const int sl = 4 * (q & 1), sh = 2 * q;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            r.ca[i] = ((qs[i] >> sl) & 0x03030303u) | (((hm[i] >> sh) & 0x01010101u) << 2);
+            r.cb[i] = ((qs[i] >> (sl + 2)) & 0x03030303u) | (((hm[i] >> (sh + 1)) & 0x01010101u) << 2);
+        }
+        // 6-bit scales of sub-blocks 4q..4q+3, one per byte: low nibbles of scale bytes 4(q&1)..+3
+        // (high nibbles for q >= 2), bits 2q, 2q+1 of bytes 8..11
+        const uint32_t lo = ((q & 1) ? l.s1 : l.s0) >> (4 * (q >> 1));
+        const uint32_t sc = (lo & 0x0f0f0f0fu) | (((l.s2 >> sh) & 0x03030303u) << 4);
+        r.fa1 = d * (float)((int)(sc & 0xff) - 32);
+        r.fa2 = d * (float)((int)((sc >> 8) & 0xff) - 32);
+        r.fb1 = d * (float)((int)((sc >> 16) & 0xff) - 32);
+        r.fb2 = d * (float)((int)(sc >> 24) - 32);
         return r;
     }
 };

@@ -152,8 +152,14 @@ int fail(int code, const char *fmt, ...)
 }
 
 int block_elems(int t) { return t == GQ_Q8_0 ? 32 : 256; }
-int block_bytes(int t) { return t == GQ_Q8_0 ? 34 : (t == GQ_Q4_K ? 144 : (t == GQ_Q5_K ? 176 : 210)); }
-bool known_type(int t) { return t == GQ_Q8_0 || t == GQ_Q4_K || t == GQ_Q6_K || t == GQ_Q5_K; }
+int block_bytes(int t)
+{
+    return t == GQ_Q8_0 ? 34 : (t == GQ_Q4_K ? 144 : (t == GQ_Q5_K ? 176 : (t == GQ_Q3_K ? 110 : 210)));
+}
+bool known_type(int t) { return t == GQ_Q8_0 || t == GQ_Q4_K || t == GQ_Q6_K || t == GQ_Q5_K || t == GQ_Q3_K; }
+// Q5_K and Q3_K: q8_1 activations only, the streaming GEMM their only GEMM kernel, no device quantizer
+bool sgemm_only(int t) { return t == GQ_Q5_K || t == GQ_Q3_K; }
+const char *type_name(int t) { return t == GQ_Q3_K ? "Q3_K" : (t == GQ_Q5_K ? "Q5_K" : "type"); }
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -211,7 +217,7 @@ constexpr int64_t kSkinnyMinTokens = 5, kSkinnyMaxTokens = 16, kSkinnyForcedMax 
 bool use_skinny(int t, int form, int64_t N, int act = GQ_ACT_Q8_1)
 {
     const int sk = gq::tuning().skinny;
-    if (form != gq::AF_F16 || sk == 0 || t == GQ_Q5_K) return false; // (Q5_K: the streaming GEMM only)
+    if (form != gq::AF_F16 || sk == 0 || sgemm_only(t)) return false; // (Q5_K, Q3_K: the streaming GEMM only)
     if (sk == 1) return N <= kSkinnyForcedMax;
     // the fp8 variant has no decode kernel: its 1..4 tokens take the skinny kernel too
     const int64_t lo = act == GQ_ACT_FP8_E4M3 ? 1 : kSkinnyMinTokens;
@@ -241,7 +247,7 @@ bool gemm_knob_pinned()
 bool use_rgemm(int t, int form, int64_t M, int64_t N, int64_t K)
 {
     const int rg = gq::tuning().rgemm;
-    if (t == GQ_Q5_K) return false; // (no resident form: the streaming GEMM, whatever GQ_RGEMM says)
+    if (sgemm_only(t)) return false; // (no resident form: the streaming GEMM, whatever GQ_RGEMM says)
     if (rg == 0 || form != gq::AF_F16 || use_gemv(N, K) || use_blas(N, K) || K % 256 != 0) return false;
     if (gemm_rows_per_launch(t, M, K) < M || gemm_toks_per_launch(N, K) < N) return false;
     const gq::RGemmPlan p = gq::plan_rgemm(M, N, K);
@@ -324,9 +330,9 @@ constexpr int64_t kSgemmMinTokens = 17, kSgemmQ6MinTokens = 5;
 bool use_sgemm(int t, int form, int64_t M, int64_t N, int64_t K)
 {
     const int sg = gq::tuning().sgemm;
-    // Q5_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
+    // Q5_K's and Q3_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
     // knob of the other GEMMs says; rows over the per-launch limit are cut into chunks (compute())
-    if (t == GQ_Q5_K)
+    if (sgemm_only(t))
         return form == gq::AF_F16 && !use_gemv(N, K) && !use_blas(N, K) && K % 256 == 0 && M > 0 &&
                gemm_toks_per_launch(N, K) >= N && 256 * row_bytes_of(t, K) < ((int64_t)1 << 31);
     if (sg == 0 || form != gq::AF_F16 || use_gemv(N, K) || use_blas(N, K) || K % 256 != 0) return false;
@@ -357,15 +363,15 @@ size_t sgemm_partial_bytes(int t, int64_t M, int64_t N, int64_t K)
     return sgemm_streamk(t, M, N, K, it, g) ? g.partial_bytes : sgemm_plan(M, N, K).partial_bytes;
 }
 
-// Q5_K on the GEMM token counts: the streaming GEMM per chunk of gemm_rows_per_launch rows (rows
+// Q5_K / Q3_K on the GEMM token counts: the streaming GEMM per chunk of gemm_rows_per_launch rows (rows
 // are independent); its partials are the largest chunk shape's
-size_t q5k_partial_bytes(int64_t M, int64_t N, int64_t K)
+size_t q5k_partial_bytes(int t, int64_t M, int64_t N, int64_t K)
 {
-    const int64_t mr = gemm_rows_per_launch(GQ_Q5_K, M, K);
+    const int64_t mr = gemm_rows_per_launch(t, M, K);
     size_t p = 0;
     for (int64_t mc : {mr, M % mr})
         if (mc > 0) {
-            const size_t q = sgemm_partial_bytes(GQ_Q5_K, mc, N, K);
+            const size_t q = sgemm_partial_bytes(t, mc, N, K);
             p = q > p ? q : p;
         }
     return p;
@@ -440,8 +446,8 @@ size_t ws_bytes(int t, int act, int64_t M, int64_t N, int64_t K)
     const Route r = route(t, act, N, K);
     size_t b = act_bytes(act, N, K);
     if (r.blas) b += align_up((size_t)M * K * 2) + gq::blas_workspace_bytes(); // fp16 W + hipBLASLt
-    else if (!r.gemv && t == GQ_Q5_K) {
-        if (M > 0 && N > 0 && use_sgemm(t, r.form, M, N, K)) b += align_up(q5k_partial_bytes(M, N, K));
+    else if (!r.gemv && sgemm_only(t)) {
+        if (M > 0 && N > 0 && use_sgemm(t, r.form, M, N, K)) b += align_up(q5k_partial_bytes(t, M, N, K));
     } else if (!r.gemv && gq::gemm_supported(t, K) && M > 0 && N > 0) {
         // split-K partials of the largest need over the launch shapes (full and remainder chunks)
         // (the kernel is chosen by the call's token count, so every chunk runs the same arithmetic)
@@ -598,10 +604,11 @@ static int check_common(gq_type t, int64_t M, int64_t N, int64_t K)
     return GQ_OK;
 }
 
-// Q5_K runs with q8_1 activations only
+// Q5_K and Q3_K run with q8_1 activations only
 static int check_pair(gq_type t, int act)
 {
-    if (t == GQ_Q5_K && act == GQ_ACT_FP8_E4M3) return fail(GQ_EUNSUPPORTED, "Q5_K has no fp8-activation form");
+    if (sgemm_only(t) && act == GQ_ACT_FP8_E4M3)
+        return fail(GQ_EUNSUPPORTED, "%s has no fp8-activation form", type_name(t));
     return GQ_OK;
 }
 
@@ -697,11 +704,11 @@ static int compute(gq_type t, int act, const void *A, void *workspace, size_t wo
     hipError_t e;
     if (r.gemv) {
         e = gq::launch_gemv(t, (const uint8_t *)A, c.xq, c.xd, c.xs, (uint16_t *)C, M, N, K, ldc, s);
-    } else if (t == GQ_Q5_K) {
+    } else if (sgemm_only(t)) {
         // the streaming GEMM and nothing else; row chunks under the per-launch byte limit
         if (!use_sgemm(t, r.form, M, N, K))
-            return fail(GQ_EUNSUPPORTED, "Q5_K: not a streaming-GEMM shape (M=%lld N=%lld K=%lld)", (long long)M,
-                        (long long)N, (long long)K);
+            return fail(GQ_EUNSUPPORTED, "%s: not a streaming-GEMM shape (M=%lld N=%lld K=%lld)", type_name(t),
+                        (long long)M, (long long)N, (long long)K);
         const int64_t mr = gemm_rows_per_launch(t, M, K);
         gq::SGroupItem it;
         gq::SGroupPlan g;
@@ -823,10 +830,10 @@ int gq_mmq_ex(gq_type t, gq_act act, const void *A, const void *B, void *C, int6
         if (e != hipSuccess) return fail(GQ_EHIP, "HIP launch failed (rgemm): %s", hipGetErrorString(e));
         return GQ_OK;
     }
-    if (!r.gemv && !r.blas && t == GQ_Q5_K && !use_sgemm(t, r.form, M, N, K)) // (before any launch)
-        return fail(GQ_EUNSUPPORTED, "Q5_K: not a streaming-GEMM shape (M=%lld N=%lld K=%lld)", (long long)M,
+    if (!r.gemv && !r.blas && sgemm_only(t) && !use_sgemm(t, r.form, M, N, K)) // (before any launch)
+        return fail(GQ_EUNSUPPORTED, "%s: not a streaming-GEMM shape (M=%lld N=%lld K=%lld)", type_name(t), (long long)M,
                     (long long)N, (long long)K);
-    if (!r.gemv && !r.blas && t != GQ_Q5_K && act == GQ_ACT_Q8_1 && r.form == gq::AF_F16 && !use_skinny(t, r.form, N) &&
+    if (!r.gemv && !r.blas && !sgemm_only(t) && act == GQ_ACT_Q8_1 && r.form == gq::AF_F16 && !use_skinny(t, r.form, N) &&
         !use_sgemm(t, r.form, M, N, K) &&
         gemm_rows_per_launch(t, M, K) >= M &&
         gemm_toks_per_launch(N, K) >= N) {
@@ -981,6 +988,7 @@ int gq_quantize_weights(gq_type t, const void *X, void *Y, int64_t n, void *stre
 {
     g_err.clear();
     if (t == GQ_Q5_K) return fail(GQ_EUNSUPPORTED, "Q5_K has no device quantizer (gq_quantize_q5_k on the host)");
+    if (t == GQ_Q3_K) return fail(GQ_EUNSUPPORTED, "Q3_K has no device quantizer (gq_quantize_q3_k on the host)");
     if (t != GQ_Q8_0 && t != GQ_Q4_K && t != GQ_Q6_K) return fail(GQ_EUNSUPPORTED, "unknown gguf type %d", (int)t);
     if (n < 0) return fail(GQ_EINVAL, "negative size");
     const int qk = block_elems(t);
@@ -1338,6 +1346,6 @@ const char *gq_debug_route(gq_type t, gq_act act, int64_t M, int64_t N, int64_t 
         return p.splits == 1 ? "sgemm_kernel"
                : gq::sgemm_ilc(p) ? "sgemm_kernel (in-launch split-K sum)" : "sgemm_kernel + gemm_reduce_f16_kernel";
     }
-    if (t == GQ_Q5_K) return "none"; // (Q5_K never reaches the LDS-DMA GEMM: GQ_EUNSUPPORTED)
+    if (sgemm_only(t)) return "none"; // (Q5_K / Q3_K never reach the LDS-DMA GEMM: GQ_EUNSUPPORTED)
     return "gemm_kernel + gemm_reduce_f16_kernel";
 }

@@ -5,6 +5,7 @@
 //   Q4_K w = d*sc_j*q - dmin*m_j                   (q4_k_ref.c:358-364, q4_k.py:125-158)
 //   Q6_K w = d*sc_{e/16}*(q - 32)                  (q6_k_ref.c:320-336, q6_k.py:117-159)
 //   Q5_K w = (d*sc_j)*q - (dmin*m_j), q = 0..31    (no reference: include/gguf_quant.h)
+//   Q3_K w = (d*sc_{e/16})*q, q = -4..3, sc = -32..31 (no reference: include/gguf_quant.h)
 // one thread per 32-element sub-block, 4 x 16-byte stores.  PERM stores each 4-element group
 // in the order (0,2,1,3) -- the order act_quant's DEQ form uses for x~ -- so a GEMM over
 // (W_perm, x~) sums the same products as over the natural order.
@@ -97,6 +98,36 @@ __global__ __launch_bounds__(256) void dequant_kernel(const uint8_t *__restrict_
             const int hi = (byte_of(hw[i >> 2], i & 3) >> s) & 1;
             w[i] = ds * (float)(lo | (hi << 4)) - dm;
         }
+    } else if constexpr (F == Q3_K) {
+        // run jj = j & 7 of the super-block: elements 32*jj + i -> qs bytes 32*(jj >> 2).. at shift
+        // 2*(jj & 3), bit jj of the hmask bytes, scales 2jj and 2jj+1 (6 bits: low nibble of scale
+        // byte s & 7 -- high for s >= 8 -- and bits 2*(s >> 2).. of byte 8 + s % 4); the tail load
+        // is the block's last 16 bytes (94..109: scales at 2.., d at 14)
+        const uint8_t *b = rowp + 110 * (j >> 3);
+        const int jj = (int)(j & 7);
+        const u32x4 m0 = ld16(b), m1 = ld16(b + 16);
+        const u32x4 q0 = ld16(b + 32 + 32 * (jj >> 2)), q1 = ld16(b + 48 + 32 * (jj >> 2));
+        const u32x4 t = ld16(b + 94);
+        const uint32_t mw[8] = {m0.x, m0.y, m0.z, m0.w, m1.x, m1.y, m1.z, m1.w};
+        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        const uint32_t sw[3] = {__builtin_amdgcn_alignbyte(t.y, t.x, 2), __builtin_amdgcn_alignbyte(t.z, t.y, 2),
+                                __builtin_amdgcn_alignbyte(t.w, t.z, 2)};
+        const float d = h2f(t.w >> 16);
+        float ds[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int sidx = 2 * jj + k;
+            const uint32_t lo4 = (byte_of(sw[(sidx >> 2) & 1], sidx & 3) >> (4 * (sidx >> 3))) & 0xf;
+            const uint32_t hi2 = (byte_of(sw[2], sidx & 3) >> (2 * (sidx >> 2))) & 3;
+            ds[k] = d * (float)((int)(lo4 | (hi2 << 4)) - 32);
+        }
+        const int shl = 2 * (jj & 3);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const int lo = (byte_of(qw[i >> 2], i & 3) >> shl) & 3;
+            const int hi = (byte_of(mw[i >> 2], i & 3) >> jj) & 1;
+            w[i] = (i < 16 ? ds[0] : ds[1]) * (float)((lo | (hi << 2)) - 4);
+        }
     } else {
         static_assert(F == Q6_K, "dequant_kernel: unlisted format");
         // run jj = j & 7 of the super-block: elements 32*jj + i, i < 32 -> half h = jj >> 2,
@@ -132,6 +163,7 @@ hipError_t dequant_perm(int fmt, const uint8_t *A, uint16_t *W, int64_t M, int64
     case Q4_K: dequant_kernel<Q4_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     case Q6_K: dequant_kernel<Q6_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     case Q5_K: dequant_kernel<Q5_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
+    case Q3_K: dequant_kernel<Q3_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

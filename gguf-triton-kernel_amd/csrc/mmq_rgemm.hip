@@ -79,6 +79,11 @@ constexpr int kSpol = 16; // split-K partial stores write-through (sc1)
 //         The 112-B stride is 28 dwords: the 16 rows of a fragment read start on banks 28r mod 64
 //         = {0, 4, ..., 60}, and a lane pair's two 8-byte reads (or one 16-byte header read) cover
 //         the 4 banks from there -- all 64 banks once, as Q4_K's 80-B stride (20 dwords): no padding
+//   Q3_K  5 pieces: the 32 hmask bytes, qs bytes 32+32h..+31, then super-block bytes 94..109 (the
+//         12 scale bytes and d; the block's last 16 bytes, so no piece reaches past the tensor).
+//         Q4_K's 80-B stride (20 dwords): the 16 rows of a fragment read start on banks 20r mod 64
+//         = the 16 multiples of 4, the 8-byte hmask / qs reads of a lane pair and the 16-byte tail
+//         read cover the 4 banks from there -- conflict-free, no padding (streaming GEMM only)
 //   Q6_K  8 pieces: ql 64h.. (4), qh 128+32h.. (2), bytes 192..207 (scales), 194..209 (d at image
 //         byte 126); a 128-B stride is 2 bank sets, so row r's pieces are XOR-permuted by r & 7
 //         (hpos_swz).  (Until round 5 a ninth padding piece made the stride 144 B instead; the 8
@@ -87,6 +92,7 @@ template <int F> struct HImg;
 template <> struct HImg<Q8_0> { static constexpr int NPH = 9; };
 template <> struct HImg<Q4_K> { static constexpr int NPH = 5; };
 template <> struct HImg<Q5_K> { static constexpr int NPH = 7; };
+template <> struct HImg<Q3_K> { static constexpr int NPH = 5; };
 #ifndef GQ_Q6_NPH
 #define GQ_Q6_NPH 8 // (-DGQ_Q6_NPH=9: the padded image, A/B builds)
 #endif
@@ -102,6 +108,7 @@ template <int F> __device__ __forceinline__ uint32_t hsrc(int h, int pc)
     if constexpr (F == Q8_0) return 128u * h + 16u * pc;
     if constexpr (F == Q4_K) return pc == 0 ? 0u : 16u + 64u * h + 16u * (pc - 1);
     if constexpr (F == Q5_K) return pc < 3 ? 16u * pc : 48u + 64u * h + 16u * (pc - 3);
+    if constexpr (F == Q3_K) return pc < 2 ? 16u * pc : (pc < 4 ? 32u + 32u * h + 16u * (pc - 2) : 94u);
     return pc < 4 ? 64u * h + 16u * pc : (pc < 6 ? 128u + 32u * h + 16u * (pc - 4) : (pc == 6 ? 192u : 194u));
 }
 
@@ -169,6 +176,7 @@ template <int F> __device__ __forceinline__ void half_frags(const uint8_t *img, 
     if constexpr (F == Q8_0) stage_frags<Q8_0>(img - 128 * h, g, u, frag, 0); // (16-byte aligned: HRB = 144)
     else if constexpr (F == Q4_K) q4k_frags(img, img + 16 + 32 * (u & 1), g, u, frag);
     else if constexpr (F == Q5_K) q5k_frags(img, img + 16, img + 48 + 32 * (u & 1), g, u, frag);
+    else if constexpr (F == Q3_K) q3k_frags(img, g, u, frag);
     else if constexpr (HImg<F>::NPH == 8) q6k_half_frags_swz(img, g, h, u & 1, hpos_swz<F>(r), frag);
     else q6k_half_frags(img, g, h, u & 1, frag);
 }
@@ -1016,22 +1024,31 @@ template <int NB> constexpr int max_slds()
 {
     constexpr int a = SCfg<Q8_0, NB>::LDS, b = sgemm_lds<Q4_K, NB>(), c = SCfg<Q6_K, NB>::LDS;
     static_assert(SCfg<Q5_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q5_K within the others' LDS");
+    static_assert(SCfg<Q3_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q3_K within the others' LDS");
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
-template <int NB>
+// Q3 = 1: the launch holds a Q3_K part.  A kernel of its own: the Q3_K body beside the others
+// raised sgemm_grouped_kernel<8>'s registers (185 -> 195), so the other formats' launches keep
+// the kernel they had.
+template <int NB, int Q3 = 0>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a);
-template <int NB> int grouped_occ()
+template <int NB, int Q3 = 0> int grouped_occ()
 {
     int n = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sgemm_grouped_kernel<NB>, 64 * RW, 0) == hipSuccess ? n : 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sgemm_grouped_kernel<NB, Q3>, 64 * RW, 0) == hipSuccess ? n : 0;
 }
-template <int NB>
+template <int NB, int Q3>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
 {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[max_slds<NB>()];
     const int b = (int)blockIdx.x;
     auto run = [&](const SPart &q, const TileId &id, int64_t sb0, int64_t sb1) __attribute__((always_inline)) {
+        if constexpr (Q3 != 0)
+            if (q.fmt == Q3_K) {
+                sgemm_body<Q3_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
+                return;
+            }
         switch (q.fmt) {
         case Q8_0: sgemm_body<Q8_0, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
         case Q4_K:
@@ -1045,7 +1062,7 @@ __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
             return;
         case Q6_K: sgemm_body<Q6_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
         case Q5_K: sgemm_body<Q5_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
-        default: return; // (plan_sgemm_grouped admits the four formats only)
+        default: return; // (plan_sgemm_grouped admits the five formats only; Q3_K: above)
         }
     };
     if (!a.streamk) { // tile-granular splits: workgroup = (part, tile, split)
@@ -1292,7 +1309,7 @@ int rgemm_per_cu(int fmt, int nb)
     case Q8_0: GQ_RPC(Q8_0)
     case Q4_K: GQ_RPC(Q4_K)
     case Q6_K: GQ_RPC(Q6_K)
-    default: return 0; // (no resident form: Q5_K)
+    default: return 0; // (no resident form: Q5_K, Q3_K)
     }
 #undef GQ_RPC
 }
@@ -1361,6 +1378,7 @@ hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *
     case Q4_K: GQ_SG_NB(Q4_K)
     case Q6_K: GQ_SG_NB(Q6_K)
     case Q5_K: GQ_SG_NB(Q5_K)
+    case Q3_K: GQ_SG_NB(Q3_K)
     default: return hipErrorInvalidValue;
     }
 #undef GQ_SG_NB
@@ -1403,6 +1421,7 @@ hipError_t launch_sgemm_id(int fmt, const uint8_t *A, const uint16_t *X, uint16_
     case Q4_K: GQ_SID_NB(Q4_K)
     case Q6_K: GQ_SID_NB(Q6_K)
     case Q5_K: GQ_SID_NB(Q5_K)
+    case Q3_K: GQ_SID_NB(Q3_K)
     default: return hipErrorInvalidValue;
     }
 #undef GQ_SID_NB
@@ -1417,7 +1436,8 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
     int64_t units = 0, Lmax = 1;
     for (int i = 0; i < n; ++i) {
         if (items[i].M < 1 || items[i].K < 256 || items[i].K % 256 != 0) return g;
-        if (items[i].fmt != Q8_0 && items[i].fmt != Q4_K && items[i].fmt != Q6_K && items[i].fmt != Q5_K) return g;
+        if (items[i].fmt != Q8_0 && items[i].fmt != Q4_K && items[i].fmt != Q6_K && items[i].fmt != Q5_K && items[i].fmt != Q3_K)
+            return g;
         g.tiles_m[i] = (int)((items[i].M + RBM - 1) / RBM);
         const int64_t t = (int64_t)g.tiles_m[i] * tn, nsb = items[i].K / 256;
         units += t * nsb;
@@ -1448,7 +1468,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
         // (profiles/r05/sgemm_grouped_cost_ab.txt; -55, the K-chunked stream's best, 74.6 / 76.1 / 99.2)
         int64_t ctot = 0;
         for (int i = 0; i < n; ++i) {
-            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : (items[i].fmt == Q5_K ? 176 : 210));
+            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : (items[i].fmt == Q5_K ? 176 : (items[i].fmt == Q3_K ? 110 : 210)));
             g.cstart[i] = (int)ctot;
             ctot += (int64_t)g.tiles_m[i] * tn * (items[i].K / 256) * g.cost[i];
         }
@@ -1533,8 +1553,11 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     a.spol = kSpol;
     a.full = tuning().sgemm_full > 0;
     a.streamk = r.streamk = g.streamk ? 1 : 0;
+    bool q3 = false;
+    for (int i = 0; i < n; ++i) q3 = q3 || items[i].fmt == Q3_K;
     static const int occ[4] = {grouped_occ<1>(), grouped_occ<2>(), grouped_occ<4>(), grouped_occ<8>()};
-    const int oc = occ[g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3))];
+    static const int occ3[4] = {grouped_occ<1, 1>(), grouped_occ<2, 1>(), grouped_occ<4, 1>(), grouped_occ<8, 1>()};
+    const int oc = (q3 ? occ3 : occ)[g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3))];
     a.ilc = g.streamk && tuning().rgemm_ilc != 0 && g.blocks <= num_cus() * oc ? 1 : 0;
     a.U = r.U = g.U;
     a.W = r.W = g.blocks;
@@ -1553,7 +1576,7 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
             rb += g.tiles_m[i] * g.tiles_n * bpt;
         }
     }
-#define GQ_SGG(NB_)                                                                                                       case NB_:                                                                                                                 sgemm_grouped_kernel<NB_><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                                        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                                    if (r.n > 0) reduce_grouped_kernel<NB_><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);                                   return hipGetLastError();
+#define GQ_SGG(NB_)                                                                                                       case NB_:                                                                                                                 if (q3) sgemm_grouped_kernel<NB_, 1><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                             else sgemm_grouped_kernel<NB_><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                                        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                                    if (r.n > 0) reduce_grouped_kernel<NB_><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);                                   return hipGetLastError();
     switch (g.nb) {
         GQ_SGG(1) GQ_SGG(2) GQ_SGG(4) GQ_SGG(8)
     default: return hipErrorInvalidValue;
@@ -1576,7 +1599,7 @@ hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, in
     case Q8_0: GQ_RG_AQ(Q8_0)
     case Q4_K: GQ_RG_AQ(Q4_K)
     case Q6_K: GQ_RG_AQ(Q6_K)
-    default: return hipErrorInvalidValue; // (no resident form: Q5_K)
+    default: return hipErrorInvalidValue; // (no resident form: Q5_K, Q3_K)
     }
 #undef GQ_RG_AQ
 }

@@ -11,6 +11,7 @@
 //   Q4_K: term = ((d*sc)*dB)*idot - (dmin*m)*sB  in fp32   (the scalar is cast to fp16 first)
 //   Q5_K: Q4_K's term over codes 0..31 (no reference counterpart)
 //   Q6_K: term = dB*((d*sc_lo)*dot_lo + (d*sc_hi)*dot_hi) in fp32
+//   Q3_K: Q6_K's term over codes -4..3 and 6-bit scales -32..31 (no reference counterpart)
 //   C = fp16(float(C) + float(fp16(term)))
 // (build with -ffp-contract=off: no fused multiply-adds).
 //
@@ -146,6 +147,29 @@ void unpack_q6_k(const uint8_t *row, int64_t K, Row &r)
     }
 }
 
+// Q3_K: Q6_K's row form (d*sc per 16 elements, signed codes)
+void unpack_q3_k(const uint8_t *row, int64_t K, Row &r)
+{
+    const auto &T = half_table();
+    for (int64_t sb = 0; sb < K / 256; ++sb) {
+        const uint8_t *b = row + 110 * sb;
+        const uint8_t *hm = b, *qs = b + 32, *sc = b + 96;
+        const float d = T.v[ld16(b + 108)];
+        for (int s = 0; s < 16; ++s) {
+            const int lo4 = s < 8 ? sc[s] & 15 : sc[s - 8] >> 4;
+            const int hi2 = (sc[8 + s % 4] >> (2 * (s / 4))) & 3;
+            const float v = d * (float)((lo4 | (hi2 << 4)) - 32);
+            if (s & 1) r.c1[8 * sb + s / 2] = v;
+            else r.c0[8 * sb + s / 2] = v;
+        }
+        int8_t *dst = &r.q[256 * sb];
+        for (int e = 0; e < 256; ++e) {
+            const int h = e / 128, j = (e % 128) / 32, l = e % 32;
+            dst[e] = (int8_t)(((qs[32 * h + l] >> (2 * j)) & 3) + 4 * ((hm[l] >> (4 * h + j)) & 1) - 4);
+        }
+    }
+}
+
 // Token n's q8_1 row: codes and the fp16 d / s of each 32-block.
 struct Act {
     std::vector<int8_t> q;
@@ -220,16 +244,19 @@ void rows_q4_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N
     }
 }
 
+// (Q3 = true: Q3_K rows -- the same terms and fp16 running sum)
+template <bool Q3 = false>
 void rows_q6_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N, int64_t K, uint16_t *C)
 {
     const auto &T = half_table();
-    const int64_t nb = K / 32, row_bytes = (K / 256) * 210;
+    const int64_t nb = K / 32, row_bytes = (K / 256) * (Q3 ? 110 : 210);
     Row r;
     r.q.resize((size_t)K);
     r.c0.resize((size_t)nb);
     r.c1.resize((size_t)nb);
     for (int64_t m = m0; m < m1; ++m) {
-        unpack_q6_k(A + m * row_bytes, K, r);
+        if (Q3) unpack_q3_k(A + m * row_bytes, K, r);
+        else unpack_q6_k(A + m * row_bytes, K, r);
         for (int64_t n = 0; n < N; ++n) {
             const int8_t *xq = &x.q[n * K];
             const uint16_t *xd = &x.d[n * nb];
@@ -250,12 +277,12 @@ void rows_q6_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N
 extern "C" {
 
 // C (M, N) fp16 bits = the reference CPU MMQ of packed weights A (type 0 Q8_0, 1 Q4_K,
-// 2 Q6_K, 3 Q5_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
+// 2 Q6_K, 3 Q5_K, 4 Q3_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
 // Returns 0, or -1 for an unknown type / K not a whole number of blocks.
 int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int64_t K, uint16_t *C, int threads)
 {
     const int qk = type == 0 ? 32 : 256;
-    if (type < 0 || type > 3 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
+    if (type < 0 || type > 4 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
     if (M == 0 || N == 0) return 0;
     half_table();
     const Act x = unpack_act((const uint8_t *)B, N, K);
@@ -263,7 +290,8 @@ int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int
         if (type == 0) rows_q8_0((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 1) rows_q4_k<false>((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 3) rows_q4_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);
-        else rows_q6_k((const uint8_t *)A, x, m0, m1, N, K, C);
+        else if (type == 4) rows_q6_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);
+        else rows_q6_k<false>((const uint8_t *)A, x, m0, m1, N, K, C);
     };
     int64_t nt = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());
     nt = std::max<int64_t>(1, std::min<int64_t>(nt, M));

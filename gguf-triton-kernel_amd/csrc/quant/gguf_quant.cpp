@@ -73,6 +73,14 @@ void gq_quantize_q5_k(const float *x, void *y, int64_t n)
     });
 }
 
+// x: n fp32 values (n % 256 == 0), y: n/256 * 110 bytes (Q3_K: include/gguf_quant.h).
+void gq_quantize_q3_k(const float *x, void *y, int64_t n)
+{
+    parallel_blocks(n / QK, [&](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) q3k_block(x + b * QK, (uint8_t *)y + b * 110);
+    });
+}
+
 // x: n fp32 values (n % 256 == 0), y: n/256 * 210 bytes.
 void gq_quantize_q6_k(const float *x, void *y, int64_t n)
 {
@@ -161,6 +169,23 @@ void gq_dequantize_q5_k(const void *y, float *out, int64_t nblocks)
                 int q = ((qs[32 * (j >> 1) + i] >> (4 * (j & 1))) & 0x0f) + 16 * ((qh[i] >> j) & 1);
                 out[256 * b + 32 * j + i] = ds * (float)q - dm;
             }
+        }
+    }
+}
+
+// (d*sc_{e/16})*q in fp32, in that order (gq_dequantize_q6_k's)
+void gq_dequantize_q3_k(const void *y, float *out, int64_t nblocks)
+{
+    const uint8_t *p = (const uint8_t *)y;
+    for (int64_t b = 0; b < nblocks; ++b, p += 110) {
+        const uint8_t *hm = p, *qs = p + 32, *sc = p + 96;
+        float d = h2f(get16(p + 108));
+        for (int e = 0; e < 256; ++e) {
+            const int h = e / 128, j = (e % 128) / 32, l = e % 32, s = e / 16;
+            const int q = ((qs[32 * h + l] >> (2 * j)) & 3) + 4 * ((hm[l] >> (4 * h + j)) & 1) - 4;
+            const int lo4 = s < 8 ? sc[s] & 15 : sc[s - 8] >> 4;
+            const int hi2 = (sc[8 + s % 4] >> (2 * (s / 4))) & 3;
+            out[256 * b + e] = (d * (float)((lo4 | (hi2 << 4)) - 32)) * (float)q;
         }
     }
 }

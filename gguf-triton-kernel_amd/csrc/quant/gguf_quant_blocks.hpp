@@ -8,6 +8,7 @@
 //   q4k_block  <- (GGML) quantize_row_q4_K_ref / make_qkx2_quants, q4_k_ref.c:188-368
 //   q6k_block  <- (GGML) quantize_row_q6_K_ref / make_qx_quants, q6_k_ref.c:153-340
 //   q5k_block  (no reference; host only) q4k_block's search with 31 levels, Q5_K packing
+//   q3k_block  (no reference; host only) q6k_block's search over codes -4..3, Q3_K packing
 //   q8_block   <- utils/quantize/q8_0.py:4-49 (Q8_0), utils/quantize/q8_1.py:18-70 (Q8_1)
 #pragma once
 #include <algorithm>
@@ -251,9 +252,12 @@ GQ_QHD inline void q5k_block(const float *x, uint8_t *blk)
 // ---------------- Q6_K ----------------
 // Symmetric fit x ~ scale * l, l in [-32, 31], squared-x weights
 // (GGML make_qx_quants with nmax=32, rmse_type=1).  L receives l + 32.
+// NMAX: codes in [-NMAX, NMAX - 1], L receives l + NMAX (32: Q6_K, 4: Q3_K).  W2 = false: plain
+// squared error (Q3_K: no squared-x weights).
+template <int NMAX = 32, bool W2 = true>
 GQ_QHD inline float fit_scale_sym(const float *x, int8_t *L)
 {
-    constexpr int n = 16, nmax = 32;
+    constexpr int n = 16, nmax = NMAX;
     float peak = 0, amax = 0;
     for (int i = 0; i < n; ++i) {
         float a = std::fabs(x[i]);
@@ -272,7 +276,7 @@ GQ_QHD inline float fit_scale_sym(const float *x, int8_t *L)
         int l = round_magic(inv * x[i]);
         l = std::max(-nmax, std::min(nmax - 1, l));
         L[i] = (int8_t)(l + nmax);
-        float w = x[i] * x[i];
+        float w = W2 ? x[i] * x[i] : 1.f;
         sxl += w * x[i] * l;
         sl2 += w * l * l;
     }
@@ -285,7 +289,7 @@ GQ_QHD inline float fit_scale_sym(const float *x, int8_t *L)
         for (int i = 0; i < n; ++i) {
             int l = round_magic(cand * x[i]);
             l = std::max(-nmax, std::min(nmax - 1, l));
-            float w = x[i] * x[i];
+            float w = W2 ? x[i] * x[i] : 1.f;
             a += w * x[i] * l;
             b += w * l * l;
         }
@@ -341,6 +345,57 @@ GQ_QHD inline void q6k_block(const float *x, uint8_t *blk)
             ql[64 * half + l + 32] = (uint8_t)((b & 0x0f) | ((d & 0x0f) << 4));
             qh[32 * half + l] = (uint8_t)((a >> 4) | ((b >> 4) << 2) | ((c >> 4) << 4) | ((d >> 4) << 6));
         }
+    }
+}
+
+// ---------------- Q3_K ----------------
+// Q6_K's producer with codes -4..3: per 16 elements the symmetric scale search (fit_scale_sym<4, false>: plain squared error),
+// the sixteen scales quantized to 6 bits (-32..31) against the one of largest magnitude, which
+// takes -32; then the codes re-fitted to the quantized scales.  Packing: include/gguf_mmq.h.
+GQ_QHD inline void q3k_block(const float *x, uint8_t *blk)
+{
+    int8_t L[QK];
+    float sub[16];
+    float max_scale = 0, max_abs = 0;
+    for (int ib = 0; ib < 16; ++ib) {
+        sub[ib] = fit_scale_sym<4, false>(x + 16 * ib, L + 16 * ib);
+        float a = std::fabs(sub[ib]);
+        if (a > max_abs) {
+            max_abs = a;
+            max_scale = sub[ib];
+        }
+    }
+    __builtin_memset(blk, 0, 110);
+    int sc[16];
+    if (max_abs < kGroupMaxEps) { // all codes -4 + 4 = hmask set, scales 0 (stored 32), d = 0: zeros
+        for (int ib = 0; ib < 16; ++ib) sc[ib] = 0;
+        for (int i = 0; i < QK; ++i) L[i] = 4;
+        put16(blk + 108, f2h(0.f));
+    } else {
+        float inv = -32.f / max_scale;
+        uint16_t dh = f2h(1 / inv);
+        put16(blk + 108, dh);
+        for (int ib = 0; ib < 16; ++ib) sc[ib] = std::max(-32, std::min(31, round_magic(inv * sub[ib])));
+        for (int j = 0; j < 16; ++j) {
+            float d = h2f(dh) * sc[j];
+            if (!d) continue;
+            for (int i = 0; i < 16; ++i) {
+                int l = round_magic(x[16 * j + i] / d);
+                L[16 * j + i] = (int8_t)(std::max(-4, std::min(3, l)) + 4);
+            }
+        }
+    }
+    uint8_t *hm = blk, *qs = blk + 32, *scales = blk + 96;
+    for (int s = 0; s < 16; ++s) {
+        const int v = sc[s] + 32; // 0..63
+        if (s < 8) scales[s] |= (uint8_t)(v & 15);
+        else scales[s - 8] |= (uint8_t)((v & 15) << 4);
+        scales[8 + s % 4] |= (uint8_t)((v >> 4) << (2 * (s / 4)));
+    }
+    for (int e = 0; e < QK; ++e) {
+        const int h = e / 128, j = (e % 128) / 32, l = e % 32, c = L[e];
+        qs[32 * h + l] |= (uint8_t)((c & 3) << (2 * j));
+        hm[l] |= (uint8_t)((c >> 2) << (4 * h + j));
     }
 }
 

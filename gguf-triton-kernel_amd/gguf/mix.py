@@ -1,4 +1,4 @@
-"""The Q4_K_M (and Q5_K_M) layer-type mix of a Llama block (BASELINE.json configs[4]).
+"""The Q4_K_M (and Q5_K_M, Q3_K_M) layer-type mix of a Llama block (BASELINE.json configs[4]).
 
 llama.cpp's Q4_K_M recipe (not in the reference): every weight Q4_K except attn_v and
 ffn_down, which are Q6_K on a subset of layers -- the first eighth, the last eighth and every
@@ -26,3 +26,20 @@ def q5_k_m_layer_types(layer: int, n_layers: int = 32):
     """{projection: gguf type} of layer `layer` under Q5_K_M: Q4_K_M's rule with q5_k as the base type."""
     hi = "q6_k" if _more_bits(layer, n_layers) else "q5_k"
     return {name: (hi if name in ("attn_v", "ffn_down") else "q5_k") for name in LLAMA_LAYER_SHAPES}
+
+
+def q3_k_m_layer_types(layer: int, n_layers: int = 32):
+    """{projection: gguf type} of layer `layer` under Q3_K_M.
+
+    llama.cpp's rule for Llama models, written here from memory (nothing here can check it against
+    llama.cpp): attn_v q5_k on layers 0-1 and q4_k after, attn_output q4_k, ffn_down q5_k on the
+    first sixteenth of the layers and q4_k after, everything else q3_k."""
+    def one(name):
+        if name == "attn_v":
+            return "q5_k" if layer < 2 else "q4_k"
+        if name == "attn_output":
+            return "q4_k"
+        if name == "ffn_down":
+            return "q5_k" if layer < n_layers // 16 else "q4_k"
+        return "q3_k"
+    return {name: one(name) for name in LLAMA_LAYER_SHAPES}

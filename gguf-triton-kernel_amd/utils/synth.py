@@ -2,14 +2,14 @@
 
 Random bytes are valid blocks for every format except where a byte pair is an fp16 scale,
 so those fields are overwritten with fp16(U(0.5, 1.5) * 2^-7); Q6_K's
-int8 sub-block scales stay uniformly random (including negative ones).  The kernels have
+int8 sub-block scales and Q3_K's 6-bit ones stay uniformly random (including negative ones).  The kernels have
 no data-dependent control flow, so timings do not depend on the values.
 """
 from __future__ import annotations
 
 import numpy as np
 
-BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176)}
+BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176), "q3_k": (256, 110)}
 
 
 def _scales(rng, n):
@@ -32,6 +32,9 @@ def random_blocks(fmt: str, M: int, K: int, seed: int = 0) -> np.ndarray:
         d, dm = _scales(rng, nb), _scales(rng, nb)
         u16[:, 0], u16[:, 1] = d & 0xFF, d >> 8
         u16[:, 2], u16[:, 3] = dm & 0xFF, dm >> 8
+    elif fmt == "q3_k":
+        d = _scales(rng, nb)
+        u16[:, 108], u16[:, 109] = d & 0xFF, d >> 8
     else:
         d = _scales(rng, nb)
         u16[:, 208], u16[:, 209] = d & 0xFF, d >> 8

@@ -40,7 +40,18 @@ extern "C" {
  * gq_mmq_grouped[_ex] at 5..32 tokens answer GQ_EUNSUPPORTED for it and launch nothing.
  * gq_version() did not change with it: a caller detects Q5_K by gq_block_bytes(GQ_Q5_K) == 176
  * (a library without it answers 210). */
-typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3 } gq_type;
+/* GQ_Q3_K (GGML type 11, block_q3_K; the reference has none): 256 weights in 110 bytes, little
+ * endian, rows of K/256 blocks without padding (blocks are 2-byte aligned) --
+ *   [0:32] hmask[32] | [32:96] qs[64] | [96:108] scales[12] | [108:110] d fp16
+ * element e, h = e / 128, j = (e % 128) / 32, l = e % 32, s = e / 16:
+ *   q  = ((qs[32*h + l] >> 2*j) & 3) + 4*((hmask[l] >> (4*h + j)) & 1) - 4           (-4 .. 3)
+ *   sc = ((s < 8 ? scales[s] & 15 : scales[s-8] >> 4) | ((scales[8 + s%4] >> 2*(s/4)) & 3) << 4) - 32
+ *   w  = d*sc*q;  against q8_1 activations Q6_K's expression (a scale per 16 elements, no mins).
+ * As GQ_Q5_K: q8_1 activations only, gq_quantize_weights and gq_mmq_grouped[_ex] at 5..32 tokens
+ * answer GQ_EUNSUPPORTED and launch nothing; gq_mmq_id and gq_mmq_id_sorted take it under their
+ * limits.  gq_version() did not change with it: detect it by gq_block_bytes(GQ_Q3_K) == 110
+ * (a library without it answers 210). */
+typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3, GQ_Q3_K = 4 } gq_type;
 
 /* How the activations are quantized before the matmul.
  *   GQ_ACT_Q8_1      the reference's semantics: q8_1 (int8 per 32 elements, utils/quantize/q8_1.py).
@@ -59,7 +70,7 @@ enum {
     GQ_EUNSUPPORTED = 3 /* valid but not implemented (unknown type) */
 };
 
-/* Elements per block (32 / 256 / 256 / 256) and bytes per block (34 / 144 / 210 / 176). */
+/* Elements per block (32 / 256 / 256 / 256 / 256) and bytes per block (34 / 144 / 210 / 176 / 110). */
 int gq_block_elems(gq_type t);
 int gq_block_bytes(gq_type t);
 
@@ -138,7 +149,7 @@ int gq_act_prepare_grouped(gq_act act, const gq_prep_item *items, int n, void *s
 /*
  * Dequantize packed `t` weights to fp16: W[m * ldw + k] = w (the reference's block formulas,
  * utils/quantize/{q8_0,q4_k,q6_k}.py dequantize, evaluated in fp32, rounded once to fp16).
- * GQ_Q5_K: (d*sc_j)*q - (dmin*m_j), the formula above, in that order.
+ * GQ_Q5_K: (d*sc_j)*q - (dmin*m_j), the formula above, in that order.  GQ_Q3_K: (d*sc)*q.
  * M rows of K (a multiple of the block) elements.  gq_mmq uses the same kernel for its
  * library-GEMM path (N >= a few hundred tokens: fp16 W + hipBLASLt).
  */
@@ -163,7 +174,7 @@ int gq_quantize_fp8(const void *X, void *codes, void *scales, int64_t rows, int6
  *   GQ_Q8_0: X = n fp16 values (n % 32 == 0)  -> Y = n/32 blocks of 34 bytes (quantize_to_q8_0)
  *   GQ_Q4_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 144 bytes (quantize_to_q4_k)
  *   GQ_Q6_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 210 bytes (quantize_to_q6_k)
- * GQ_Q5_K: GQ_EUNSUPPORTED (host only: include/gguf_quant.h gq_quantize_q5_k).
+ * GQ_Q5_K, GQ_Q3_K: GQ_EUNSUPPORTED (host only: include/gguf_quant.h gq_quantize_q5_k / _q3_k).
  * X is read as flat blocks (a row-major (M, K) matrix gives the packed A of gq_mmq).  One thread
  * per block runs the host producer's exact code; no host sync.
  */
