@@ -94,8 +94,15 @@ __device__ __forceinline__ void act_quant_body(const uint16_t *__restrict__ X, i
     } else if constexpr (MODE == ACT_I8) {
         *(u32x2 *)(codes + row * K + 32 * j + 8 * sub) = (u32x2){q.codes[0], q.codes[1]};
         if (sub == 0) {
-            dout[j * ((rows + 3) & ~(int64_t)3) + row] = q.d;
-            if (sout) sout[j * ((rows + 3) & ~(int64_t)3) + row] = h2f(q.sbits); // (the integer-MFMA skinny kernel's s)
+            const int64_t ld = (rows + 3) & ~(int64_t)3;
+            dout[j * ld + row] = q.d;
+            if (sout) sout[j * ld + row] = h2f(q.sbits); // (the integer-MFMA skinny kernel's s)
+            // the pad columns too: the int8 GEMM loads four tokens' scales at a time, and what the
+            // workspace held there before reached its whole output (Q8_0 1000x77x1280: all zeros)
+            for (int64_t r = rows; row == rows - 1 && r < ld; ++r) {
+                dout[j * ld + r] = 0.f;
+                if (sout) sout[j * ld + r] = 0.f;
+            }
         }
     } else {
         *(u32x4 *)(xdeq + row * K + 32 * j + 8 * sub) = deq_words(q);

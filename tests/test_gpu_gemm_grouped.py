@@ -31,7 +31,8 @@ def _layer(types, seed=0):
 
 
 def _prepare(kl, B, N, K, act="q8_1", need=None):
-    need = need if need is not None else kl.workspace_size(kl.GQ_Q4_K, 256, N, K, act)
+    # (the activation part does not depend on the type: sized for Q8_0, valid at every K % 32 == 0)
+    need = need if need is not None else kl.workspace_size(kl.GQ_Q8_0, 256, N, K, act)
     ws = torch.empty(need, dtype=torch.uint8, device=_dev())
     kl.act_prepare(B, N, K, ws, act=act)
     return ws

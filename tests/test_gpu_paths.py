@@ -57,6 +57,26 @@ def test_q8_0_int8_mfma_gemm(M, N, K, splits, tune):
     assert O.allclose(exact, got, 0.01)
 
 
+def test_q8_0_int8_gemm_ignores_what_the_workspace_held(tune):
+    """N % 4 != 0: the block-major scale rows have pad columns (scale_ld(N) = 80 for 77 tokens) that
+    the int8 GEMM loads with the last tokens' scales.  act_quant writes them, so the result does not
+    depend on what the workspace held before the call: the same bits on a zeroed workspace and on
+    one full of 0x7f bytes (which, left in the pad, zeroed the whole output)."""
+    import kernels._lib as kl
+    tune(GQ_GEMM_I8=1)
+    M, N, K = 1000, 77, 1280
+    dev = _dev()
+    A_t = torch.from_numpy(random_blocks("q8_0", M, K, seed=5).view(np.int8)).to(dev)
+    B_t = torch.from_numpy(random_activations(N, K, seed=6)).to(dev)
+    outs = []
+    for fill in (0, 0x7F):
+        ws = torch.full((kl.workspace_size(kl.GQ_Q8_0, M, N, K),), fill, dtype=torch.uint8, device=dev)
+        outs.append(kl.mmq(kl.GQ_Q8_0, A_t, B_t, M, N, K, workspace=ws))
+    torch.cuda.synchronize()
+    assert torch.isfinite(outs[0].float()).all() and outs[0].abs().max() > 0
+    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
+
+
 @pytest.mark.parametrize("M,N,K", [(4096, 128, 4096), (11008, 128, 4096), (4096, 300, 11008)])
 def test_q8_0_int8_mfma_full_size(M, N, K, tune):
     """The int8 form at BASELINE sizes (configs[1]: 4096^2 x128; the 7B up/down shapes), every

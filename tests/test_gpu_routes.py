@@ -33,6 +33,48 @@ def test_default_routes(fmt, M, N, K, prepared, want):
     assert want in got, got
 
 
+@pytest.mark.parametrize("knob,kernel", [("GQ_KSTREAM", "kstream_kernel"), ("GQ_RGEMM", "rgemm_kernel")])
+@pytest.mark.parametrize("fmt", ["q4_k", "q8_0"])
+def test_raw_call_alignment_fallback(tune, knob, kernel, fmt):
+    """A raw call takes the one-launch kernels (activations quantized inside) only when B's rows are
+    16-byte aligned (ldb % 8 == 0, B & 15 == 0); gq_debug_route sees the shape alone.  A B that is
+    not falls back to act_quant + a prepared kernel: the same result within the GEMM tolerance
+    (another kernel may sum over K in another order)."""
+    import numpy as np
+
+    import kernels._lib as kl
+    import oracle as O
+    from test_gpu_route_sweep import GEMM_TOL
+    from utils.synth import random_activations, random_blocks
+    dev = torch.device("cuda:0")
+    t = kl.TYPES[fmt]
+    tune(**{knob: 1})
+    M, N, K = 256, 16, 512
+    for step in range(10):  # the smallest shape the forced kernel takes, M and K doubled in turn
+        if kernel in kl.route_name(t, M, N, K, prepared=False):
+            break
+        M, K = (2 * M, K) if step % 2 == 0 else (M, 2 * K)
+    assert kernel in kl.route_name(t, M, N, K, prepared=False), (M, N, K, kl.route_name(t, M, N, K))
+    A = torch.from_numpy(np.ascontiguousarray(random_blocks(fmt, M, K, seed=11).view(np.int8))).to(dev)
+    B = torch.from_numpy(random_activations(N, K, seed=12)).to(dev)
+    strided = torch.zeros((N, K + 4), dtype=torch.float16, device=dev)[:, :K]  # ldb % 8 == 4
+    strided.copy_(B)
+    shifted = torch.zeros(N * K + 8, dtype=torch.float16, device=dev)[1:1 + N * K].view(N, K)  # B & 15 == 2
+    shifted.copy_(B)
+    assert B.data_ptr() % 16 == 0 and strided.data_ptr() % 16 == 0 and strided.stride(0) % 8 != 0
+    assert shifted.data_ptr() % 16 == 2 and shifted.stride(0) == K
+    outs = [kl.mmq(t, A, x, M, N, K) for x in (B, strided, shifted)]
+    torch.cuda.synchronize()
+    ref = outs[0].cpu().numpy().astype(np.float32)
+    assert np.isfinite(ref).all()
+    for name, o in zip(("ldb % 8 != 0", "B & 15 != 0"), outs[1:]):
+        got = o.cpu().numpy()
+        assert np.isfinite(got.astype(np.float32)).all(), name
+        err = O.max_rel_err(got, ref)
+        print(f"{fmt} {knob}=1 {M}x{N}x{K} {name}: max rel err {err:.3g}")
+        assert err <= GEMM_TOL, (name, err)
+
+
 def test_route_knobs(tune):
     import kernels._lib as kl
     tune(GQ_GEMM_SPLITS=4)  # a GEMM knob pins the LDS-DMA GEMM
