@@ -12,6 +12,9 @@
 //   Q3_K 256 elems /110 B : [0:32] hmask | [32:96] qs (2-bit) | [96:108] 6-bit sc x16 | [108:110] d
 //                           q = ((qs[32*(e/128) + e%32] >> 2*((e%128)/32)) & 3)
 //                               + 4*((hmask[e%32] >> e/32) & 1) - 4;  w = d*(sc_{e/16} - 32)*q
+//   Q2_K 256 elems / 84 B : [0:16] scales (sc = low nibble, m = high, per 16 elements) |
+//                           [16:80] qs (2-bit, Q3_K's layout) | [80:82] d | [82:84] dmin
+//                           q = (qs[32*(e/128) + e%32] >> 2*((e%128)/32)) & 3;  w = d*sc_{e/16}*q - dmin*m_{e/16}
 //   Q8_1 (activations) 36 B: [0:2] d | [2:4] s = d*sum(q) | [4:36] qs int8[32]
 // Reference: block docs in kernels/mmq_q4_k.py:1-16, kernels/mmq_q6_k.py:1-14,
 // utils/quantize/q8_1.py:1-11; unpack rules kernels/mmq_q4_k.py:30-114, mmq_q6_k.py:28-68.
@@ -26,7 +29,7 @@
 
 namespace gq {
 
-enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3, Q3_K = 4 };
+enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3, Q3_K = 4, Q2_K = 5 };
 
 template <int F> struct Layout;
 template <> struct Layout<Q8_0> { static constexpr int QK = 32, BYTES = 34; };
@@ -38,8 +41,11 @@ constexpr bool has_mins(int f) { return f == Q4_K || f == Q5_K; }
 template <> struct Layout<Q3_K> { static constexpr int QK = 256, BYTES = 110; };
 // Q6_K's q8_1 arithmetic (a signed scale per 16 elements, no mins; the codes enter v_dot4 unsigned
 // and the offset -- Q6_K 32, Q3_K 4 -- is taken out with the activations' per-16 code sums)
-constexpr bool has_sums(int f) { return f == Q6_K || f == Q3_K; }
+// (Q2_K: unsigned codes 0..3 and a min per 16 elements -- the same per-16 code sums carry dmin*m)
+constexpr bool has_sums(int f) { return f == Q6_K || f == Q3_K || f == Q2_K; }
 constexpr int code_offset(int f) { return f == Q3_K ? 4 : 32; }
+// 84 = 4 * 21 bytes: every super-block and every field is 4-byte aligned
+template <> struct Layout<Q2_K> { static constexpr int QK = 256, BYTES = 84; };
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

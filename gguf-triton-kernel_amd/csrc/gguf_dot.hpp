@@ -6,6 +6,7 @@
 //   Q6_K : dB*(d*sc1*sum((q-32)*qB)_lo + d*sc2*sum(...)_hi)  mmq_q6_k_q8_1_cpu.py:117-150
 //   Q5_K : Q4_K's expression, q = 0..31
 //   Q3_K : Q6_K's expression with (q-4), the unit's two blocks being 2u and 2u+1
+//   Q2_K : dB*(d*sc*sum(q*qB) - dmin*m*sum(qB)) per 16 elements, blocks 2u and 2u+1
 // with exact int32 dot products (v_dot4_i32_i8) and fp32 accumulation.
 #pragma once
 #include "gguf_blocks.hpp"
@@ -18,7 +19,7 @@ struct Act {
     uint32_t q[NT][16]; // int8 codes of the two activation blocks
     float d[NT][2];
     float s[NT][2];  // q8_1 s (Q4_K / Q5_K min term)
-    int sum[NT][4];  // sum of codes per 16-element quarter (Q6_K -32 / Q3_K -4 offset)
+    int sum[NT][4];  // sum of codes per 16-element quarter (Q6_K -32 / Q3_K -4 offset, Q2_K mins)
 };
 
 template <int F, int NT>
@@ -100,6 +101,26 @@ __device__ __forceinline__ void dot_unit(const UnitRaw<F> &r, const Act<F, NT> &
             acc[t] += r.ds0 * a.d[t][0] * (float)i0 - r.dm0 * a.s[t][0] + r.ds1 * a.d[t][1] * (float)i1 -
                       r.dm1 * a.s[t][1];
         }
+    } else if constexpr (F == Q2_K) {
+        // per 16-element sub-block dB*(d*sc*i - dmin*m*sigma), i = sum q*qB and sigma = sum qB exact
+        // int32: the mins are per 16 elements, so the min term takes the per-16 code sums where
+        // Q6_K / Q3_K subtract OFF*sigma (the q8_1 block's s covers 32)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            int a1 = 0, a2 = 0, b1 = 0, b2 = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                a1 = dot4(r.ca[i], a.q[t][i], a1);
+                a2 = dot4(r.ca[4 + i], a.q[t][4 + i], a2);
+                b1 = dot4(r.cb[i], a.q[t][8 + i], b1);
+                b2 = dot4(r.cb[4 + i], a.q[t][12 + i], b2);
+            }
+            const float pa = (r.fa1 * (float)a1 - r.ma1 * (float)a.sum[t][0]) +
+                             (r.fa2 * (float)a2 - r.ma2 * (float)a.sum[t][1]);
+            const float pb = (r.fb1 * (float)b1 - r.mb1 * (float)a.sum[t][2]) +
+                             (r.fb2 * (float)b2 - r.mb2 * (float)a.sum[t][3]);
+            acc[t] += a.d[t][0] * pa + a.d[t][1] * pb;
+        }
     } else {
         static_assert(F == Q6_K || F == Q3_K, "dot_unit: unlisted format");
         constexpr int OFF = code_offset(F);
@@ -151,7 +172,7 @@ __device__ __forceinline__ uint32_t n02(uint32_t v) { return (v & 0x000f000fu) |
 template <int F, int NT, bool NS = false>
 __device__ __forceinline__ void dot_unit_h(const UnitRaw<F> &r, const ActH<NT> &a, float (&acc)[NT])
 {
-    static_assert(F == Q8_0 || F == Q4_K || F == Q6_K, "the fp8 variant has no Q5_K / Q3_K form");
+    static_assert(F == Q8_0 || F == Q4_K || F == Q6_K, "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
     typedef _Float16 hb2 __attribute__((ext_vector_type(2)));
     auto unbias = [](uint32_t v, float b) {
         const hb2 bb = {(_Float16)b, (_Float16)b};

@@ -184,6 +184,33 @@ __device__ __forceinline__ void q3k_frags(const uint8_t *img, int g, int u, f16x
     }
 }
 
+// Q2_K sub-stage u (elements 64u..64u+63) from a half-super-block image (mmq_rgemm.hip, half
+// h = u >> 1): the 16 scale bytes at 0, qs bytes 16+32h.. at 16, super-block bytes 68..83 at 48
+// (d at 60, dmin at 62); the fifth piece (64..79) only pads the row stride.  k-step n = elements
+// 64u+32n+[0,32): 2-bit codes at shift 4(u&1)+2n of the qs bytes; sub-block 4u+2n+(g>>1), its
+// scale in the low and its min in the high nibble of scale byte 4u+2n+(g>>1).
+// Q4_K's roundings: fp16 d*sc, fp16 -(dmin*m), one fp16 fma per weight on the exact code.
+__device__ __forceinline__ void q2k_frags(const uint8_t *img, int g, int u, f16x8 (&frag)[2])
+{
+    const uint32_t sb4 = *(const uint32_t *)(img + 4 * u); // scale bytes of sub-blocks 4u..4u+3
+    const uint32_t dd = *(const uint32_t *)(img + 60);
+    const float d = h2f(dd & 0xffffu), dmin = h2f(dd >> 16);
+    const u32x2 qs = *(const u32x2 *)(img + 16 + 8 * g);
+    const h2 bias = splat(-1024.f);
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const uint32_t b = (sb4 >> (8 * (2 * n + (g >> 1)))) & 0xffu;
+        const h2 ds = splat(d * (float)(b & 15u));
+        const h2 ndm = splat(-(dmin * (float)(b >> 4)));
+        const int sl = 4 * (u & 1) + 2 * n;
+        const uint32_t c0 = (qs.x >> sl) & 0x03030303u, c1 = (qs.y >> sl) & 0x03030303u;
+        frag[n] = frag4(__builtin_elementwise_fma(pair02(c0) + bias, ds, ndm),
+                        __builtin_elementwise_fma(pair13(c0) + bias, ds, ndm),
+                        __builtin_elementwise_fma(pair02(c1) + bias, ds, ndm),
+                        __builtin_elementwise_fma(pair13(c1) + bias, ds, ndm));
+    }
+}
+
 // Q6_K sub-stage s4 = (h, v): k-step 0 = elements 128h+32v+[0,32) (ql[64h+32v..] low nibbles,
 // qh bits 2v), k-step 1 = 128h+64+32v+[0,32) (same ql bytes, high nibbles; qh bits 4+2v).
 template <>

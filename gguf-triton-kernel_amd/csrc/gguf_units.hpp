@@ -8,6 +8,8 @@
 //          128h+64+32v+[0,32) ("B") -- ql bytes 64h+32v..+31 (both nibbles), qh 32h..+31
 //   Q3_K : super-block u/4, elements 64(u%4)+[0,64): all 32 hmask bytes (bits 2(u%4), 2(u%4)+1),
 //          qs bytes 32((u%4)/2)..+31 at shifts 4(u%2) and 4(u%2)+2, the 12 scale bytes and d
+//   Q2_K : super-block u/4, elements 64(u%4)+[0,64): qs bytes 32((u%4)/2)..+31 at shifts 4(u%2)
+//          and 4(u%2)+2, the four scale bytes 4(u%4)..+3, d and dmin (one dword)
 // so two consecutive units (2c, 2c+1) tile K-chunk c of 128 elements.  Every unit needs
 // 16-byte loads only (Q8_0/Q6_K fields are 2-byte aligned: unaligned dwordx4, which
 // gfx950 serves in unaligned mode).  act_blocks() gives the two 32-element activation
@@ -259,6 +261,53 @@ template <> struct UnitRaw<Q3_K> {
         r.fa2 = d * (float)((int)((sc >> 8) & 0xff) - 32);
         r.fb1 = d * (float)((int)((sc >> 16) & 0xff) - 32);
         r.fb2 = d * (float)((int)(sc >> 24) - 32);
+        return r;
+    }
+};
+
+// ---- Q2_K: one quarter of a super-block (elements 64q..64q+63: activation blocks 2u, 2u+1) ----
+// 40 bytes per unit, every read inside the 84-byte block: the 32 qs bytes of the unit's half, its
+// own four scale bytes and the d / dmin dword.  The same reads serve global memory (the GEMV) and
+// the decode ring, where the block keeps its 4-byte alignment: two 16-byte and two 4-byte reads
+template <> struct UnitLoad<Q2_K> {
+    u32x4 qa, qb;
+    uint32_t sc, dd; // scale bytes 4q..4q+3 (sc low nibble, m high); d | dmin << 16
+    __device__ __forceinline__ void load(const uint8_t *__restrict__ rowp, int u, int64_t /*nb32*/)
+    {
+        const int sb = u >> 2, q = u & 3;
+        const uint8_t *p = rowp + 84 * (int64_t)sb;
+        qa = ld16(p + 16 + 32 * (q >> 1));
+        qb = ld16(p + 32 + 32 * (q >> 1));
+        sc = ld4(p + 4 * q);
+        dd = ld4(p + 80);
+    }
+};
+
+template <> struct UnitRaw<Q2_K> {
+    float fa1, fa2, fb1, fb2; // d*sc of the four 16-element sub-blocks 4q..4q+3
+    float ma1, ma2, mb1, mb2; // dmin*m of the same
+    uint32_t ca[8], cb[8];     // 2-bit codes (0..3) of elements 64q+[0,32) and 64q+32+[0,32), one per byte
+
+    __device__ __forceinline__ static UnitRaw from(const UnitLoad<Q2_K> &l, int u, int64_t /*nb32*/)
+    {
+        UnitRaw r;
+        const int sl = 4 * (u & 1);
+        const float d = h2f(l.dd & 0xffffu), dmin = h2f(l.dd >> 16);
+        const uint32_t qs[8] = {l.qa.x, l.qa.y, l.qa.z, l.qa.w, l.qb.x, l.qb.y, l.qb.z, l.qb.w};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            r.ca[i] = (qs[i] >> sl) & 0x03030303u;
+            r.cb[i] = (qs[i] >> (sl + 2)) & 0x03030303u;
+        }
+        const uint32_t s = l.sc & 0x0f0f0f0fu, m = (l.sc >> 4) & 0x0f0f0f0fu;
+        r.fa1 = d * (float)(s & 0xff);
+        r.fa2 = d * (float)((s >> 8) & 0xff);
+        r.fb1 = d * (float)((s >> 16) & 0xff);
+        r.fb2 = d * (float)(s >> 24);
+        r.ma1 = dmin * (float)(m & 0xff);
+        r.ma2 = dmin * (float)((m >> 8) & 0xff);
+        r.mb1 = dmin * (float)((m >> 16) & 0xff);
+        r.mb2 = dmin * (float)(m >> 24);
         return r;
     }
 };

@@ -138,7 +138,7 @@ int num_cus()
 namespace {
 
 // One row per gq_type: block geometry, whether the streaming GEMM is the type's only GEMM kernel
-// (Q5_K and Q3_K: q8_1 activations only, no resident / skinny / K-chunked / LDS-DMA form) and the
+// (Q5_K, Q3_K and Q2_K: q8_1 activations only, no resident / skinny / K-chunked / LDS-DMA form) and the
 // kind of its device quantizer (launch_quant_blocks; -1: none, gq_quantize_<lname> on the host).
 struct TypeInfo {
     const char *name, *lname;
@@ -150,8 +150,10 @@ constexpr TypeInfo kTypes[] = {{"Q8_0", "q8_0", 32, 34, false, 0},
                                {"Q4_K", "q4_k", 256, 144, false, 1},
                                {"Q6_K", "q6_k", 256, 210, false, 2},
                                {"Q5_K", "q5_k", 256, 176, true, -1},
-                               {"Q3_K", "q3_k", 256, 110, true, -1}};
-static_assert(GQ_Q8_0 == 0 && GQ_Q4_K == 1 && GQ_Q6_K == 2 && GQ_Q5_K == 3 && GQ_Q3_K == 4, "kTypes is indexed by gq_type");
+                               {"Q3_K", "q3_k", 256, 110, true, -1},
+                               {"Q2_K", "q2_k", 256, 84, true, -1}};
+static_assert(GQ_Q8_0 == 0 && GQ_Q4_K == 1 && GQ_Q6_K == 2 && GQ_Q5_K == 3 && GQ_Q3_K == 4 && GQ_Q2_K == 5,
+              "kTypes is indexed by gq_type");
 bool known_type(int t) { return t >= 0 && t < (int)(sizeof(kTypes) / sizeof(kTypes[0])); }
 // (an unknown type answers with Q6_K's row, as gq_block_bytes always did: callers detect a type by it)
 const TypeInfo &type_info(int t) { return kTypes[known_type(t) ? t : (int)GQ_Q6_K]; }
@@ -309,10 +311,19 @@ constexpr int64_t kSgemmMinTokens = 17, kSgemmQ6MinTokens = 5;
 bool use_sgemm(int t, int form, int64_t M, int64_t N, int64_t K, const Tuning &u)
 {
     if (form != AF_F16 || use_gemv(N, K) || use_blas(N, K, u) || K % 256 != 0) return false;
-    // Q5_K's and Q3_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
+    // Q5_K's, Q3_K's and Q2_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
     // knob of the other GEMMs says; rows over the per-launch limit are cut into chunks
-    if (type_info(t).sgemm_only)
-        return M > 0 && gemm_toks_per_launch(N, K, u) >= N && 256 * row_bytes_of(t, K) < ((int64_t)1 << 31);
+    if (type_info(t).sgemm_only) {
+        // the call's tokens go into every launch (rows alone are cut).  Counted as the other GEMMs
+        // count them, in whole 128-token tiles of x~ -- but for a type whose 768 rows weigh less than
+        // 128 tokens' x~ at every K (768 * block bytes < 128 * 2 * block elements: Q2_K alone, 252 K
+        // against 256 K bytes) that count admits 16 tokens under any limit that cuts its rows at
+        // all, so for it the x~ bytes are counted exactly
+        const TypeInfo &ti = type_info(t);
+        const bool toks_fit = 768 * ti.bytes < 256 * ti.elems ? N * 2 * K <= gemm_max_bytes(u)
+                                                              : gemm_toks_per_launch(N, K, u) >= N;
+        return M > 0 && toks_fit && 256 * row_bytes_of(t, K) < ((int64_t)1 << 31);
+    }
     if (u.sgemm == 0) return false;
     if (gemm_rows_per_launch(t, M, K, u) < M || gemm_toks_per_launch(N, K, u) < N) return false;
     if (!plan_sgemm(M, N, K, u.sgemm_splits).ok) return false;
@@ -501,7 +512,7 @@ Plan plan_call(const Call &c, const Tuning &u)
     } else if (sgemm) {
         p.kernel = streamk ? K_SGEMM_STREAMK : K_SGEMM;
         if (!streamk) p.rg = sg;
-    } else if (!ti.sgemm_only) { // (Q5_K / Q3_K: the streaming GEMM or nothing, GQ_EUNSUPPORTED)
+    } else if (!ti.sgemm_only) { // (Q5_K / Q3_K / Q2_K: the streaming GEMM or nothing, GQ_EUNSUPPORTED)
         p.kernel = K_GEMM;
         if (!c.prepared && act == GQ_ACT_Q8_1 && p.form == AF_F16 && p.rows >= M && p.toks >= N) {
             // 16/32-token tiles whose split fits LDS: the GEMM quantizes the activations itself (no
@@ -561,7 +572,7 @@ const char *route_name(const Call &c, const Plan &p)
                : sgemm_ilc(p.rg) ? "sgemm_kernel (in-launch split-K sum)"
                                  : "sgemm_kernel + gemm_reduce_f16_kernel";
     case K_GEMM: return "gemm_kernel + gemm_reduce_f16_kernel";
-    case K_NONE: break; // (Q5_K / Q3_K never reach the LDS-DMA GEMM: GQ_EUNSUPPORTED)
+    case K_NONE: break; // (Q5_K / Q3_K / Q2_K never reach the LDS-DMA GEMM: GQ_EUNSUPPORTED)
     }
     return "none";
 }
@@ -672,7 +683,7 @@ size_t sharded_ws(int t, int64_t M, int64_t N, int64_t K, int world)
 // alone is refused here too, before any planning divides by a block count.  Two refused
 // combinations are still sized, as they always were: the fp8 variant at K % 256 != 0
 // (test_abi.py::test_fp8_host_argument_checks pins gq_mmq_workspace_size_ex(Q8_0, fp8, 8, 4, 96) > 0)
-// and Q5_K / Q3_K with fp8 activations.
+// and Q5_K / Q3_K / Q2_K with fp8 activations.
 bool sizable(int t, int act, int64_t M, int64_t N, int64_t K)
 {
     if (!gq::known_type(t) || (act != GQ_ACT_Q8_1 && act != GQ_ACT_FP8_E4M3)) return false;
@@ -734,7 +745,7 @@ static int check_act(int act, int64_t K)
 }
 
 // The shape checks every MMQ entry starts with, in this order: the type and the sizes, the
-// activation format, and the pair (Q5_K and Q3_K run with q8_1 activations only)
+// activation format, and the pair (Q5_K, Q3_K and Q2_K run with q8_1 activations only)
 static int check_mmq_shape(gq_type t, int act, int64_t M, int64_t N, int64_t K)
 {
     int rc = check_common(t, M, N, K);
@@ -839,7 +850,7 @@ static int launch_plan(const gq::Call &c, const gq::Plan &p, const void *A_, con
         it.ldc = ldc;
         return hip_rc(gq::launch_sgemm_grouped(&it, 1, N, p.sg, w.partials, s), "sgemm");
     }
-    case gq::K_SGEMM: // row chunks under the per-launch byte limit (Q5_K / Q3_K; the others are never cut)
+    case gq::K_SGEMM: // row chunks under the per-launch byte limit (Q5_K / Q3_K / Q2_K; the others are never cut)
         for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += p.rows) {
             const int64_t mc = M - m0 < p.rows ? M - m0 : p.rows;
             e = gq::launch_sgemm(t, A + m0 * gq::row_bytes_of(t, K), w.xdeq, C + m0, w.partials,

@@ -206,9 +206,9 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     uint8_t *ring = smem + wave * (NS * SLOT);
     uint8_t *codes = smem + RING;
     float *sd = (float *)(codes + NT * kp * (FP8 ? 2 : 1)); // FP8: quarter sums [NT][2*nb]
-    float *sx = sd + NT * nb; // Q4_K / Q5_K: s [NT][nb] (float); Q6_K / Q3_K: code sums [NT][2*nb] (int)
+    float *sx = sd + NT * nb; // Q4_K / Q5_K: s [NT][nb] (float); Q6_K / Q3_K / Q2_K: code sums [NT][2*nb] (int)
     static_assert(!FP8 || NT == 1 || ITC == 0, "fp8 decode: cached activations at one token only");
-    static_assert(!FP8 || (F != Q5_K && F != Q3_K), "the fp8 variant has no Q5_K / Q3_K form");
+    static_assert(!FP8 || (F != Q5_K && F != Q3_K && F != Q2_K), "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
     // FP8 at 2+ tokens: exact code pairs, no quarter sums (gguf_dot.hpp dot_unit_h NS; act_lds)
     constexpr bool F8NS = FP8 && NT >= 2;
     // FP8: x~ 16-byte piece P of a token row at piece P ^ ((P >> 4) & 7) (the lanes of a unit
@@ -530,7 +530,8 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
         // Q5_K blocks are 16-byte aligned in the ring; Q6_K: see above; Q3_K (110-byte blocks,
         // 2-byte aligned): plain reads as Q6_K's packed ring -- the dword-aligned form
         // (UnitLoad<Q3_K>::load_lds, -DGQ_Q3_LDS_PLAIN=0) measured 0.4-1.0 us slower at one token
-        // (4096^2 6.31 vs 6.68 us, 11008x4096 11.91 vs 12.89, 4096x11008 11.49 vs 12.15)
+        // (4096^2 6.31 vs 6.68 us, 11008x4096 11.91 vs 12.89, 4096x11008 11.49 vs 12.15);
+        // Q2_K (84-byte blocks, 4-byte aligned): plain reads too, two 16-byte and two 4-byte per unit
         if constexpr (F == Q8_0 || (F == Q3_K && !GQ_Q3_LDS_PLAIN)) l.load_lds(rowp, u, nb);
         else if constexpr (IMG) l.load_img(rowp, u);
         else l.load(rowp, u, nb);
@@ -696,27 +697,40 @@ size_t act_lds(int fmt, int nt, int64_t K, bool fp8 = false)
     const int64_t kp = (K + 63) / 64 * 64, nb = K / 32;
     if (fp8) // x~ + quarter sums (2+ tokens: Q4_K's block sums only, gguf_dot.hpp dot_unit_h NS)
         return (size_t)nt * kp * 2 + (nt == 1 ? (size_t)nt * nb * 2 * 4 : (fmt == Q4_K ? (size_t)nt * nb * 4 : 0));
-    // codes + d (+ Q4_K / Q5_K: s; Q6_K / Q3_K: the two 16-element code sums)
+    // codes + d (+ Q4_K / Q5_K: s; Q6_K / Q3_K / Q2_K: the two 16-element code sums)
     return (size_t)nt * kp + (size_t)nt * nb * 4 * (fmt == Q8_0 ? 1 : (fmt == Q4_K || fmt == Q5_K ? 2 : 3));
 }
 
 // the largest cached-chunk count ITC instantiated for (format, token tile); the fp8 form caches
 // at one token only, at most two units (64 VGPRs of x~ pairs)
 constexpr int kQ3Itc1 = 6, kQ3Itc2 = 3; // Q3_K: the most cached chunks at one / two tokens
+// Q2_K: Q3_K's activation registers, but 10 raw registers per unit in flight where Q3_K has 20:
+// 7 cached chunks at one token compile without scratch (236 VGPRs), as do 4 at two (253); two
+// tokens stay at Q3_K's 3, the most the grouped kernel that holds a Q2_K item carries
+#ifndef GQ_Q2_ITC1
+#define GQ_Q2_ITC1 7
+#endif
+#ifndef GQ_Q2_ITC2
+#define GQ_Q2_ITC2 3
+#endif
+constexpr int kQ2Itc1 = GQ_Q2_ITC1, kQ2Itc2 = GQ_Q2_ITC2;
+static_assert(kQ2Itc1 <= 7 && kQ2Itc2 <= 3, "launch_f / stream_decode_grouped_kernel carry no further Q2_K cases");
 int fp8_itc_max(int fmt, int nt) { return nt == 1 ? (fmt == Q6_K ? 1 : 2) : 0; }
 int itc_max(int fmt, int nt)
 {
     // (Q5_K: twice Q4_K's code registers per unit -- 7 cached units at one token spill)
     // (Q3_K: Q5_K's code registers and the code sums besides -- kQ3Itc1 / kQ3Itc2)
-    if (nt == 1) return fmt == Q6_K ? 4 : (fmt == Q5_K ? 6 : (fmt == Q3_K ? kQ3Itc1 : 7));
-    if (nt == 2) return fmt == Q6_K ? 1 : (fmt == Q3_K ? kQ3Itc2 : 4);
+    // (Q2_K: kQ2Itc1 / kQ2Itc2)
+    if (nt == 1) return fmt == Q6_K ? 4 : (fmt == Q5_K ? 6 : (fmt == Q3_K ? kQ3Itc1 : (fmt == Q2_K ? kQ2Itc1 : 7)));
+    if (nt == 2) return fmt == Q6_K ? 1 : (fmt == Q3_K ? kQ3Itc2 : (fmt == Q2_K ? kQ2Itc2 : 4));
     return 1;
 }
 
-bool known_fmt(int fmt) { return fmt == Q8_0 || fmt == Q4_K || fmt == Q6_K || fmt == Q5_K || fmt == Q3_K; }
+bool known_fmt(int fmt) { return fmt == Q8_0 || fmt == Q4_K || fmt == Q6_K || fmt == Q5_K || fmt == Q3_K || fmt == Q2_K; }
+bool q8_1_only(int fmt) { return fmt == Q5_K || fmt == Q3_K || fmt == Q2_K; } // (no form of the fp8 variant)
 int64_t row_bytes(int fmt, int64_t K)
 {
-    return fmt == Q8_0 ? K / 32 * 34 : K / 256 * (fmt == Q4_K ? 144 : (fmt == Q5_K ? 176 : (fmt == Q3_K ? 110 : 210)));
+    return fmt == Q8_0 ? K / 32 * 34 : K / 256 * (fmt == Q4_K ? 144 : (fmt == Q5_K ? 176 : (fmt == Q3_K ? 110 : (fmt == Q2_K ? 84 : 210))));
 }
 
 // wgs: the workgroups the matrix gets (0: a launch of its own, the whole chip; a grouped launch
@@ -725,7 +739,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
 {
     // at most 4 tokens per workgroup (NT = 8 spills registers); N = 5..8 runs two token groups,
     // whose second pass over the weights is served largely by the Infinity Cache
-    if (!known_fmt(fmt) || (p.fp8 && (fmt == Q5_K || fmt == Q3_K))) return false; // (no Q5_K / Q3_K form of the fp8 variant)
+    if (!known_fmt(fmt) || (p.fp8 && q8_1_only(fmt))) return false;
     const int nts[3] = {1, 2, 4};
     p.nt = 4;
     for (int i = 0; i < 3; ++i)
@@ -769,7 +783,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
         while ((1 << lp2) < cpr && lp2 < 6) ++lp2;
         g.lp2 = lp2;
     } else {
-        const int64_t unit64 = fmt == Q8_0 ? 64 * 68 : (fmt == Q4_K ? 64 * 36 : (fmt == Q5_K ? 64 * 44 : (fmt == Q3_K ? 64 * 110 / 4 : 64 * (img ? kImgSB : 210) / 4)));
+        const int64_t unit64 = fmt == Q8_0 ? 64 * 68 : (fmt == Q4_K ? 64 * 36 : (fmt == Q5_K ? 64 * 44 : (fmt == Q3_K ? 64 * 110 / 4 : (fmt == Q2_K ? 64 * 21 : 64 * (img ? kImgSB : 210) / 4))));
         if (cap < unit64) return false; // a 64-unit segment must fit one task (tuning builds with small NI)
         g.G = 1;
         g.segu = (int)(64 * (cap / unit64));
@@ -782,7 +796,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
     const int64_t itc = (cpr + (1 << g.lp2) - 1) >> g.lp2, units = itc * (upr / cpr);
     p.itc = ((p.nt <= 2 && units <= (fmt == Q6_K ? 2 : 4)) || (p.nt == 1 && units <= 8)) ? (int)itc : 0;
     // only the instantiated chunk counts (launch_f, stream_decode_grouped_kernel): one token
-    // 0..7 (Q6_K 0..4, Q5_K / Q3_K 0..6), two 0..4 (Q6_K 0..1), four 0..1 -- e.g. K = 29568 at one token gives 8
+    // 0..7 (Q6_K 0..4, Q5_K / Q3_K 0..6), two 0..4 (Q6_K 0..1, Q3_K / Q2_K 0..3), four 0..1 -- e.g. K = 29568 at one token gives 8
     if (p.itc > itc_max(fmt, p.nt)) p.itc = 0;
     // four tokens, one unit per lane (K <= 4096): cached too (Q6_K 14336x4096 x4 27.7 -> 20.7 us,
     // profiles/r02/decode_nt4_cache_ab.txt)
@@ -820,9 +834,9 @@ hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *
 {
 #define GQ_LT(nt, itc) launch_t<F, nt, itc>(A, X, ldx, C, M, N, K, ldc, p, s)
 #define GQ_LTI(nt, itc) launch_t<F, nt, itc, 1>(A, X, ldx, C, M, N, K, ldc, p, s)
-    if constexpr (F == Q5_K || F == Q3_K)
+    if constexpr (F == Q5_K || F == Q3_K || F == Q2_K)
         if (p.fp8) return hipErrorInvalidValue;
-    if constexpr (F != Q5_K && F != Q3_K) if (p.fp8) { // (itc: one token only, fp8_itc_max)
+    if constexpr (F != Q5_K && F != Q3_K && F != Q2_K) if (p.fp8) { // (itc: one token only, fp8_itc_max)
         if (p.nt == 1 && p.itc == 1) {
             if constexpr (F == Q6_K)
                 if (p.img) return launch_t<F, 1, 1, 1, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
@@ -878,16 +892,16 @@ hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *
         case 13: return GQ_LT(1, 5);
         case 14: return GQ_LT(1, 6);
         case 15:
-            if constexpr (F != Q5_K && F != Q3_K) return GQ_LT(1, 7);
-            return hipErrorInvalidValue; // (itc_max: Q5_K and Q3_K cache at most 6 units)
+            if constexpr (F != Q5_K && F != Q3_K && (F != Q2_K || kQ2Itc1 >= 7)) return GQ_LT(1, 7);
+            return hipErrorInvalidValue; // (itc_max: Q5_K and Q3_K cache at most 6 units, Q2_K kQ2Itc1)
 
         case 16: return GQ_LT(2, 0);
         case 17: return GQ_LT(2, 1);
         case 18: return GQ_LT(2, 2);
         case 19: return GQ_LT(2, 3);
         case 20:
-            if constexpr (F != Q3_K) return GQ_LT(2, 4);
-            return hipErrorInvalidValue; // (itc_max: Q3_K caches at most 3 units at two tokens)
+            if constexpr (F != Q3_K && F != Q2_K) return GQ_LT(2, 4);
+            return hipErrorInvalidValue; // (itc_max: Q3_K and Q2_K cache at most 3 units at two tokens)
         case 32: return GQ_LT(4, 0);
         case 33: return GQ_LT(4, 1);
         default: return hipErrorInvalidValue; // (pick() caps itc at itc_max)
@@ -924,14 +938,19 @@ struct GroupedArgs {
 // (kernel-resource-usage) -- and decode_grouped_ok refuses a mixed launch beyond that.
 // Q5 = 2: the launch holds a Q3_K item.  Again a kernel of its own (the Q5 = 0 and Q5 = 1 kernels
 // keep their case sets): Q5 = 1's cases and Q3_K's, at one token up to kQ3GroupItc cached chunks.
+// Q5 = 3: the launch holds a Q2_K item.  A fourth kernel for the same reason: Q5 = 2's cases (a
+// Q2_K file's layer holds Q3_K items too) and Q2_K's, at one token up to kQ2GroupItc cached chunks.
 #ifndef GQ_Q3_GROUP_ITC
 #define GQ_Q3_GROUP_ITC 3
 #endif
-constexpr int kQ5GroupItc = 4, kQ3GroupItc = GQ_Q3_GROUP_ITC;
+#ifndef GQ_Q2_GROUP_ITC
+#define GQ_Q2_GROUP_ITC 3
+#endif
+constexpr int kQ5GroupItc = 4, kQ3GroupItc = GQ_Q3_GROUP_ITC, kQ2GroupItc = GQ_Q2_GROUP_ITC;
 template <int NT, int FP8 = 0, int Q5 = 0>
 __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const GroupedArgs args)
 {
-    static_assert(!(FP8 && Q5), "the fp8 variant has no Q5_K / Q3_K form");
+    static_assert(!(FP8 && Q5), "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
     const int b = (int)blockIdx.x;
     int i = 0;
@@ -961,6 +980,16 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GF(Q8_0, 0, 0) GQ_GF(Q4_K, 0, 0) GQ_GF(Q6_K, 0, 0) GQ_GF(Q6_K, 0, 1)
         default: return;
         }
+    } else if constexpr (NT == 1 && Q5 == 3) { // (kQ2GroupItc)
+#define GQ_G2(itc) GQ_GB(Q8_0, itc) GQ_GB(Q4_K, itc) GQ_GB(Q6_K, itc) GQ_GBI(itc) GQ_GB(Q5_K, itc) GQ_GB(Q3_K, itc) GQ_GB(Q2_K, itc)
+        switch (q.code) {
+            GQ_G2(0) GQ_G2(1) GQ_G2(2)
+#if GQ_Q2_GROUP_ITC >= 3
+            GQ_G2(3)
+#endif
+        default: return;
+        }
+#undef GQ_G2
     } else if constexpr (NT == 1 && Q5 == 2) { // (kQ3GroupItc)
 #define GQ_G3(itc) GQ_GB(Q8_0, itc) GQ_GB(Q4_K, itc) GQ_GB(Q6_K, itc) GQ_GBI(itc) GQ_GB(Q5_K, itc) GQ_GB(Q3_K, itc)
         switch (q.code) {
@@ -1000,8 +1029,12 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1) GQ_GB(Q5_K, 2) GQ_GB(Q5_K, 3) GQ_GB(Q5_K, 4)
         default: break;
         }
-        if constexpr (Q5 == 2) switch (q.code) { // (kQ3Itc2)
+        if constexpr (Q5 >= 2) switch (q.code) { // (kQ3Itc2)
             GQ_GB(Q3_K, 0) GQ_GB(Q3_K, 1) GQ_GB(Q3_K, 2) GQ_GB(Q3_K, 3)
+        default: break;
+        }
+        if constexpr (Q5 == 3) switch (q.code) { // (kQ2Itc2)
+            GQ_GB(Q2_K, 0) GQ_GB(Q2_K, 1) GQ_GB(Q2_K, 2) GQ_GB(Q2_K, 3)
         default: break;
         }
     } else {
@@ -1013,8 +1046,12 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1)
         default: break;
         }
-        if constexpr (Q5 == 2) switch (q.code) {
+        if constexpr (Q5 >= 2) switch (q.code) {
             GQ_GB(Q3_K, 0) GQ_GB(Q3_K, 1)
+        default: break;
+        }
+        if constexpr (Q5 == 3) switch (q.code) {
+            GQ_GB(Q2_K, 0) GQ_GB(Q2_K, 1)
         default: break;
         }
     }
@@ -1086,7 +1123,7 @@ hipError_t launch_id_t(const IdArgs &a, int pairs, size_t lds, hipStream_t s)
     return hipGetLastError();
 }
 
-// launch_f's one-token cases (itc_max: Q8_0 / Q4_K 0..7, Q5_K / Q3_K 0..6, Q6_K 0..4 packed and image)
+// launch_f's one-token cases (itc_max: Q8_0 / Q4_K / Q2_K 0..7, Q5_K / Q3_K 0..6, Q6_K 0..4 packed and image)
 template <int F>
 hipError_t launch_id_f(const IdArgs &a, int pairs, const Pick &p, hipStream_t s)
 {
@@ -1112,7 +1149,7 @@ hipError_t launch_id_f(const IdArgs &a, int pairs, const Pick &p, hipStream_t s)
     if constexpr (F != Q6_K) {
         if (p.itc == 5) return GQ_LID(5, 0);
         if (p.itc == 6) return GQ_LID(6, 0);
-        if constexpr (F != Q5_K && F != Q3_K)
+        if constexpr (F != Q5_K && F != Q3_K && (F != Q2_K || kQ2Itc1 >= 7))
             if (p.itc == 7) return GQ_LID(7, 0);
     }
 #undef GQ_LID
@@ -1151,6 +1188,7 @@ hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int
         case Q6_K: e = launch_f<Q6_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
         case Q5_K: e = launch_f<Q5_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
         case Q3_K: e = launch_f<Q3_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
+        case Q2_K: e = launch_f<Q2_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
         default: return hipErrorInvalidValue;
         }
         if (e != hipSuccess) return e;
@@ -1166,18 +1204,19 @@ bool decode_grouped_ok(const DecodeItem *items, int n, int64_t N, bool fp8)
         if (it.M < 1 || !decode_fused_ok(it.fmt, N, it.K, fp8)) return false;
         if (it.M * row_bytes(it.fmt, it.K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets
     }
-    // a one-token launch with a Q5_K or Q3_K item: every item within the cached chunks its kernel carries
-    bool q5 = false, q3 = false;
+    // a one-token launch with a Q5_K, Q3_K or Q2_K item: every item within the cached chunks its kernel carries
+    bool q5 = false, q3 = false, q2 = false;
     for (int i = 0; i < n; ++i) {
         q5 = q5 || items[i].fmt == Q5_K;
         q3 = q3 || items[i].fmt == Q3_K;
+        q2 = q2 || items[i].fmt == Q2_K;
     }
-    if (q5 || q3) {
+    if (q5 || q3 || q2) {
         if (fp8) return false;
         for (int i = 0; i < n; ++i) {
             Pick p;
             if (!pick(items[i].fmt, items[i].M, N, items[i].K, p)) return false;
-            if (p.nt == 1 && p.itc > (q3 ? kQ3GroupItc : kQ5GroupItc)) return false;
+            if (p.nt == 1 && p.itc > (q2 ? kQ2GroupItc : (q3 ? kQ3GroupItc : kQ5GroupItc))) return false;
         }
     }
     return true;
@@ -1278,15 +1317,21 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
             blocks += p.grid;
         }
         a.n = np;
-        bool q5 = false, q3 = false;
+        bool q5 = false, q3 = false, q2 = false;
         for (int j = 0; j < np; ++j) {
             q5 = q5 || items[pi[j]].fmt == Q5_K;
             q3 = q3 || items[pi[j]].fmt == Q3_K;
+            q2 = q2 || items[pi[j]].fmt == Q2_K;
         }
-        if ((q5 || q3) && nt == 1)
+        if ((q5 || q3 || q2) && nt == 1)
             for (int j = 0; j < np; ++j)
-                if (a.p[j].code % 8 > (q3 ? kQ3GroupItc : kQ5GroupItc)) return hipErrorInvalidValue; // (decode_grouped_ok)
-        hipError_t e = q3        ? (fp8 ? hipErrorInvalidValue
+                if (a.p[j].code % 8 > (q2 ? kQ2GroupItc : (q3 ? kQ3GroupItc : kQ5GroupItc)))
+                    return hipErrorInvalidValue; // (decode_grouped_ok)
+        hipError_t e = q2        ? (fp8 ? hipErrorInvalidValue
+                                        : nt == 1 ? launch_grouped_nt<1, 0, 3>(a, blocks, lds, s)
+                                        : nt == 2 ? launch_grouped_nt<2, 0, 3>(a, blocks, lds, s)
+                                                  : launch_grouped_nt<4, 0, 3>(a, blocks, lds, s))
+                       : q3        ? (fp8 ? hipErrorInvalidValue
                                         : nt == 1 ? launch_grouped_nt<1, 0, 2>(a, blocks, lds, s)
                                         : nt == 2 ? launch_grouped_nt<2, 0, 2>(a, blocks, lds, s)
                                                   : launch_grouped_nt<4, 0, 2>(a, blocks, lds, s))
@@ -1345,6 +1390,7 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
     case Q6_K: return launch_id_f<Q6_K>(a, (int)pairs, p, s);
     case Q5_K: return launch_id_f<Q5_K>(a, (int)pairs, p, s);
     case Q3_K: return launch_id_f<Q3_K>(a, (int)pairs, p, s);
+    case Q2_K: return launch_id_f<Q2_K>(a, (int)pairs, p, s);
     default: return hipErrorInvalidValue;
     }
 }

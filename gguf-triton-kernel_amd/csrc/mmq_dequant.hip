@@ -6,6 +6,7 @@
 //   Q6_K w = d*sc_{e/16}*(q - 32)                  (q6_k_ref.c:320-336, q6_k.py:117-159)
 //   Q5_K w = (d*sc_j)*q - (dmin*m_j), q = 0..31    (no reference: include/gguf_quant.h)
 //   Q3_K w = (d*sc_{e/16})*q, q = -4..3, sc = -32..31 (no reference: include/gguf_quant.h)
+//   Q2_K w = (d*sc_{e/16})*q - dmin*m_{e/16}, q = 0..3, sc, m = 0..15 (no reference: include/gguf_quant.h)
 // one thread per 32-element sub-block, 4 x 16-byte stores.  PERM stores each 4-element group
 // in the order (0,2,1,3) -- the order act_quant's DEQ form uses for x~ -- so a GEMM over
 // (W_perm, x~) sums the same products as over the natural order.
@@ -98,6 +99,27 @@ __global__ __launch_bounds__(256) void dequant_kernel(const uint8_t *__restrict_
             const int hi = (byte_of(hw[i >> 2], i & 3) >> s) & 1;
             w[i] = ds * (float)(lo | (hi << 4)) - dm;
         }
+    } else if constexpr (F == Q2_K) {
+        // run jj = j & 7 of the super-block: elements 32*jj + i -> qs bytes 32*(jj >> 2).. at shift
+        // 2*(jj & 3), scale bytes 2jj and 2jj+1 (sc low nibble, m high); every load inside the block.
+        // d*sc*q and dmin*m are exact in fp32, so the weight is rounded once, fused or not
+        const uint8_t *b = rowp + 84 * (j >> 3);
+        const int jj = (int)(j & 7);
+        const u32x4 q0 = ld16(b + 16 + 32 * (jj >> 2)), q1 = ld16(b + 32 + 32 * (jj >> 2));
+        const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+        const uint32_t sw = ld4(b + 4 * (jj >> 1)), dd = ld4(b + 80);
+        const float d = h2f(dd & 0xffffu), dmin = h2f(dd >> 16);
+        float ds[2], dm[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const uint32_t sb = byte_of(sw, 2 * (jj & 1) + k);
+            ds[k] = d * (float)(sb & 15u);
+            dm[k] = dmin * (float)(sb >> 4);
+        }
+        const int shl = 2 * (jj & 3);
+#pragma unroll
+        for (int i = 0; i < 32; ++i)
+            w[i] = (i < 16 ? ds[0] : ds[1]) * (float)((byte_of(qw[i >> 2], i & 3) >> shl) & 3) - (i < 16 ? dm[0] : dm[1]);
     } else if constexpr (F == Q3_K) {
         // run jj = j & 7 of the super-block: elements 32*jj + i -> qs bytes 32*(jj >> 2).. at shift
         // 2*(jj & 3), bit jj of the hmask bytes, scales 2jj and 2jj+1 (6 bits: low nibble of scale
@@ -164,6 +186,7 @@ hipError_t dequant_perm(int fmt, const uint8_t *A, uint16_t *W, int64_t M, int64
     case Q6_K: dequant_kernel<Q6_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     case Q5_K: dequant_kernel<Q5_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     case Q3_K: dequant_kernel<Q3_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
+    case Q2_K: dequant_kernel<Q2_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -8,6 +8,7 @@
 //   Q6_K : dB*(d*sc1*sum((q-32)*qB)_lo + d*sc2*sum(...)_hi)  mmq_q6_k_q8_1_cpu.py:117-150
 //   Q5_K : Q4_K's expression with q = 0..31
 //   Q3_K : Q6_K's expression with (q-4) over blocks 2u, 2u+1
+//   Q2_K : dB*(d*sc*sum(q*qB) - dmin*m*sum(qB)) per 16 elements over blocks 2u, 2u+1
 // with exact int32 dot products (v_dot4_i32_i8) and fp32 accumulation (the reference
 // accumulates in fp16), one fp16 rounding at the store.
 //
@@ -85,7 +86,7 @@ template <int F>
 hipError_t launch_fmt(const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C, int64_t M,
                       int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    // rows per wave (profiles/r02/gemv_rows_tune.txt): 1-2 tokens Q8_0 4, Q4_K / Q6_K 2 (Q5_K, Q3_K as Q4_K)
+    // rows per wave (profiles/r02/gemv_rows_tune.txt): 1-2 tokens Q8_0 4, Q4_K / Q6_K 2 (Q5_K, Q3_K, Q2_K as Q4_K)
     // (Q4_K 4096x28672 x2 30.3 -> 23.9 us, Q6_K 8192x28672 x2 64.9 -> 58.3); 3-4 tokens 2,
     // Q6_K 4 (x4 81.7 -> 72.9)
     const int r = N <= 2 ? (F == Q8_0 ? 4 : 2) : (F == Q6_K ? 4 : 2);
@@ -111,6 +112,7 @@ hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float 
     case Q6_K: return launch_fmt<Q6_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
     case Q5_K: return launch_fmt<Q5_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
     case Q3_K: return launch_fmt<Q3_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
+    case Q2_K: return launch_fmt<Q2_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
     default: return hipErrorInvalidValue; // (an unlisted format never runs another format's strides)
     }
 }

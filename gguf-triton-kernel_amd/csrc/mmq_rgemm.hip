@@ -84,6 +84,13 @@ constexpr int kSpol = 16; // split-K partial stores write-through (sc1)
 //         Q4_K's 80-B stride (20 dwords): the 16 rows of a fragment read start on banks 20r mod 64
 //         = the 16 multiples of 4, the 8-byte hmask / qs reads of a lane pair and the 16-byte tail
 //         read cover the 4 banks from there -- conflict-free, no padding (streaming GEMM only)
+//   Q2_K  5 pieces: the 16 scale bytes, qs bytes 16+32h..+31, super-block bytes 68..83 (d at image
+//         byte 60, dmin at 62; the block's last 16 bytes), and the scale bytes once more as padding.
+//         The four pieces that carry the half would make a 64-B stride (16 dwords): the 16 rows of a
+//         fragment read would start on four distinct banks only (4-way conflicts).  The fifth,
+//         in-block piece gives Q4_K's conflict-free 80-B stride instead of an XOR placement of the
+//         four (hpos_swz): 25% more weight DMA instructions, no address arithmetic in the reads
+//         (the 64-B image was not built; streaming GEMM only)
 //   Q6_K  8 pieces: ql 64h.. (4), qh 128+32h.. (2), bytes 192..207 (scales), 194..209 (d at image
 //         byte 126); a 128-B stride is 2 bank sets, so row r's pieces are XOR-permuted by r & 7
 //         (hpos_swz).  (Until round 5 a ninth padding piece made the stride 144 B instead; the 8
@@ -93,6 +100,7 @@ template <> struct HImg<Q8_0> { static constexpr int NPH = 9; };
 template <> struct HImg<Q4_K> { static constexpr int NPH = 5; };
 template <> struct HImg<Q5_K> { static constexpr int NPH = 7; };
 template <> struct HImg<Q3_K> { static constexpr int NPH = 5; };
+template <> struct HImg<Q2_K> { static constexpr int NPH = 5; };
 #ifndef GQ_Q6_NPH
 #define GQ_Q6_NPH 8 // (-DGQ_Q6_NPH=9: the padded image, A/B builds)
 #endif
@@ -109,6 +117,7 @@ template <int F> __device__ __forceinline__ uint32_t hsrc(int h, int pc)
     if constexpr (F == Q4_K) return pc == 0 ? 0u : 16u + 64u * h + 16u * (pc - 1);
     if constexpr (F == Q5_K) return pc < 3 ? 16u * pc : 48u + 64u * h + 16u * (pc - 3);
     if constexpr (F == Q3_K) return pc < 2 ? 16u * pc : (pc < 4 ? 32u + 32u * h + 16u * (pc - 2) : 94u);
+    if constexpr (F == Q2_K) return pc == 0 || pc == 4 ? 0u : (pc < 3 ? 16u + 32u * h + 16u * (pc - 1) : 68u);
     return pc < 4 ? 64u * h + 16u * pc : (pc < 6 ? 128u + 32u * h + 16u * (pc - 4) : (pc == 6 ? 192u : 194u));
 }
 
@@ -177,6 +186,7 @@ template <int F> __device__ __forceinline__ void half_frags(const uint8_t *img, 
     else if constexpr (F == Q4_K) q4k_frags(img, img + 16 + 32 * (u & 1), g, u, frag);
     else if constexpr (F == Q5_K) q5k_frags(img, img + 16, img + 48 + 32 * (u & 1), g, u, frag);
     else if constexpr (F == Q3_K) q3k_frags(img, g, u, frag);
+    else if constexpr (F == Q2_K) q2k_frags(img, g, u, frag);
     else if constexpr (HImg<F>::NPH == 8) q6k_half_frags_swz(img, g, h, u & 1, hpos_swz<F>(r), frag);
     else q6k_half_frags(img, g, h, u & 1, frag);
 }
@@ -1025,12 +1035,14 @@ template <int NB> constexpr int max_slds()
     constexpr int a = SCfg<Q8_0, NB>::LDS, b = sgemm_lds<Q4_K, NB>(), c = SCfg<Q6_K, NB>::LDS;
     static_assert(SCfg<Q5_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q5_K within the others' LDS");
     static_assert(SCfg<Q3_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q3_K within the others' LDS");
+    static_assert(SCfg<Q2_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q2_K within the others' LDS");
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
 // Q3 = 1: the launch holds a Q3_K part.  A kernel of its own: the Q3_K body beside the others
 // raised sgemm_grouped_kernel<8>'s registers (185 -> 195), so the other formats' launches keep
-// the kernel they had.
+// the kernel they had.  Q3 = 2: the launch holds a Q2_K part -- a third kernel for the same
+// reason, with Q3_K's body too (a Q2_K file's layers hold both).
 template <int NB, int Q3 = 0>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a);
 template <int NB, int Q3 = 0> int grouped_occ()
@@ -1049,6 +1061,11 @@ __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
                 sgemm_body<Q3_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
                 return;
             }
+        if constexpr (Q3 == 2)
+            if (q.fmt == Q2_K) {
+                sgemm_body<Q2_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
+                return;
+            }
         switch (q.fmt) {
         case Q8_0: sgemm_body<Q8_0, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
         case Q4_K:
@@ -1062,7 +1079,7 @@ __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
             return;
         case Q6_K: sgemm_body<Q6_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
         case Q5_K: sgemm_body<Q5_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
-        default: return; // (plan_sgemm_grouped admits the five formats only; Q3_K: above)
+        default: return; // (plan_sgemm_grouped admits the six formats only; Q3_K, Q2_K: above)
         }
     };
     if (!a.streamk) { // tile-granular splits: workgroup = (part, tile, split)
@@ -1309,7 +1326,7 @@ int rgemm_per_cu(int fmt, int nb)
     case Q8_0: GQ_RPC(Q8_0)
     case Q4_K: GQ_RPC(Q4_K)
     case Q6_K: GQ_RPC(Q6_K)
-    default: return 0; // (no resident form: Q5_K, Q3_K)
+    default: return 0; // (no resident form: Q5_K, Q3_K, Q2_K)
     }
 #undef GQ_RPC
 }
@@ -1379,6 +1396,7 @@ hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *
     case Q6_K: GQ_SG_NB(Q6_K)
     case Q5_K: GQ_SG_NB(Q5_K)
     case Q3_K: GQ_SG_NB(Q3_K)
+    case Q2_K: GQ_SG_NB(Q2_K)
     default: return hipErrorInvalidValue;
     }
 #undef GQ_SG_NB
@@ -1422,6 +1440,7 @@ hipError_t launch_sgemm_id(int fmt, const uint8_t *A, const uint16_t *X, uint16_
     case Q6_K: GQ_SID_NB(Q6_K)
     case Q5_K: GQ_SID_NB(Q5_K)
     case Q3_K: GQ_SID_NB(Q3_K)
+    case Q2_K: GQ_SID_NB(Q2_K)
     default: return hipErrorInvalidValue;
     }
 #undef GQ_SID_NB
@@ -1436,7 +1455,8 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
     int64_t units = 0, Lmax = 1;
     for (int i = 0; i < n; ++i) {
         if (items[i].M < 1 || items[i].K < 256 || items[i].K % 256 != 0) return g;
-        if (items[i].fmt != Q8_0 && items[i].fmt != Q4_K && items[i].fmt != Q6_K && items[i].fmt != Q5_K && items[i].fmt != Q3_K)
+        if (items[i].fmt != Q8_0 && items[i].fmt != Q4_K && items[i].fmt != Q6_K && items[i].fmt != Q5_K && items[i].fmt != Q3_K &&
+            items[i].fmt != Q2_K)
             return g;
         g.tiles_m[i] = (int)((items[i].M + RBM - 1) / RBM);
         const int64_t t = (int64_t)g.tiles_m[i] * tn, nsb = items[i].K / 256;
@@ -1468,7 +1488,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
         // (profiles/r05/sgemm_grouped_cost_ab.txt; -55, the K-chunked stream's best, 74.6 / 76.1 / 99.2)
         int64_t ctot = 0;
         for (int i = 0; i < n; ++i) {
-            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : (items[i].fmt == Q5_K ? 176 : (items[i].fmt == Q3_K ? 110 : 210)));
+            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : (items[i].fmt == Q5_K ? 176 : (items[i].fmt == Q3_K ? 110 : (items[i].fmt == Q2_K ? 84 : 210))));
             g.cstart[i] = (int)ctot;
             ctot += (int64_t)g.tiles_m[i] * tn * (items[i].K / 256) * g.cost[i];
         }
@@ -1553,11 +1573,15 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     a.spol = kSpol;
     a.full = tuning().sgemm_full > 0;
     a.streamk = r.streamk = g.streamk ? 1 : 0;
-    bool q3 = false;
-    for (int i = 0; i < n; ++i) q3 = q3 || items[i].fmt == Q3_K;
+    bool q3 = false, q2 = false;
+    for (int i = 0; i < n; ++i) {
+        q3 = q3 || items[i].fmt == Q3_K;
+        q2 = q2 || items[i].fmt == Q2_K;
+    }
     static const int occ[4] = {grouped_occ<1>(), grouped_occ<2>(), grouped_occ<4>(), grouped_occ<8>()};
     static const int occ3[4] = {grouped_occ<1, 1>(), grouped_occ<2, 1>(), grouped_occ<4, 1>(), grouped_occ<8, 1>()};
-    const int oc = (q3 ? occ3 : occ)[g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3))];
+    static const int occ2[4] = {grouped_occ<1, 2>(), grouped_occ<2, 2>(), grouped_occ<4, 2>(), grouped_occ<8, 2>()};
+    const int oc = (q2 ? occ2 : (q3 ? occ3 : occ))[g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3))];
     a.ilc = g.streamk && tuning().rgemm_ilc != 0 && g.blocks <= num_cus() * oc ? 1 : 0;
     a.U = r.U = g.U;
     a.W = r.W = g.blocks;
@@ -1576,7 +1600,7 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
             rb += g.tiles_m[i] * g.tiles_n * bpt;
         }
     }
-#define GQ_SGG(NB_)                                                                                                       case NB_:                                                                                                                 if (q3) sgemm_grouped_kernel<NB_, 1><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                             else sgemm_grouped_kernel<NB_><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                                        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                                    if (r.n > 0) reduce_grouped_kernel<NB_><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);                                   return hipGetLastError();
+#define GQ_SGG(NB_)                                                                                                       case NB_:                                                                                                                 if (q2) sgemm_grouped_kernel<NB_, 2><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                             else if (q3) sgemm_grouped_kernel<NB_, 1><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                             else sgemm_grouped_kernel<NB_><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                                        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                                    if (r.n > 0) reduce_grouped_kernel<NB_><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);                                   return hipGetLastError();
     switch (g.nb) {
         GQ_SGG(1) GQ_SGG(2) GQ_SGG(4) GQ_SGG(8)
     default: return hipErrorInvalidValue;
@@ -1599,7 +1623,7 @@ hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, in
     case Q8_0: GQ_RG_AQ(Q8_0)
     case Q4_K: GQ_RG_AQ(Q4_K)
     case Q6_K: GQ_RG_AQ(Q6_K)
-    default: return hipErrorInvalidValue; // (no resident form: Q5_K, Q3_K)
+    default: return hipErrorInvalidValue; // (no resident form: Q5_K, Q3_K, Q2_K)
     }
 #undef GQ_RG_AQ
 }

@@ -12,6 +12,12 @@
 //   Q5_K: Q4_K's term over codes 0..31 (no reference counterpart)
 //   Q6_K: term = dB*((d*sc_lo)*dot_lo + (d*sc_hi)*dot_hi) in fp32
 //   Q3_K: Q6_K's term over codes -4..3 and 6-bit scales -32..31 (no reference counterpart)
+//   Q2_K (no reference counterpart), per q8_1 block, every operation one fp32 rounding, in this order:
+//         a_lo = d*sc_lo, a_hi = d*sc_hi, b_lo = dmin*m_lo, b_hi = dmin*m_hi   (exact)
+//         p  = a_lo*float(i_lo) + a_hi*float(i_hi)          (two products, then their sum)
+//         s  = b_lo*float(sig_lo) + b_hi*float(sig_hi)      (two products, then their sum)
+//         term = dB*p - dB*s                                (two products, then their difference)
+//         with i = sum q*qB and sig = sum qB over the block's 16-element halves, exact int32
 //   C = fp16(float(C) + float(fp16(term)))
 // (build with -ffp-contract=off: no fused multiply-adds).
 //
@@ -61,6 +67,7 @@ struct Row {
     std::vector<int8_t> q;
     std::vector<float> c0, c1; // Q8_0: dA (fp16 bits in c0 as float); Q4_K: d*sc, dmin*m; Q6_K: d*sc_lo, d*sc_hi
     std::vector<uint16_t> h;   // Q8_0: dA fp16 bits
+    std::vector<float> m0, m1; // Q2_K: dmin*m_lo, dmin*m_hi
 };
 
 void unpack_q8_0(const uint8_t *row, int64_t K, Row &r)
@@ -170,6 +177,32 @@ void unpack_q3_k(const uint8_t *row, int64_t K, Row &r)
     }
 }
 
+// Q2_K: d*sc per 16 elements in c0 / c1 (Q6_K's row form), dmin*m of the same in m0 / m1; codes 0..3
+void unpack_q2_k(const uint8_t *row, int64_t K, Row &r)
+{
+    const auto &T = half_table();
+    for (int64_t sb = 0; sb < K / 256; ++sb) {
+        const uint8_t *b = row + 84 * sb;
+        const uint8_t *sc = b, *qs = b + 16;
+        const float d = T.v[ld16(b + 80)], dmin = T.v[ld16(b + 82)];
+        for (int s = 0; s < 16; ++s) {
+            const float v = d * (float)(sc[s] & 15), mn = dmin * (float)(sc[s] >> 4);
+            if (s & 1) {
+                r.c1[8 * sb + s / 2] = v;
+                r.m1[8 * sb + s / 2] = mn;
+            } else {
+                r.c0[8 * sb + s / 2] = v;
+                r.m0[8 * sb + s / 2] = mn;
+            }
+        }
+        int8_t *dst = &r.q[256 * sb];
+        for (int e = 0; e < 256; ++e) {
+            const int h = e / 128, j = (e % 128) / 32, l = e % 32;
+            dst[e] = (int8_t)((qs[32 * h + l] >> (2 * j)) & 3);
+        }
+    }
+}
+
 // Token n's q8_1 row: codes and the fp16 d / s of each 32-block.
 struct Act {
     std::vector<int8_t> q;
@@ -272,17 +305,59 @@ void rows_q6_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N
     }
 }
 
+inline int32_t sum32(const int8_t *a, int n)
+{
+    int32_t s = 0;
+    for (int i = 0; i < n; ++i) s += (int32_t)a[i];
+    return s;
+}
+
+// Q2_K rows: the term of the header comment and the others' fp16 running sum in block order
+void rows_q2_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N, int64_t K, uint16_t *C)
+{
+    const auto &T = half_table();
+    const int64_t nb = K / 32, row_bytes = (K / 256) * 84;
+    Row r;
+    r.q.resize((size_t)K);
+    r.c0.resize((size_t)nb);
+    r.c1.resize((size_t)nb);
+    r.m0.resize((size_t)nb);
+    r.m1.resize((size_t)nb);
+    // the activations' code sums per 16-element half: once per call's row range, not per weight row
+    std::vector<int32_t> sg((size_t)(N * nb * 2));
+    for (int64_t i = 0; i < N * nb * 2; ++i) sg[i] = sum32(&x.q[16 * i], 16);
+    for (int64_t m = m0; m < m1; ++m) {
+        unpack_q2_k(A + m * row_bytes, K, r);
+        for (int64_t n = 0; n < N; ++n) {
+            const int8_t *xq = &x.q[n * K];
+            const uint16_t *xd = &x.d[n * nb];
+            const int32_t *xg = &sg[n * nb * 2];
+            uint16_t c = 0;
+            for (int64_t j = 0; j < nb; ++j) {
+                const int32_t lo = dot32(&r.q[32 * j], xq + 32 * j, 16);
+                const int32_t hi = dot32(&r.q[32 * j + 16], xq + 32 * j + 16, 16);
+                const float dB = T.v[xd[j]];
+                const float p = r.c0[j] * (float)lo + r.c1[j] * (float)hi;
+                const float s = r.m0[j] * (float)xg[2 * j] + r.m1[j] * (float)xg[2 * j + 1];
+                const float t = dB * p - dB * s;
+                c = f2h(T.v[c] + T.v[f2h(t)]);
+            }
+            C[m * N + n] = c;
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
 
 // C (M, N) fp16 bits = the reference CPU MMQ of packed weights A (type 0 Q8_0, 1 Q4_K,
-// 2 Q6_K, 3 Q5_K, 4 Q3_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
+// 2 Q6_K, 3 Q5_K, 4 Q3_K, 5 Q2_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
 // Returns 0, or -1 for an unknown type / K not a whole number of blocks.
 int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int64_t K, uint16_t *C, int threads)
 {
     const int qk = type == 0 ? 32 : 256;
-    if (type < 0 || type > 4 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
+    if (type < 0 || type > 5 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
     if (M == 0 || N == 0) return 0;
     half_table();
     const Act x = unpack_act((const uint8_t *)B, N, K);
@@ -291,6 +366,7 @@ int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int
         else if (type == 1) rows_q4_k<false>((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 3) rows_q4_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 4) rows_q6_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);
+        else if (type == 5) rows_q2_k((const uint8_t *)A, x, m0, m1, N, K, C);
         else rows_q6_k<false>((const uint8_t *)A, x, m0, m1, N, K, C);
     };
     int64_t nt = threads > 0 ? threads : (int64_t)std::max(1u, std::thread::hardware_concurrency());

@@ -81,6 +81,14 @@ void gq_quantize_q3_k(const float *x, void *y, int64_t n)
     });
 }
 
+// x: n fp32 values (n % 256 == 0), y: n/256 * 84 bytes (Q2_K: include/gguf_quant.h).
+void gq_quantize_q2_k(const float *x, void *y, int64_t n)
+{
+    parallel_blocks(n / QK, [&](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) q2k_block(x + b * QK, (uint8_t *)y + b * 84);
+    });
+}
+
 // x: n fp32 values (n % 256 == 0), y: n/256 * 210 bytes.
 void gq_quantize_q6_k(const float *x, void *y, int64_t n)
 {
@@ -186,6 +194,22 @@ void gq_dequantize_q3_k(const void *y, float *out, int64_t nblocks)
             const int lo4 = s < 8 ? sc[s] & 15 : sc[s - 8] >> 4;
             const int hi2 = (sc[8 + s % 4] >> (2 * (s / 4))) & 3;
             out[256 * b + e] = (d * (float)((lo4 | (hi2 << 4)) - 32)) * (float)q;
+        }
+    }
+}
+
+// (d*sc_{e/16})*q - (dmin*m_{e/16}) in fp32: both products are exact (an 11-bit significand times
+// at most 4 + 2 bits), so the weight is the difference rounded once
+void gq_dequantize_q2_k(const void *y, float *out, int64_t nblocks)
+{
+    const uint8_t *p = (const uint8_t *)y;
+    for (int64_t b = 0; b < nblocks; ++b, p += 84) {
+        const uint8_t *sc = p, *qs = p + 16;
+        const float d = h2f(get16(p + 80)), dmin = h2f(get16(p + 82));
+        for (int e = 0; e < 256; ++e) {
+            const int h = e / 128, j = (e % 128) / 32, l = e % 32, s = e / 16;
+            const int q = (qs[32 * h + l] >> (2 * j)) & 3;
+            out[256 * b + e] = (d * (float)(sc[s] & 15)) * (float)q - dmin * (float)(sc[s] >> 4);
         }
     }
 }

@@ -9,6 +9,7 @@
 //   q6k_block  <- (GGML) quantize_row_q6_K_ref / make_qx_quants, q6_k_ref.c:153-340
 //   q5k_block  (no reference; host only) q4k_block's search with 31 levels, Q5_K packing
 //   q3k_block  (no reference; host only) q6k_block's search over codes -4..3, Q3_K packing
+//   q2k_block  (no reference; host only) q4k_block's scale / min fit per 16 elements over codes 0..3, Q2_K packing
 //   q8_block   <- utils/quantize/q8_0.py:4-49 (Q8_0), utils/quantize/q8_1.py:18-70 (Q8_1)
 #pragma once
 #include <algorithm>
@@ -56,11 +57,11 @@ GQ_QHD inline uint16_t get16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] 
 // ---------------- Q4_K ----------------
 // Weighted fit of x ~ scale * L + min over L in [0, nmax] (GGML make_qkx2_quants with
 // rmin=-1, rdelta=0.1, nstep=20, squared error).  Returns scale, writes -min to *neg_min.
-// NMAX: the largest code (15: Q4_K, 31: Q5_K).
-template <int NMAX = 15>
+// NMAX: the largest code (15: Q4_K, 31: Q5_K, 3: Q2_K).  N: elements per sub-block (Q2_K: 16).
+template <int NMAX = 15, int N = 32>
 GQ_QHD inline float fit_scale_min(const float *x, const float *w, uint8_t *L, uint8_t *Ltmp, float *neg_min)
 {
-    constexpr int n = 32, nmax = NMAX, nstep = 20;
+    constexpr int n = N, nmax = NMAX, nstep = 20;
     constexpr float rmin = -1.f, rdelta = 0.1f;
     float lo = x[0], hi = x[0];
     float sw = w[0];
@@ -396,6 +397,50 @@ GQ_QHD inline void q3k_block(const float *x, uint8_t *blk)
         const int h = e / 128, j = (e % 128) / 32, l = e % 32, c = L[e];
         qs[32 * h + l] |= (uint8_t)((c & 3) << (2 * j));
         hm[l] |= (uint8_t)((c >> 2) << (4 * h + j));
+    }
+}
+
+// ---------------- Q2_K ----------------
+// Per 16 elements a scale and a non-negative min over codes 0..3 (fit_scale_min<3, 16>, plain
+// squared error: all weights 1); the sixteen scales and the sixteen mins quantized to 4 bits against
+// the largest of each (d = max scale / 15, dmin = max min / 15); then the codes re-fitted to the
+// quantized scales and mins.  Packing: include/gguf_mmq.h.
+GQ_QHD inline void q2k_block(const float *x, uint8_t *blk)
+{
+    uint8_t L[QK], Ltmp[16];
+    float w[16], sub_scale[16], sub_min[16];
+    float max_scale = 0, max_min = 0;
+    for (int l = 0; l < 16; ++l) w[l] = 1.f;
+    for (int j = 0; j < 16; ++j) {
+        sub_scale[j] = fit_scale_min<3, 16>(x + 16 * j, w, L + 16 * j, Ltmp, &sub_min[j]);
+        if (sub_scale[j] > max_scale) max_scale = sub_scale[j];
+        if (sub_min[j] > max_min) max_min = sub_min[j];
+    }
+    const float inv_s = max_scale > 0 ? 15.f / max_scale : 0.f;
+    const float inv_m = max_min > 0 ? 15.f / max_min : 0.f;
+    const uint16_t dh = f2h(max_scale / 15.f), mh = f2h(max_min / 15.f);
+    __builtin_memset(blk, 0, 84);
+    put16(blk + 80, dh);
+    put16(blk + 82, mh);
+    uint8_t *scales = blk, *qs = blk + 16;
+    for (int j = 0; j < 16; ++j) {
+        const int ls = std::max(0, std::min(15, round_magic(inv_s * sub_scale[j])));
+        const int lm = std::max(0, std::min(15, round_magic(inv_m * sub_min[j])));
+        scales[j] = (uint8_t)(ls | (lm << 4));
+        const float d = h2f(dh) * ls;
+        if (!d) { // (a zero scale: the codes carry nothing, the min alone stands for the sub-block)
+            for (int i = 0; i < 16; ++i) L[16 * j + i] = 0;
+            continue;
+        }
+        const float dm = h2f(mh) * lm;
+        for (int i = 0; i < 16; ++i) {
+            int l = round_magic((x[16 * j + i] + dm) / d);
+            L[16 * j + i] = (uint8_t)std::max(0, std::min(3, l));
+        }
+    }
+    for (int e = 0; e < QK; ++e) {
+        const int h = e / 128, j = (e % 128) / 32, l = e % 32;
+        qs[32 * h + l] |= (uint8_t)(L[e] << (2 * j));
     }
 }
 

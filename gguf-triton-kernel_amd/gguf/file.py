@@ -20,7 +20,7 @@ import numpy as np
 
 GGUF_MAGIC = b"GGUF"
 # ggml type id -> (name, block elements, block bytes)
-GGML_TYPES = {0: ("f32", 1, 4), 1: ("f16", 1, 2), 8: ("q8_0", 32, 34), 11: ("q3_k", 256, 110),
+GGML_TYPES = {0: ("f32", 1, 4), 1: ("f16", 1, 2), 8: ("q8_0", 32, 34), 10: ("q2_k", 256, 84), 11: ("q3_k", 256, 110),
               12: ("q4_k", 256, 144), 13: ("q5_k", 256, 176), 14: ("q6_k", 256, 210)}
 TYPE_IDS = {v[0]: k for k, v in GGML_TYPES.items()}
 
@@ -33,7 +33,7 @@ _SCALAR = {_U8: "<B", _I8: "<b", _U16: "<H", _I16: "<h", _U32: "<I", _I32: "<i",
 @dataclass
 class GGUFTensor:
     name: str
-    type_name: str   # "q3_k", "q4_k", "q5_k", "q6_k", "q8_0", "f16", "f32"
+    type_name: str   # "q2_k", "q3_k", "q4_k", "q5_k", "q6_k", "q8_0", "f16", "f32"
     dims: tuple      # GGUF order: innermost (K) first
     offset: int      # from the start of the data section
     data: np.ndarray  # raw bytes (uint8 memmap)

@@ -1,4 +1,4 @@
-"""The Q4_K_M (and Q5_K_M, Q3_K_M) layer-type mix of a Llama block (BASELINE.json configs[4]).
+"""The Q4_K_M (and Q5_K_M, Q3_K_M, Q2_K) layer-type mix of a Llama block (BASELINE.json configs[4]).
 
 llama.cpp's Q4_K_M recipe (not in the reference): every weight Q4_K except attn_v and
 ffn_down, which are Q6_K on a subset of layers -- the first eighth, the last eighth and every
@@ -42,4 +42,19 @@ def q3_k_m_layer_types(layer: int, n_layers: int = 32):
         if name == "ffn_down":
             return "q5_k" if layer < n_layers // 16 else "q4_k"
         return "q3_k"
+    return {name: one(name) for name in LLAMA_LAYER_SHAPES}
+
+
+def q2_k_layer_types(layer: int, n_layers: int = 32, n_gqa: int = 1):
+    """{projection: gguf type} of layer `layer` under llama.cpp's Q2_K file type.
+
+    llama.cpp's rule for Llama models, written here from memory (nothing here can check it against
+    llama.cpp): attn_v q3_k, or q4_k when the model groups its query heads (n_gqa >= 4);
+    attn_output q3_k; ffn_down q3_k; everything else q2_k.  The rule does not depend on the layer."""
+    def one(name):
+        if name == "attn_v":
+            return "q4_k" if n_gqa >= 4 else "q3_k"
+        if name in ("attn_output", "ffn_down"):
+            return "q3_k"
+        return "q2_k"
     return {name: one(name) for name in LLAMA_LAYER_SHAPES}

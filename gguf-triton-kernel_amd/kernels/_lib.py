@@ -15,12 +15,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(os.path.dirname(_HERE), "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgguf_mmq.so")
 
-GQ_Q8_0, GQ_Q4_K, GQ_Q6_K, GQ_Q5_K, GQ_Q3_K = 0, 1, 2, 3, 4
+GQ_Q8_0, GQ_Q4_K, GQ_Q6_K, GQ_Q5_K, GQ_Q3_K, GQ_Q2_K = 0, 1, 2, 3, 4, 5
 GQ_ACT_Q8_1, GQ_ACT_FP8_E4M3 = 0, 1
 ACTS = {"q8_1": GQ_ACT_Q8_1, "fp8": GQ_ACT_FP8_E4M3}
-TYPES = {"q8_0": GQ_Q8_0, "q4_k": GQ_Q4_K, "q6_k": GQ_Q6_K, "q5_k": GQ_Q5_K, "q3_k": GQ_Q3_K}
-BLOCK_ELEMS = {GQ_Q8_0: 32, GQ_Q4_K: 256, GQ_Q6_K: 256, GQ_Q5_K: 256, GQ_Q3_K: 256}
-BLOCK_BYTES = {GQ_Q8_0: 34, GQ_Q4_K: 144, GQ_Q6_K: 210, GQ_Q5_K: 176, GQ_Q3_K: 110}
+TYPES = {"q8_0": GQ_Q8_0, "q4_k": GQ_Q4_K, "q6_k": GQ_Q6_K, "q5_k": GQ_Q5_K, "q3_k": GQ_Q3_K,
+         "q2_k": GQ_Q2_K}
+BLOCK_ELEMS = {GQ_Q8_0: 32, GQ_Q4_K: 256, GQ_Q6_K: 256, GQ_Q5_K: 256, GQ_Q3_K: 256, GQ_Q2_K: 256}
+BLOCK_BYTES = {GQ_Q8_0: 34, GQ_Q4_K: 144, GQ_Q6_K: 210, GQ_Q5_K: 176, GQ_Q3_K: 110, GQ_Q2_K: 84}
 
 # symbol -> (argtypes, restype); mirrors include/gguf_mmq.h
 _P, _I64, _I, _SZ = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t

@@ -13,7 +13,7 @@ _lib = None
 _P, _I64 = ctypes.c_void_p, ctypes.c_int64
 
 BLOCK = {"q8_0": (32, 34), "q8_1": (32, 36), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176),
-         "q3_k": (256, 110)}
+         "q3_k": (256, 110), "q2_k": (256, 84)}
 
 
 def lib():
@@ -34,7 +34,7 @@ def lib():
 def quantize(fmt: str, x: torch.Tensor) -> torch.Tensor:
     """Host quantization of any-shape x (numel % QK == 0) -> flat int8 CPU tensor."""
     qk, nbytes = BLOCK[fmt]
-    if fmt in ("q4_k", "q6_k", "q5_k", "q3_k"):
+    if fmt in ("q4_k", "q6_k", "q5_k", "q3_k", "q2_k"):
         arr = np.ascontiguousarray(x.detach().cpu().to(torch.float32).numpy().reshape(-1))
     else:
         arr = np.ascontiguousarray(x.detach().cpu().to(torch.float16).numpy().reshape(-1)).view(np.uint16)

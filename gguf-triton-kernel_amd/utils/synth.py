@@ -2,14 +2,16 @@
 
 Random bytes are valid blocks for every format except where a byte pair is an fp16 scale,
 so those fields are overwritten with fp16(U(0.5, 1.5) * 2^-7); Q6_K's
-int8 sub-block scales and Q3_K's 6-bit ones stay uniformly random (including negative ones).  The kernels have
+int8 sub-block scales and Q3_K's 6-bit ones stay uniformly random (including negative ones), as do
+Q2_K's 4-bit scales and mins (d at bytes 80..81, dmin at 82..83).  The kernels have
 no data-dependent control flow, so timings do not depend on the values.
 """
 from __future__ import annotations
 
 import numpy as np
 
-BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176), "q3_k": (256, 110)}
+BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176), "q3_k": (256, 110),
+         "q2_k": (256, 84)}
 
 
 def _scales(rng, n):
@@ -35,6 +37,10 @@ def random_blocks(fmt: str, M: int, K: int, seed: int = 0) -> np.ndarray:
     elif fmt == "q3_k":
         d = _scales(rng, nb)
         u16[:, 108], u16[:, 109] = d & 0xFF, d >> 8
+    elif fmt == "q2_k":
+        d, dm = _scales(rng, nb), _scales(rng, nb)
+        u16[:, 80], u16[:, 81] = d & 0xFF, d >> 8
+        u16[:, 82], u16[:, 83] = dm & 0xFF, dm >> 8
     else:
         d = _scales(rng, nb)
         u16[:, 208], u16[:, 209] = d & 0xFF, d >> 8

@@ -51,7 +51,19 @@ extern "C" {
  * answer GQ_EUNSUPPORTED and launch nothing; gq_mmq_id and gq_mmq_id_sorted take it under their
  * limits.  gq_version() did not change with it: detect it by gq_block_bytes(GQ_Q3_K) == 110
  * (a library without it answers 210). */
-typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3, GQ_Q3_K = 4 } gq_type;
+/* GQ_Q2_K (GGML type 10, block_q2_K; the reference has none): 256 weights in 84 bytes, little
+ * endian, rows of K/256 blocks without padding (84 = 4*21: blocks and fields are 4-byte aligned) --
+ *   [0:16] scales[16] | [16:80] qs[64] | [80:82] d fp16 | [82:84] dmin fp16
+ * element e, h = e / 128, j = (e % 128) / 32, l = e % 32, s = e / 16:
+ *   q  = (qs[32*h + l] >> 2*j) & 3                                                    (0 .. 3)
+ *   sc = scales[s] & 15,  m = scales[s] >> 4                                          (0 .. 15)
+ *   w  = d*sc*q - dmin*m   (d*sc*q and dmin*m are exact in fp32: one rounding);
+ * against q8_1 activations, per 16 elements, dB*(d*sc*sum(q*qB) - dmin*m*sum(qB)).
+ * As GQ_Q5_K and GQ_Q3_K: q8_1 activations only, gq_quantize_weights and gq_mmq_grouped[_ex] at
+ * 5..32 tokens answer GQ_EUNSUPPORTED and launch nothing; gq_mmq_id and gq_mmq_id_sorted take it
+ * under their limits.  gq_version() did not change with it: detect it by
+ * gq_block_bytes(GQ_Q2_K) == 84 (a library without it answers 210). */
+typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3, GQ_Q3_K = 4, GQ_Q2_K = 5 } gq_type;
 
 /* How the activations are quantized before the matmul.
  *   GQ_ACT_Q8_1      the reference's semantics: q8_1 (int8 per 32 elements, utils/quantize/q8_1.py).
@@ -70,7 +82,7 @@ enum {
     GQ_EUNSUPPORTED = 3 /* valid but not implemented (unknown type) */
 };
 
-/* Elements per block (32 / 256 / 256 / 256 / 256) and bytes per block (34 / 144 / 210 / 176 / 110). */
+/* Elements per block (32 / 256 / 256 / 256 / 256 / 256) and bytes per block (34 / 144 / 210 / 176 / 110 / 84). */
 int gq_block_elems(gq_type t);
 int gq_block_bytes(gq_type t);
 
@@ -150,6 +162,7 @@ int gq_act_prepare_grouped(gq_act act, const gq_prep_item *items, int n, void *s
  * Dequantize packed `t` weights to fp16: W[m * ldw + k] = w (the reference's block formulas,
  * utils/quantize/{q8_0,q4_k,q6_k}.py dequantize, evaluated in fp32, rounded once to fp16).
  * GQ_Q5_K: (d*sc_j)*q - (dmin*m_j), the formula above, in that order.  GQ_Q3_K: (d*sc)*q.
+ * GQ_Q2_K: (d*sc)*q - (dmin*m), one rounding.
  * M rows of K (a multiple of the block) elements.  gq_mmq uses the same kernel for its
  * library-GEMM path (N >= a few hundred tokens: fp16 W + hipBLASLt).
  */
@@ -174,7 +187,7 @@ int gq_quantize_fp8(const void *X, void *codes, void *scales, int64_t rows, int6
  *   GQ_Q8_0: X = n fp16 values (n % 32 == 0)  -> Y = n/32 blocks of 34 bytes (quantize_to_q8_0)
  *   GQ_Q4_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 144 bytes (quantize_to_q4_k)
  *   GQ_Q6_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 210 bytes (quantize_to_q6_k)
- * GQ_Q5_K, GQ_Q3_K: GQ_EUNSUPPORTED (host only: include/gguf_quant.h gq_quantize_q5_k / _q3_k).
+ * GQ_Q5_K, GQ_Q3_K, GQ_Q2_K: GQ_EUNSUPPORTED (host only: include/gguf_quant.h gq_quantize_q5_k / _q3_k / _q2_k).
  * X is read as flat blocks (a row-major (M, K) matrix gives the packed A of gq_mmq).  One thread
  * per block runs the host producer's exact code; no host sync.
  */

@@ -19,6 +19,13 @@
  *                      sixteen scales to 6 bits against the largest, codes re-fitted (no byte contract)
  *   gq_dequantize_q3_k (d*sc)*q in fp32, in that order (gq_dequantize_q6_k's)
  *   gq_cpu_mmq type 4  Q6_K's terms and fp16 running sum over codes -4..3
+ * and Q2_K (GGML type 10; the layout in include/gguf_mmq.h) --
+ *   gq_quantize_q2_k   per 16 elements a scale and a non-negative min over codes 0..3
+ *                      (gq_quantize_q4_k's fit), the sixteen scales and mins to 4 bits against the
+ *                      largest of each, codes re-fitted (no byte contract)
+ *   gq_dequantize_q2_k (d*sc)*q - (dmin*m) in fp32 (both products exact: one rounding)
+ *   gq_cpu_mmq type 5  per q8_1 block dB*((d*sc_lo)*i_lo + (d*sc_hi)*i_hi)
+ *                      - dB*((dmin*m_lo)*sigma_lo + (dmin*m_hi)*sigma_hi), the fp16 running sum
  */
 #ifndef GGUF_QUANT_H
 #define GGUF_QUANT_H
@@ -36,6 +43,8 @@ void gq_quantize_q6_k(const float *x, void *y, int64_t n);
 void gq_quantize_q5_k(const float *x, void *y, int64_t n);
 /* x: n fp32 (n % 256 == 0) -> y: n/256 blocks of 110 bytes (Q3_K) */
 void gq_quantize_q3_k(const float *x, void *y, int64_t n);
+/* x: n fp32 (n % 256 == 0) -> y: n/256 blocks of 84 bytes (Q2_K) */
+void gq_quantize_q2_k(const float *x, void *y, int64_t n);
 
 /* x: n fp16 bit patterns (n % 32 == 0) -> y: n/32 blocks of 34 (Q8_0) / 36 (Q8_1) bytes */
 void gq_quantize_q8_0(const uint16_t *x, void *y, int64_t n);
@@ -48,9 +57,10 @@ void gq_dequantize_q4_k(const void *y, float *out, int64_t nblocks);
 void gq_dequantize_q6_k(const void *y, float *out, int64_t nblocks);
 void gq_dequantize_q5_k(const void *y, float *out, int64_t nblocks);
 void gq_dequantize_q3_k(const void *y, float *out, int64_t nblocks);
+void gq_dequantize_q2_k(const void *y, float *out, int64_t nblocks);
 
 /* C (M, N) fp16 bits, row-major = the reference CPU MMQ of packed weights A (type 0 Q8_0,
- * 1 Q4_K, 2 Q6_K, 3 Q5_K, 4 Q3_K; M rows of K) and packed q8_1 activations B (N rows of K).  threads <= 0:
+ * 1 Q4_K, 2 Q6_K, 3 Q5_K, 4 Q3_K, 5 Q2_K; M rows of K) and packed q8_1 activations B (N rows of K).  threads <= 0:
  * every hardware thread (the result does not depend on it).  0 = OK, -1 = bad type or K. */
 int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int64_t K, uint16_t *C, int threads);
 
