@@ -27,25 +27,90 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace gq {
 
 enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3, Q3_K = 4, Q2_K = 5 };
 
-template <int F> struct Layout;
-template <> struct Layout<Q8_0> { static constexpr int QK = 32, BYTES = 34; };
-template <> struct Layout<Q4_K> { static constexpr int QK = 256, BYTES = 144; };
-template <> struct Layout<Q6_K> { static constexpr int QK = 256, BYTES = 210; };
-template <> struct Layout<Q5_K> { static constexpr int QK = 256, BYTES = 176; };
-// Q4_K's header and q8_1 arithmetic (6-bit scales and mins, the activation block's s in the min term)
-constexpr bool has_mins(int f) { return f == Q4_K || f == Q5_K; }
-template <> struct Layout<Q3_K> { static constexpr int QK = 256, BYTES = 110; };
-// Q6_K's q8_1 arithmetic (a signed scale per 16 elements, no mins; the codes enter v_dot4 unsigned
-// and the offset -- Q6_K 32, Q3_K 4 -- is taken out with the activations' per-16 code sums)
-// (Q2_K: unsigned codes 0..3 and a min per 16 elements -- the same per-16 code sums carry dmin*m)
-constexpr bool has_sums(int f) { return f == Q6_K || f == Q3_K || f == Q2_K; }
-constexpr int code_offset(int f) { return f == Q3_K ? 4 : 32; }
-// 84 = 4 * 21 bytes: every super-block and every field is 4-byte aligned
-template <> struct Layout<Q2_K> { static constexpr int QK = 256, BYTES = 84; };
+// The cached-chunk caps of the Q3_K / Q2_K decode kernels (FmtInfo below), with their build-time
+// overrides (make variant VFLAGS=... A/B builds).
+constexpr int kQ3Itc1 = 6, kQ3Itc2 = 3; // Q3_K: the most cached chunks at one / two tokens
+// Q2_K: Q3_K's activation registers, but 10 raw registers per unit in flight where Q3_K has 20:
+// 7 cached chunks at one token compile without scratch (236 VGPRs), as do 4 at two (253); two
+// tokens stay at Q3_K's 3, the most the grouped kernel that holds a Q2_K item carries
+#ifndef GQ_Q2_ITC1
+#define GQ_Q2_ITC1 7
+#endif
+#ifndef GQ_Q2_ITC2
+#define GQ_Q2_ITC2 3
+#endif
+constexpr int kQ2Itc1 = GQ_Q2_ITC1, kQ2Itc2 = GQ_Q2_ITC2;
+
+// What the host side and the kernels' template parameters need to know of a block type: one row
+// per Fmt in kFmt[].  A new type is a row here plus its device code ("Adding a block type").
+struct FmtInfo {
+    int qk, bytes; // elements and bytes of one block
+    // Q4_K's header and q8_1 arithmetic (6-bit scales and mins, the activation block's s in the min term)
+    bool has_mins;
+    // Q6_K's q8_1 arithmetic (a signed scale per 16 elements, no mins; the codes enter v_dot4 unsigned
+    // and code_offset -- Q6_K 32, Q3_K 4 -- is taken out with the activations' per-16 code sums)
+    // (Q2_K: unsigned codes 0..3 and a min per 16 elements -- the same per-16 code sums carry dmin*m)
+    bool has_sums;
+    int code_offset;
+    // no fp8 activation form and no resident / skinny / K-chunked / LDS-DMA GEMM: only the q8_1
+    // decode kernels, the GEMV and the streaming GEMM
+    bool q8_1_only;
+    // streaming decode (mmq_decode.hip): the most cached activation chunks a kernel exists for, at
+    // one / two / four tokens with q8_1 activations and at one token with fp8 ones (unused where
+    // q8_1_only), and the 64-weight units of a lane's work item at up to two tokens.
+    // (Q5_K: twice Q4_K's code registers per unit -- 7 cached units at one token spill;
+    // Q3_K: Q5_K's code registers and the code sums besides)
+    int itc[3], fp8_itc, upc2;
+    // the case set a grouped launch holding the type needs, the largest over its items:
+    // stream_decode_grouped_kernel's SET and sgemm_grouped_kernel's
+    int group_set, sgemm_set;
+    constexpr int sb_bytes() const { return 256 / qk * bytes; } // the bytes of 256 weights (Q8_0: 272)
+};
+constexpr FmtInfo kFmt[] = {
+    // qk bytes mins   sums   off  q8_1only  itc at 1, 2, 4 tokens  fp8 upc2 sets
+    {32, 34, false, false, 32, false, {7, 4, 1}, 2, 1, 0, 0},              // Q8_0
+    {256, 144, true, false, 32, false, {7, 4, 1}, 2, 1, 0, 0},             // Q4_K
+    {256, 210, false, true, 32, false, {4, 1, 1}, 1, 2, 0, 0},             // Q6_K
+    {256, 176, true, false, 32, true, {6, 4, 1}, 2, 1, 1, 0},              // Q5_K
+    {256, 110, false, true, 4, true, {kQ3Itc1, kQ3Itc2, 1}, 2, 1, 2, 1},   // Q3_K
+    // 84 = 4 * 21 bytes: every super-block and every field is 4-byte aligned
+    {256, 84, false, true, 32, true, {kQ2Itc1, kQ2Itc2, 1}, 2, 1, 3, 2},   // Q2_K
+};
+constexpr int kNumFmts = (int)(sizeof(kFmt) / sizeof(kFmt[0]));
+constexpr bool known_fmt(int f) { return f >= 0 && f < kNumFmts; }
+// A type outside the table (every caller refuses it by known_fmt first): Q6_K's block -- the C
+// ABI's answer for an unknown type's row size -- with the general caps.
+constexpr FmtInfo kFmtOther = {256, 210, false, true, 32, false, {7, 4, 1}, 2, 1, 0, 0};
+constexpr const FmtInfo &fmt_info(int f) { return known_fmt(f) ? kFmt[f] : kFmtOther; }
+// packed bytes of a K-element row.  Not K / 256 * sb_bytes: a Q8_0 row may be a multiple of 32 only
+constexpr int64_t row_bytes(int f, int64_t K) { return K / fmt_info(f).qk * fmt_info(f).bytes; }
+
+template <int F> struct Layout { static constexpr int QK = kFmt[F].qk, BYTES = kFmt[F].bytes; };
+constexpr bool has_mins(int f) { return fmt_info(f).has_mins; }
+constexpr bool has_sums(int f) { return fmt_info(f).has_sums; }
+constexpr int code_offset(int f) { return fmt_info(f).code_offset; }
+constexpr bool q8_1_only(int f) { return fmt_info(f).q8_1_only; }
+
+// fn(ic<I>{}) for i == I in 0..MAX, which instantiates fn for exactly those; hipErrorInvalidValue
+// for any other i
+template <int V> using ic = std::integral_constant<int, V>;
+template <int MAX, int I = 0, class Fn> hipError_t dispatch_upto(int i, Fn &&fn)
+{
+    if constexpr (I <= MAX) {
+        if (i == I) return fn(ic<I>{});
+        return dispatch_upto<MAX, I + 1>(i, fn);
+    } else {
+        return hipErrorInvalidValue;
+    }
+}
+// fn(ic<F>{}) for the table's type fmt; hipErrorInvalidValue for an unknown one
+template <class Fn> hipError_t dispatch_fmt(int fmt, Fn &&fn) { return dispatch_upto<kNumFmts - 1>(fmt, fn); }
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));

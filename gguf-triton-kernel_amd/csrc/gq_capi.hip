@@ -137,29 +137,24 @@ int num_cus()
 // ---- the planner: host-only; everything the ABI decides about a call is decided here, once ----
 namespace {
 
-// One row per gq_type: block geometry, whether the streaming GEMM is the type's only GEMM kernel
-// (Q5_K, Q3_K and Q2_K: q8_1 activations only, no resident / skinny / K-chunked / LDS-DMA form) and the
-// kind of its device quantizer (launch_quant_blocks; -1: none, gq_quantize_<lname> on the host).
+// One row per gq_type of what is the ABI's own: the type's names and the kind of its device
+// quantizer (launch_quant_blocks; -1: none, gq_quantize_<lname> on the host).  The block geometry
+// and whether the streaming GEMM is the type's only GEMM kernel (q8_1_only) are gguf_blocks.hpp's kFmt.
 struct TypeInfo {
     const char *name, *lname;
-    int elems, bytes;
-    bool sgemm_only;
     int quant_kind;
 };
-constexpr TypeInfo kTypes[] = {{"Q8_0", "q8_0", 32, 34, false, 0},
-                               {"Q4_K", "q4_k", 256, 144, false, 1},
-                               {"Q6_K", "q6_k", 256, 210, false, 2},
-                               {"Q5_K", "q5_k", 256, 176, true, -1},
-                               {"Q3_K", "q3_k", 256, 110, true, -1},
-                               {"Q2_K", "q2_k", 256, 84, true, -1}};
-static_assert(GQ_Q8_0 == 0 && GQ_Q4_K == 1 && GQ_Q6_K == 2 && GQ_Q5_K == 3 && GQ_Q3_K == 4 && GQ_Q2_K == 5,
-              "kTypes is indexed by gq_type");
-bool known_type(int t) { return t >= 0 && t < (int)(sizeof(kTypes) / sizeof(kTypes[0])); }
-// (an unknown type answers with Q6_K's row, as gq_block_bytes always did: callers detect a type by it)
+constexpr TypeInfo kTypes[] = {{"Q8_0", "q8_0", 0},  {"Q4_K", "q4_k", 1},  {"Q6_K", "q6_k", 2},
+                               {"Q5_K", "q5_k", -1}, {"Q3_K", "q3_k", -1}, {"Q2_K", "q2_k", -1}};
+static_assert(GQ_Q8_0 == 0 && GQ_Q4_K == 1 && GQ_Q6_K == 2 && GQ_Q5_K == 3 && GQ_Q3_K == 4 && GQ_Q2_K == 5 &&
+                  sizeof(kTypes) / sizeof(kTypes[0]) == kNumFmts,
+              "kTypes and kFmt are indexed by gq_type");
+bool known_type(int t) { return known_fmt(t); }
+// (an unknown type answers with Q6_K's row, as gq_block_bytes always did: callers detect a type by it;
+// fmt_info does the same for the block)
 const TypeInfo &type_info(int t) { return kTypes[known_type(t) ? t : (int)GQ_Q6_K]; }
 
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-int64_t row_bytes_of(int t, int64_t K) { return (K / type_info(t).elems) * type_info(t).bytes; }
 
 // Decode path up to this many tokens; beyond it the fp16-MFMA GEMM.
 constexpr int64_t kGemvMaxTokens = 4; // 5..8 tokens: the MFMA GEMM (15.9 us at 16 tokens vs 22.3 us decode at 8, Q4_K 4096^2)
@@ -187,7 +182,7 @@ int64_t gemm_max_bytes(const Tuning &u)
 }
 int64_t gemm_rows_per_launch(int t, int64_t M, int64_t K, const Tuning &u)
 {
-    const int64_t r = gemm_max_bytes(u) / row_bytes_of(t, K) / 256 * 256; // whole 256-row tiles
+    const int64_t r = gemm_max_bytes(u) / row_bytes(t, K) / 256 * 256; // whole 256-row tiles
     return r < 256 ? 256 : (r < M ? r : M);
 }
 int64_t gemm_toks_per_launch(int64_t N, int64_t K, const Tuning &u)
@@ -215,7 +210,7 @@ constexpr int64_t kRgemmMinTokens = 5, kRgemmMultiRoundTokens = 32, kRgemmMultiR
 constexpr int64_t kSkinnyMinTokens = 5, kSkinnyMaxTokens = 16, kSkinnyForcedMax = 32;
 bool use_skinny(int t, int form, int64_t N, int act, const Tuning &u)
 {
-    if (form != AF_F16 || u.skinny == 0 || type_info(t).sgemm_only) return false;
+    if (form != AF_F16 || u.skinny == 0 || q8_1_only(t)) return false;
     if (u.skinny == 1) return N <= kSkinnyForcedMax;
     // the fp8 variant has no decode kernel: its 1..4 tokens take the skinny kernel too
     const int64_t lo = act == GQ_ACT_FP8_E4M3 ? 1 : kSkinnyMinTokens;
@@ -236,7 +231,7 @@ bool gemm_knob_pinned(const Tuning &u) { return u.gemm_splits > 0 || u.gemm_rg |
 bool use_rgemm(int t, int form, int64_t M, int64_t N, int64_t K, const Tuning &u, RGemmPlan &p)
 {
     const int rg = u.rgemm;
-    if (type_info(t).sgemm_only) return false; // (no resident form: the streaming GEMM, whatever GQ_RGEMM says)
+    if (q8_1_only(t)) return false; // (no resident form: the streaming GEMM, whatever GQ_RGEMM says)
     if (rg == 0 || form != AF_F16 || use_gemv(N, K) || use_blas(N, K, u) || K % 256 != 0) return false;
     if (gemm_rows_per_launch(t, M, K, u) < M || gemm_toks_per_launch(N, K, u) < N) return false;
     p = plan_rgemm(M, N, K);
@@ -313,16 +308,16 @@ bool use_sgemm(int t, int form, int64_t M, int64_t N, int64_t K, const Tuning &u
     if (form != AF_F16 || use_gemv(N, K) || use_blas(N, K, u) || K % 256 != 0) return false;
     // Q5_K's, Q3_K's and Q2_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
     // knob of the other GEMMs says; rows over the per-launch limit are cut into chunks
-    if (type_info(t).sgemm_only) {
+    if (q8_1_only(t)) {
         // the call's tokens go into every launch (rows alone are cut).  Counted as the other GEMMs
         // count them, in whole 128-token tiles of x~ -- but for a type whose 768 rows weigh less than
         // 128 tokens' x~ at every K (768 * block bytes < 128 * 2 * block elements: Q2_K alone, 252 K
         // against 256 K bytes) that count admits 16 tokens under any limit that cuts its rows at
         // all, so for it the x~ bytes are counted exactly
-        const TypeInfo &ti = type_info(t);
-        const bool toks_fit = 768 * ti.bytes < 256 * ti.elems ? N * 2 * K <= gemm_max_bytes(u)
+        const FmtInfo &ti = fmt_info(t);
+        const bool toks_fit = 768 * ti.bytes < 256 * ti.qk ? N * 2 * K <= gemm_max_bytes(u)
                                                               : gemm_toks_per_launch(N, K, u) >= N;
-        return M > 0 && toks_fit && 256 * row_bytes_of(t, K) < ((int64_t)1 << 31);
+        return M > 0 && toks_fit && 256 * row_bytes(t, K) < ((int64_t)1 << 31);
     }
     if (u.sgemm == 0) return false;
     if (gemm_rows_per_launch(t, M, K, u) < M || gemm_toks_per_launch(N, K, u) < N) return false;
@@ -454,7 +449,6 @@ Plan plan_call(const Call &c, const Tuning &u)
     const int t = c.t, act = c.act;
     const int64_t M = c.M, N = c.N, K = c.K;
     const bool fp8 = act == GQ_ACT_FP8_E4M3, work = M > 0 && N > 0;
-    const TypeInfo &ti = type_info(t);
     Plan p;
     const bool gemv = !fp8 && use_gemv(N, K), blas = use_blas(N, K, u);
     p.form = !fp8 && use_i8(t, N, K, u) ? AF_I8 : AF_F16;
@@ -512,7 +506,7 @@ Plan plan_call(const Call &c, const Tuning &u)
     } else if (sgemm) {
         p.kernel = streamk ? K_SGEMM_STREAMK : K_SGEMM;
         if (!streamk) p.rg = sg;
-    } else if (!ti.sgemm_only) { // (Q5_K / Q3_K / Q2_K: the streaming GEMM or nothing, GQ_EUNSUPPORTED)
+    } else if (!q8_1_only(t)) { // (Q5_K / Q3_K / Q2_K: the streaming GEMM or nothing, GQ_EUNSUPPORTED)
         p.kernel = K_GEMM;
         if (!c.prepared && act == GQ_ACT_Q8_1 && p.form == AF_F16 && p.rows >= M && p.toks >= N) {
             // 16/32-token tiles whose split fits LDS: the GEMM quantizes the activations itself (no
@@ -531,7 +525,7 @@ Plan plan_call(const Call &c, const Tuning &u)
     // stream has its K ranges.  ABI-visible (gguf_mmq.h bumps gq_version when a size grows).
     if (blas) {
         p.partial_bytes = align_up((size_t)M * K * 2) + blas_workspace_bytes();
-    } else if (gemm_tokens && ti.sgemm_only) {
+    } else if (gemm_tokens && q8_1_only(t)) {
         // the streaming GEMM per chunk of p.rows rows (rows are independent): the largest chunk shape's
         size_t b = 0;
         for (int64_t mc : {p.rows, M % p.rows})
@@ -687,7 +681,7 @@ size_t sharded_ws(int t, int64_t M, int64_t N, int64_t K, int world)
 bool sizable(int t, int act, int64_t M, int64_t N, int64_t K)
 {
     if (!gq::known_type(t) || (act != GQ_ACT_Q8_1 && act != GQ_ACT_FP8_E4M3)) return false;
-    return M >= 0 && N > 0 && K > 0 && K % gq::type_info(t).elems == 0;
+    return M >= 0 && N > 0 && K > 0 && K % gq::fmt_info(t).qk == 0;
 }
 
 } // namespace
@@ -703,8 +697,8 @@ int gq_debug_set_tuning(const char *key, long long value)
 }
 void gq_debug_reset_tuning(void) { gq::reset_tuning(); }
 
-int gq_block_elems(gq_type t) { return gq::type_info(t).elems; }
-int gq_block_bytes(gq_type t) { return gq::type_info(t).bytes; }
+int gq_block_elems(gq_type t) { return gq::fmt_info(t).qk; }
+int gq_block_bytes(gq_type t) { return gq::fmt_info(t).bytes; }
 int gq_version(void) { return 105; }
 
 unsigned int gq_debug_sync_timeouts(void) { return gq::ilc_timeouts() + gq::kstream_timeouts(); }
@@ -731,7 +725,7 @@ static int check_common(gq_type t, int64_t M, int64_t N, int64_t K)
     if (!gq::known_type(t)) return fail(GQ_EUNSUPPORTED, "unknown gguf type %d", (int)t);
     if (M < 0 || N < 0 || K < 0)
         return fail(GQ_EINVAL, "negative size M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
-    const int qk = gq::type_info(t).elems;
+    const int qk = gq::fmt_info(t).qk;
     if (K % qk != 0) return fail(GQ_EINVAL, "K=%lld is not a multiple of %d", (long long)K, qk);
     return GQ_OK;
 }
@@ -751,7 +745,7 @@ static int check_mmq_shape(gq_type t, int act, int64_t M, int64_t N, int64_t K)
     int rc = check_common(t, M, N, K);
     if (rc != GQ_OK) return rc;
     if ((rc = check_act(act, K)) != GQ_OK) return rc;
-    if (gq::type_info(t).sgemm_only && act == GQ_ACT_FP8_E4M3)
+    if (gq::q8_1_only(t) && act == GQ_ACT_FP8_E4M3)
         return fail(GQ_EUNSUPPORTED, "%s has no fp8-activation form", gq::type_info(t).name);
     return GQ_OK;
 }
@@ -853,7 +847,7 @@ static int launch_plan(const gq::Call &c, const gq::Plan &p, const void *A_, con
     case gq::K_SGEMM: // row chunks under the per-launch byte limit (Q5_K / Q3_K / Q2_K; the others are never cut)
         for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += p.rows) {
             const int64_t mc = M - m0 < p.rows ? M - m0 : p.rows;
-            e = gq::launch_sgemm(t, A + m0 * gq::row_bytes_of(t, K), w.xdeq, C + m0, w.partials,
+            e = gq::launch_sgemm(t, A + m0 * gq::row_bytes(t, K), w.xdeq, C + m0, w.partials,
                                  mc == M ? p.rg : gq::plan_sgemm(mc, N, K, gq::tuning().sgemm_splits), mc, N, K, ldc, s);
         }
         return hip_rc(e, "sgemm");
@@ -871,7 +865,7 @@ static int launch_plan(const gq::Call &c, const gq::Plan &p, const void *A_, con
     for (int64_t n0 = 0; n0 < N && e == hipSuccess; n0 += p.toks)
         for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += p.rows) {
             const int64_t mc = M - m0 < p.rows ? M - m0 : p.rows, nc = N - n0 < p.toks ? N - n0 : p.toks;
-            const uint8_t *Ac = A + m0 * gq::row_bytes_of(t, K);
+            const uint8_t *Ac = A + m0 * gq::row_bytes(t, K);
             uint16_t *Cc = C + n0 * ldc + m0;
             if (p.kernel == gq::K_SKINNY) {
                 e = gq::launch_skinny(t, Ac, w.xdeq + n0 * K, Cc, gq::plan_skinny(t, mc, nc, K, gq::tuning().skinny_rg, 0),
@@ -1037,10 +1031,11 @@ int gq_quantize_weights(gq_type t, const void *X, void *Y, int64_t n, void *stre
     if (ti.quant_kind < 0)
         return fail(GQ_EUNSUPPORTED, "%s has no device quantizer (gq_quantize_%s on the host)", ti.name, ti.lname);
     if (n < 0) return fail(GQ_EINVAL, "negative size");
-    if (n % ti.elems != 0) return fail(GQ_EINVAL, "n=%lld is not a multiple of %d", (long long)n, ti.elems);
+    const int qk = gq::fmt_info(t).qk;
+    if (n % qk != 0) return fail(GQ_EINVAL, "n=%lld is not a multiple of %d", (long long)n, qk);
     if (n == 0) return GQ_OK;
     if (!X || !Y) return fail(GQ_EINVAL, "null pointer");
-    return hip_rc(gq::launch_quant_blocks(ti.quant_kind, X, Y, n / ti.elems, (hipStream_t)stream), "weight quantizer");
+    return hip_rc(gq::launch_quant_blocks(ti.quant_kind, X, Y, n / qk, (hipStream_t)stream), "weight quantizer");
 }
 
 int gq_quantize_fp8(const void *X, void *codes, void *scales, int64_t rows, int64_t K, int64_t ldx, void *stream)
@@ -1182,7 +1177,7 @@ static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, in
     if (K <= 0 || K % 256 != 0 || E < 1 || E > gq::kMaxSortExperts || M < 1 || N < 1 || S < 1) return none;
     if (N > gq::kMaxSortPairs || S > gq::kMaxSortPairs || N * S > gq::kMaxSortPairs) return none;
     if (N * S * K * 2 >= ((int64_t)1 << 32)) return none;        // (sgemm_body's 32-bit descriptor over x~)
-    const int64_t rb = gq::row_bytes_of(t, K);
+    const int64_t rb = gq::row_bytes(t, K);
     if (M > INT64_MAX / rb || M * rb >= ((int64_t)1 << 31)) return none; // one expert
     return gq::plan_sgemm_id(E, M, N * S, K);
 }

@@ -23,6 +23,7 @@
 // units per row for short rows, several rows per wave pass); it reads the unit's packed bytes
 // and its activation block pair from LDS, dots them with v_dot4_i32_i8, and P-lane xor
 // shuffles reduce the row.
+#include <algorithm>
 #include <cstdlib>
 
 #include "gguf_blocks.hpp"
@@ -69,8 +70,8 @@ constexpr int RING = DW * NS * SLOT;
 constexpr int LDS_CAP = 160 * 1024;
 // units (64 weights) per lane work item: Q6_K lanes take whole super-block halves (up to two
 // tokens: with four, two units' activations at once exceed the register file)
-template <int F, int NT> constexpr int UPC_OF = F == Q6_K && NT <= 2 ? 2 : 1;
-int upc_of(int fmt, int nt) { return fmt == Q6_K && nt <= 2 ? 2 : 1; }
+constexpr int upc_of(int fmt, int nt) { return nt <= 2 ? fmt_info(fmt).upc2 : 1; }
+template <int F, int NT> constexpr int UPC_OF = upc_of(F, NT);
 
 // Q6_K tasks land in the ring as an aligned image: every 210-byte super-block (2-byte aligned
 // in the tensor) becomes 224 bytes -- 13 pieces from its first byte (0..207) and one from byte
@@ -697,41 +698,15 @@ size_t act_lds(int fmt, int nt, int64_t K, bool fp8 = false)
     const int64_t kp = (K + 63) / 64 * 64, nb = K / 32;
     if (fp8) // x~ + quarter sums (2+ tokens: Q4_K's block sums only, gguf_dot.hpp dot_unit_h NS)
         return (size_t)nt * kp * 2 + (nt == 1 ? (size_t)nt * nb * 2 * 4 : (fmt == Q4_K ? (size_t)nt * nb * 4 : 0));
-    // codes + d (+ Q4_K / Q5_K: s; Q6_K / Q3_K / Q2_K: the two 16-element code sums)
-    return (size_t)nt * kp + (size_t)nt * nb * 4 * (fmt == Q8_0 ? 1 : (fmt == Q4_K || fmt == Q5_K ? 2 : 3));
+    // codes + d (+ has_mins: s; has_sums: the two 16-element code sums)
+    return (size_t)nt * kp + (size_t)nt * nb * 4 * (has_sums(fmt) ? 3 : (has_mins(fmt) ? 2 : 1));
 }
 
-// the largest cached-chunk count ITC instantiated for (format, token tile); the fp8 form caches
-// at one token only, at most two units (64 VGPRs of x~ pairs)
-constexpr int kQ3Itc1 = 6, kQ3Itc2 = 3; // Q3_K: the most cached chunks at one / two tokens
-// Q2_K: Q3_K's activation registers, but 10 raw registers per unit in flight where Q3_K has 20:
-// 7 cached chunks at one token compile without scratch (236 VGPRs), as do 4 at two (253); two
-// tokens stay at Q3_K's 3, the most the grouped kernel that holds a Q2_K item carries
-#ifndef GQ_Q2_ITC1
-#define GQ_Q2_ITC1 7
-#endif
-#ifndef GQ_Q2_ITC2
-#define GQ_Q2_ITC2 3
-#endif
-constexpr int kQ2Itc1 = GQ_Q2_ITC1, kQ2Itc2 = GQ_Q2_ITC2;
-static_assert(kQ2Itc1 <= 7 && kQ2Itc2 <= 3, "launch_f / stream_decode_grouped_kernel carry no further Q2_K cases");
-int fp8_itc_max(int fmt, int nt) { return nt == 1 ? (fmt == Q6_K ? 1 : 2) : 0; }
-int itc_max(int fmt, int nt)
-{
-    // (Q5_K: twice Q4_K's code registers per unit -- 7 cached units at one token spill)
-    // (Q3_K: Q5_K's code registers and the code sums besides -- kQ3Itc1 / kQ3Itc2)
-    // (Q2_K: kQ2Itc1 / kQ2Itc2)
-    if (nt == 1) return fmt == Q6_K ? 4 : (fmt == Q5_K ? 6 : (fmt == Q3_K ? kQ3Itc1 : (fmt == Q2_K ? kQ2Itc1 : 7)));
-    if (nt == 2) return fmt == Q6_K ? 1 : (fmt == Q3_K ? kQ3Itc2 : (fmt == Q2_K ? kQ2Itc2 : 4));
-    return 1;
-}
-
-bool known_fmt(int fmt) { return fmt == Q8_0 || fmt == Q4_K || fmt == Q6_K || fmt == Q5_K || fmt == Q3_K || fmt == Q2_K; }
-bool q8_1_only(int fmt) { return fmt == Q5_K || fmt == Q3_K || fmt == Q2_K; } // (no form of the fp8 variant)
-int64_t row_bytes(int fmt, int64_t K)
-{
-    return fmt == Q8_0 ? K / 32 * 34 : K / 256 * (fmt == Q4_K ? 144 : (fmt == Q5_K ? 176 : (fmt == Q3_K ? 110 : (fmt == Q2_K ? 84 : 210))));
-}
+// the largest cached-chunk count ITC instantiated for (format, token tile) -- launch_f and
+// launch_id_f instantiate exactly 0..the cap; the fp8 form caches at one token only, at most two
+// units (64 VGPRs of x~ pairs)
+constexpr int fp8_itc_max(int fmt, int nt) { return nt == 1 ? fmt_info(fmt).fp8_itc : 0; }
+constexpr int itc_max(int fmt, int nt) { return fmt_info(fmt).itc[nt == 1 ? 0 : (nt == 2 ? 1 : 2)]; }
 
 // wgs: the workgroups the matrix gets (0: a launch of its own, the whole chip; a grouped launch
 // splits the chip's workgroups by weight bytes)
@@ -783,7 +758,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
         while ((1 << lp2) < cpr && lp2 < 6) ++lp2;
         g.lp2 = lp2;
     } else {
-        const int64_t unit64 = fmt == Q8_0 ? 64 * 68 : (fmt == Q4_K ? 64 * 36 : (fmt == Q5_K ? 64 * 44 : (fmt == Q3_K ? 64 * 110 / 4 : (fmt == Q2_K ? 64 * 21 : 64 * (img ? kImgSB : 210) / 4))));
+        const int64_t unit64 = 16 * (img ? kImgSB : fmt_info(fmt).sb_bytes()); // 64 units = 16 x 256 weights
         if (cap < unit64) return false; // a 64-unit segment must fit one task (tuning builds with small NI)
         g.G = 1;
         g.segu = (int)(64 * (cap / unit64));
@@ -795,8 +770,8 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
     // units and 1 token (K <= 28672: the 70B ffn_down rows) -- no spills (kernel-resource-usage)
     const int64_t itc = (cpr + (1 << g.lp2) - 1) >> g.lp2, units = itc * (upr / cpr);
     p.itc = ((p.nt <= 2 && units <= (fmt == Q6_K ? 2 : 4)) || (p.nt == 1 && units <= 8)) ? (int)itc : 0;
-    // only the instantiated chunk counts (launch_f, stream_decode_grouped_kernel): one token
-    // 0..7 (Q6_K 0..4, Q5_K / Q3_K 0..6), two 0..4 (Q6_K 0..1, Q3_K / Q2_K 0..3), four 0..1 -- e.g. K = 29568 at one token gives 8
+    // only the instantiated chunk counts (FmtInfo::itc: launch_f walks the same caps) -- e.g.
+    // K = 29568 at one token gives 8
     if (p.itc > itc_max(fmt, p.nt)) p.itc = 0;
     // four tokens, one unit per lane (K <= 4096): cached too (Q6_K 14336x4096 x4 27.7 -> 20.7 us,
     // profiles/r02/decode_nt4_cache_ab.txt)
@@ -828,88 +803,34 @@ hipError_t launch_t(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *
     return hipGetLastError();
 }
 
+// Every kernel pick() can ask for: itc 0..the cap pick() clamps by (itc_max / fp8_itc_max) at
+// each token tile, in both ring forms for Q6_K.  A chunk count beyond the cap has no kernel.
 template <int F>
 hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, int64_t M, int64_t N, int64_t K,
                     int64_t ldc, const Pick &p, hipStream_t s)
 {
-#define GQ_LT(nt, itc) launch_t<F, nt, itc>(A, X, ldx, C, M, N, K, ldc, p, s)
-#define GQ_LTI(nt, itc) launch_t<F, nt, itc, 1>(A, X, ldx, C, M, N, K, ldc, p, s)
-    if constexpr (F == Q5_K || F == Q3_K || F == Q2_K)
-        if (p.fp8) return hipErrorInvalidValue;
-    if constexpr (F != Q5_K && F != Q3_K && F != Q2_K) if (p.fp8) { // (itc: one token only, fp8_itc_max)
-        if (p.nt == 1 && p.itc == 1) {
-            if constexpr (F == Q6_K)
-                if (p.img) return launch_t<F, 1, 1, 1, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-            return launch_t<F, 1, 1, 0, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-        }
-        if constexpr (F != Q6_K)
-            if (p.nt == 1 && p.itc == 2) return launch_t<F, 1, 2, 0, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-        if (p.itc != 0) return hipErrorInvalidValue;
+    auto tile = [&](auto nt, auto im, auto fp8) {
+        constexpr int NT = decltype(nt)::value, IM = decltype(im)::value, FP8 = decltype(fp8)::value;
+        return dispatch_upto<FP8 ? fp8_itc_max(F, NT) : itc_max(F, NT)>(p.itc, [&](auto itc) {
+            return launch_t<F, NT, decltype(itc)::value, IM, FP8>(A, X, ldx, C, M, N, K, ldc, p, s);
+        });
+    };
+    auto ring = [&](auto nt, auto fp8) {
         if constexpr (F == Q6_K)
-            if (p.img) switch (p.nt) {
-                case 1: return launch_t<F, 1, 0, 1, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-                case 2: return launch_t<F, 2, 0, 1, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-                default: return launch_t<F, 4, 0, 1, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-                }
-        switch (p.nt) {
-        case 1: return launch_t<F, 1, 0, 0, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-        case 2: return launch_t<F, 2, 0, 0, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-        default: return launch_t<F, 4, 0, 0, 1>(A, X, ldx, C, M, N, K, ldc, p, s);
-        }
+            if (p.img) return tile(nt, ic<1>{}, fp8);
+        return tile(nt, ic<0>{}, fp8);
+    };
+    auto form = [&](auto nt) {
+        if constexpr (!q8_1_only(F))
+            if (p.fp8) return ring(nt, ic<1>{});
+        return p.fp8 ? hipErrorInvalidValue : ring(nt, ic<0>{});
+    };
+    switch (p.nt) {
+    case 1: return form(ic<1>{});
+    case 2: return form(ic<2>{});
+    case 4: return form(ic<4>{});
+    default: return hipErrorInvalidValue;
     }
-    if constexpr (F == Q6_K) { // pick(): at most 8 cached units (4 chunks), 2 with two tokens
-        if (p.img) switch (p.nt * 8 + p.itc) {
-            case 8: return GQ_LTI(1, 0);
-            case 9: return GQ_LTI(1, 1);
-            case 10: return GQ_LTI(1, 2);
-            case 11: return GQ_LTI(1, 3);
-            case 12: return GQ_LTI(1, 4);
-            case 16: return GQ_LTI(2, 0);
-            case 17: return GQ_LTI(2, 1);
-            case 32: return GQ_LTI(4, 0);
-            case 33: return GQ_LTI(4, 1);
-            default: return hipErrorInvalidValue;
-            }
-        switch (p.nt * 8 + p.itc) {
-        case 8: return GQ_LT(1, 0);
-        case 9: return GQ_LT(1, 1);
-        case 10: return GQ_LT(1, 2);
-        case 11: return GQ_LT(1, 3);
-        case 12: return GQ_LT(1, 4);
-        case 16: return GQ_LT(2, 0);
-        case 17: return GQ_LT(2, 1);
-        case 32: return GQ_LT(4, 0);
-        case 33: return GQ_LT(4, 1);
-        default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (p.nt * 8 + p.itc) {
-        case 8: return GQ_LT(1, 0);
-        case 9: return GQ_LT(1, 1);
-        case 10: return GQ_LT(1, 2);
-        case 11: return GQ_LT(1, 3);
-        case 12: return GQ_LT(1, 4);
-        case 13: return GQ_LT(1, 5);
-        case 14: return GQ_LT(1, 6);
-        case 15:
-            if constexpr (F != Q5_K && F != Q3_K && (F != Q2_K || kQ2Itc1 >= 7)) return GQ_LT(1, 7);
-            return hipErrorInvalidValue; // (itc_max: Q5_K and Q3_K cache at most 6 units, Q2_K kQ2Itc1)
-
-        case 16: return GQ_LT(2, 0);
-        case 17: return GQ_LT(2, 1);
-        case 18: return GQ_LT(2, 2);
-        case 19: return GQ_LT(2, 3);
-        case 20:
-            if constexpr (F != Q3_K && F != Q2_K) return GQ_LT(2, 4);
-            return hipErrorInvalidValue; // (itc_max: Q3_K and Q2_K cache at most 3 units at two tokens)
-        case 32: return GQ_LT(4, 0);
-        case 33: return GQ_LT(4, 1);
-        default: return hipErrorInvalidValue; // (pick() caps itc at itc_max)
-        }
-    }
-#undef GQ_LT
-#undef GQ_LTI
-    return hipErrorInvalidValue;
 }
 
 // ---- grouped decode: several matrices (own type, activations, output) in one launch ----
@@ -932,13 +853,14 @@ struct GroupedArgs {
     GroupedProblem p[kMaxGroup];
 };
 
-// Q5 = 1: the launch holds a Q5_K item.  A kernel of its own, so that the other formats' grouped
+// SET: the case set, the largest FmtInfo::group_set of the launch's items.
+// SET = 1: the launch holds a Q5_K item.  A kernel of its own, so that the other formats' grouped
 // launches keep their case set (and register allocation) exactly; at one token it carries every
 // format's cases up to kQ5GroupItc cached chunks only -- with all of them the allocator spills
 // (kernel-resource-usage) -- and decode_grouped_ok refuses a mixed launch beyond that.
-// Q5 = 2: the launch holds a Q3_K item.  Again a kernel of its own (the Q5 = 0 and Q5 = 1 kernels
-// keep their case sets): Q5 = 1's cases and Q3_K's, at one token up to kQ3GroupItc cached chunks.
-// Q5 = 3: the launch holds a Q2_K item.  A fourth kernel for the same reason: Q5 = 2's cases (a
+// SET = 2: the launch holds a Q3_K item.  Again a kernel of its own (the SET = 0 and SET = 1 kernels
+// keep their case sets): SET = 1's cases and Q3_K's, at one token up to kQ3GroupItc cached chunks.
+// SET = 3: the launch holds a Q2_K item.  A fourth kernel for the same reason: SET = 2's cases (a
 // Q2_K file's layer holds Q3_K items too) and Q2_K's, at one token up to kQ2GroupItc cached chunks.
 #ifndef GQ_Q3_GROUP_ITC
 #define GQ_Q3_GROUP_ITC 3
@@ -947,10 +869,16 @@ struct GroupedArgs {
 #define GQ_Q2_GROUP_ITC 3
 #endif
 constexpr int kQ5GroupItc = 4, kQ3GroupItc = GQ_Q3_GROUP_ITC, kQ2GroupItc = GQ_Q2_GROUP_ITC;
-template <int NT, int FP8 = 0, int Q5 = 0>
+// the one-token cap of every item in a launch of case set 1.. (set 0 carries every type's own cap)
+constexpr int kGroupItc[] = {7, kQ5GroupItc, kQ3GroupItc, kQ2GroupItc};
+constexpr int kGroupSets = 4;
+// (the case lists below are written out by hand: GroupedProblem::code holds itc <= 7, and the
+// two-token lists end at Q3_K's 3)
+static_assert(kQ2Itc1 <= 7 && kQ2Itc2 <= 3, "stream_decode_grouped_kernel carries no further Q2_K cases");
+template <int NT, int FP8 = 0, int SET = 0>
 __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const GroupedArgs args)
 {
-    static_assert(!(FP8 && Q5), "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
+    static_assert(!(FP8 && SET), "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
     const int b = (int)blockIdx.x;
     int i = 0;
@@ -980,7 +908,7 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GF(Q8_0, 0, 0) GQ_GF(Q4_K, 0, 0) GQ_GF(Q6_K, 0, 0) GQ_GF(Q6_K, 0, 1)
         default: return;
         }
-    } else if constexpr (NT == 1 && Q5 == 3) { // (kQ2GroupItc)
+    } else if constexpr (NT == 1 && SET == 3) { // (kQ2GroupItc)
 #define GQ_G2(itc) GQ_GB(Q8_0, itc) GQ_GB(Q4_K, itc) GQ_GB(Q6_K, itc) GQ_GBI(itc) GQ_GB(Q5_K, itc) GQ_GB(Q3_K, itc) GQ_GB(Q2_K, itc)
         switch (q.code) {
             GQ_G2(0) GQ_G2(1) GQ_G2(2)
@@ -990,7 +918,7 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
         default: return;
         }
 #undef GQ_G2
-    } else if constexpr (NT == 1 && Q5 == 2) { // (kQ3GroupItc)
+    } else if constexpr (NT == 1 && SET == 2) { // (kQ3GroupItc)
 #define GQ_G3(itc) GQ_GB(Q8_0, itc) GQ_GB(Q4_K, itc) GQ_GB(Q6_K, itc) GQ_GBI(itc) GQ_GB(Q5_K, itc) GQ_GB(Q3_K, itc)
         switch (q.code) {
             GQ_G3(0) GQ_G3(1) GQ_G3(2)
@@ -1003,7 +931,7 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
         default: return;
         }
 #undef GQ_G3
-    } else if constexpr (NT == 1 && Q5) { // (kQ5GroupItc)
+    } else if constexpr (NT == 1 && SET) { // (kQ5GroupItc)
         switch (q.code) {
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q8_0, 2) GQ_GB(Q8_0, 3) GQ_GB(Q8_0, 4) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1)
             GQ_GB(Q4_K, 2) GQ_GB(Q4_K, 3) GQ_GB(Q4_K, 4) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GB(Q6_K, 2) GQ_GB(Q6_K, 3)
@@ -1025,15 +953,15 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GB(Q4_K, 2) GQ_GB(Q4_K, 3) GQ_GB(Q4_K, 4) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GBI(0) GQ_GBI(1)
         default: break;
         }
-        if constexpr (Q5) switch (q.code) {
+        if constexpr (SET) switch (q.code) {
             GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1) GQ_GB(Q5_K, 2) GQ_GB(Q5_K, 3) GQ_GB(Q5_K, 4)
         default: break;
         }
-        if constexpr (Q5 >= 2) switch (q.code) { // (kQ3Itc2)
+        if constexpr (SET >= 2) switch (q.code) { // (kQ3Itc2)
             GQ_GB(Q3_K, 0) GQ_GB(Q3_K, 1) GQ_GB(Q3_K, 2) GQ_GB(Q3_K, 3)
         default: break;
         }
-        if constexpr (Q5 == 3) switch (q.code) { // (kQ2Itc2)
+        if constexpr (SET == 3) switch (q.code) { // (kQ2Itc2)
             GQ_GB(Q2_K, 0) GQ_GB(Q2_K, 1) GQ_GB(Q2_K, 2) GQ_GB(Q2_K, 3)
         default: break;
         }
@@ -1042,15 +970,15 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GBI(0) GQ_GBI(1)
         default: break;
         }
-        if constexpr (Q5) switch (q.code) {
+        if constexpr (SET) switch (q.code) {
             GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1)
         default: break;
         }
-        if constexpr (Q5 >= 2) switch (q.code) {
+        if constexpr (SET >= 2) switch (q.code) {
             GQ_GB(Q3_K, 0) GQ_GB(Q3_K, 1)
         default: break;
         }
-        if constexpr (Q5 == 3) switch (q.code) {
+        if constexpr (SET == 3) switch (q.code) {
             GQ_GB(Q2_K, 0) GQ_GB(Q2_K, 1)
         default: break;
         }
@@ -1060,17 +988,17 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
 #undef GQ_GF
 }
 
-template <int NT, int FP8 = 0, int Q5 = 0>
+template <int NT, int FP8 = 0, int SET = 0>
 hipError_t launch_grouped_nt(GroupedArgs &a, int blocks, size_t lds, hipStream_t s)
 {
     static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_grouped_kernel<NT, FP8, Q5>,
+        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_grouped_kernel<NT, FP8, SET>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    stream_decode_grouped_kernel<NT, FP8, Q5><<<dim3((unsigned)blocks), dim3(DW * 64), lds, s>>>(a);
+    stream_decode_grouped_kernel<NT, FP8, SET><<<dim3((unsigned)blocks), dim3(DW * 64), lds, s>>>(a);
     return hipGetLastError();
 }
 
@@ -1123,37 +1051,18 @@ hipError_t launch_id_t(const IdArgs &a, int pairs, size_t lds, hipStream_t s)
     return hipGetLastError();
 }
 
-// launch_f's one-token cases (itc_max: Q8_0 / Q4_K / Q2_K 0..7, Q5_K / Q3_K 0..6, Q6_K 0..4 packed and image)
+// launch_f's one-token q8_1 kernels: itc 0..itc_max(F, 1), both ring forms for Q6_K
 template <int F>
 hipError_t launch_id_f(const IdArgs &a, int pairs, const Pick &p, hipStream_t s)
 {
-#define GQ_LID(itc, im) launch_id_t<F, itc, im>(a, pairs, p.lds, s)
-    if constexpr (F == Q6_K) {
-        if (p.img) switch (p.itc) {
-            case 0: return GQ_LID(0, 1);
-            case 1: return GQ_LID(1, 1);
-            case 2: return GQ_LID(2, 1);
-            case 3: return GQ_LID(3, 1);
-            case 4: return GQ_LID(4, 1);
-            default: return hipErrorInvalidValue;
-            }
-    }
-    switch (p.itc) {
-    case 0: return GQ_LID(0, 0);
-    case 1: return GQ_LID(1, 0);
-    case 2: return GQ_LID(2, 0);
-    case 3: return GQ_LID(3, 0);
-    case 4: return GQ_LID(4, 0);
-    default: break;
-    }
-    if constexpr (F != Q6_K) {
-        if (p.itc == 5) return GQ_LID(5, 0);
-        if (p.itc == 6) return GQ_LID(6, 0);
-        if constexpr (F != Q5_K && F != Q3_K && (F != Q2_K || kQ2Itc1 >= 7))
-            if (p.itc == 7) return GQ_LID(7, 0);
-    }
-#undef GQ_LID
-    return hipErrorInvalidValue; // (pick() caps itc at itc_max)
+    auto ring = [&](auto im) {
+        return dispatch_upto<itc_max(F, 1)>(p.itc, [&](auto itc) {
+            return launch_id_t<F, decltype(itc)::value, decltype(im)::value>(a, pairs, p.lds, s);
+        });
+    };
+    if constexpr (F == Q6_K)
+        if (p.img) return ring(ic<1>{});
+    return ring(ic<0>{});
 }
 
 } // namespace
@@ -1181,16 +1090,9 @@ hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int
         Pick p;
         p.fp8 = fp8;
         if (!pick(fmt, m, N, K, p)) return hipErrorInvalidValue;
-        hipError_t e;
-        switch (fmt) {
-        case Q8_0: e = launch_f<Q8_0>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        case Q4_K: e = launch_f<Q4_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        case Q6_K: e = launch_f<Q6_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        case Q5_K: e = launch_f<Q5_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        case Q3_K: e = launch_f<Q3_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        case Q2_K: e = launch_f<Q2_K>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s); break;
-        default: return hipErrorInvalidValue;
-        }
+        hipError_t e = dispatch_fmt(fmt, [&](auto f) {
+            return launch_f<decltype(f)::value>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s);
+        });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -1205,18 +1107,14 @@ bool decode_grouped_ok(const DecodeItem *items, int n, int64_t N, bool fp8)
         if (it.M * row_bytes(it.fmt, it.K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets
     }
     // a one-token launch with a Q5_K, Q3_K or Q2_K item: every item within the cached chunks its kernel carries
-    bool q5 = false, q3 = false, q2 = false;
-    for (int i = 0; i < n; ++i) {
-        q5 = q5 || items[i].fmt == Q5_K;
-        q3 = q3 || items[i].fmt == Q3_K;
-        q2 = q2 || items[i].fmt == Q2_K;
-    }
-    if (q5 || q3 || q2) {
+    int set = 0;
+    for (int i = 0; i < n; ++i) set = std::max(set, fmt_info(items[i].fmt).group_set);
+    if (set > 0) {
         if (fp8) return false;
         for (int i = 0; i < n; ++i) {
             Pick p;
             if (!pick(items[i].fmt, items[i].M, N, items[i].K, p)) return false;
-            if (p.nt == 1 && p.itc > (q2 ? kQ2GroupItc : (q3 ? kQ3GroupItc : kQ5GroupItc))) return false;
+            if (p.nt == 1 && p.itc > kGroupItc[set]) return false;
         }
     }
     return true;
@@ -1317,32 +1215,22 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
             blocks += p.grid;
         }
         a.n = np;
-        bool q5 = false, q3 = false, q2 = false;
-        for (int j = 0; j < np; ++j) {
-            q5 = q5 || items[pi[j]].fmt == Q5_K;
-            q3 = q3 || items[pi[j]].fmt == Q3_K;
-            q2 = q2 || items[pi[j]].fmt == Q2_K;
-        }
-        if ((q5 || q3 || q2) && nt == 1)
+        int set = 0; // the kernel's case set
+        for (int j = 0; j < np; ++j) set = std::max(set, fmt_info(items[pi[j]].fmt).group_set);
+        if (set > 0 && nt == 1)
             for (int j = 0; j < np; ++j)
-                if (a.p[j].code % 8 > (q2 ? kQ2GroupItc : (q3 ? kQ3GroupItc : kQ5GroupItc)))
-                    return hipErrorInvalidValue; // (decode_grouped_ok)
-        hipError_t e = q2        ? (fp8 ? hipErrorInvalidValue
-                                        : nt == 1 ? launch_grouped_nt<1, 0, 3>(a, blocks, lds, s)
-                                        : nt == 2 ? launch_grouped_nt<2, 0, 3>(a, blocks, lds, s)
-                                                  : launch_grouped_nt<4, 0, 3>(a, blocks, lds, s))
-                       : q3        ? (fp8 ? hipErrorInvalidValue
-                                        : nt == 1 ? launch_grouped_nt<1, 0, 2>(a, blocks, lds, s)
-                                        : nt == 2 ? launch_grouped_nt<2, 0, 2>(a, blocks, lds, s)
-                                                  : launch_grouped_nt<4, 0, 2>(a, blocks, lds, s))
-                       : q5        ? (fp8 ? hipErrorInvalidValue
-                                        : nt == 1 ? launch_grouped_nt<1, 0, 1>(a, blocks, lds, s)
-                                        : nt == 2 ? launch_grouped_nt<2, 0, 1>(a, blocks, lds, s)
-                                                  : launch_grouped_nt<4, 0, 1>(a, blocks, lds, s))
-                       : fp8       ? (nt == 1 ? launch_grouped_nt<1, 1>(a, blocks, lds, s) : launch_grouped_nt<2, 1>(a, blocks, lds, s))
-                       : nt == 1 ? launch_grouped_nt<1>(a, blocks, lds, s)
-                       : nt == 2 ? launch_grouped_nt<2>(a, blocks, lds, s)
-                                 : launch_grouped_nt<4>(a, blocks, lds, s);
+                if (a.p[j].code % 8 > kGroupItc[set]) return hipErrorInvalidValue; // (decode_grouped_ok)
+        hipError_t e;
+        if (fp8) // (sets 1..: no fp8 form; decode_grouped_ok: at most two tokens)
+            e = set > 0 ? hipErrorInvalidValue
+                        : (nt == 1 ? launch_grouped_nt<1, 1>(a, blocks, lds, s) : launch_grouped_nt<2, 1>(a, blocks, lds, s));
+        else
+            e = dispatch_upto<kGroupSets - 1>(set, [&](auto st) {
+                constexpr int SET = decltype(st)::value;
+                return nt == 1   ? launch_grouped_nt<1, 0, SET>(a, blocks, lds, s)
+                       : nt == 2 ? launch_grouped_nt<2, 0, SET>(a, blocks, lds, s)
+                                 : launch_grouped_nt<4, 0, SET>(a, blocks, lds, s);
+            });
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
@@ -1384,15 +1272,7 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
     a.S = (int)S;
     a.gx = p.grid;
     a.geo = p.geo;
-    switch (fmt) {
-    case Q8_0: return launch_id_f<Q8_0>(a, (int)pairs, p, s);
-    case Q4_K: return launch_id_f<Q4_K>(a, (int)pairs, p, s);
-    case Q6_K: return launch_id_f<Q6_K>(a, (int)pairs, p, s);
-    case Q5_K: return launch_id_f<Q5_K>(a, (int)pairs, p, s);
-    case Q3_K: return launch_id_f<Q3_K>(a, (int)pairs, p, s);
-    case Q2_K: return launch_id_f<Q2_K>(a, (int)pairs, p, s);
-    default: return hipErrorInvalidValue;
-    }
+    return dispatch_fmt(fmt, [&](auto f) { return launch_id_f<decltype(f)::value>(a, (int)pairs, p, s); });
 }
 
 } // namespace gq

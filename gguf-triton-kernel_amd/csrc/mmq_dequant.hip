@@ -180,16 +180,10 @@ hipError_t dequant_perm(int fmt, const uint8_t *A, uint16_t *W, int64_t M, int64
     const int64_t n = M * (K / 32);
     if (n == 0) return hipSuccess;
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    switch (fmt) {
-    case Q8_0: dequant_kernel<Q8_0, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    case Q4_K: dequant_kernel<Q4_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    case Q6_K: dequant_kernel<Q6_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    case Q5_K: dequant_kernel<Q5_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    case Q3_K: dequant_kernel<Q3_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    case Q2_K: dequant_kernel<Q2_K, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_fmt(fmt, [&](auto f) {
+        dequant_kernel<decltype(f)::value, PERM><<<grid, block, 0, s>>>(A, W, M, K, ldw);
+        return hipGetLastError();
+    });
 }
 
 // ---- hipBLASLt plans, cached per (device, M, N, K, ldc) ----

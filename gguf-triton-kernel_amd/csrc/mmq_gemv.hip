@@ -106,15 +106,8 @@ hipError_t launch_fmt(const uint8_t *A, const int8_t *xq, const float *xd, const
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,
                        int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    switch (fmt) {
-    case Q8_0: return launch_fmt<Q8_0>(A, xq, xd, xs, C, M, N, K, ldc, s);
-    case Q4_K: return launch_fmt<Q4_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
-    case Q6_K: return launch_fmt<Q6_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
-    case Q5_K: return launch_fmt<Q5_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
-    case Q3_K: return launch_fmt<Q3_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
-    case Q2_K: return launch_fmt<Q2_K>(A, xq, xd, xs, C, M, N, K, ldc, s);
-    default: return hipErrorInvalidValue; // (an unlisted format never runs another format's strides)
-    }
+    // (an unknown format is an error: it never runs another format's strides)
+    return dispatch_fmt(fmt, [&](auto f) { return launch_fmt<decltype(f)::value>(A, xq, xd, xs, C, M, N, K, ldc, s); });
 }
 
 } // namespace gq

@@ -703,10 +703,10 @@ int kstream_cw(int64_t N, int64_t K)
 
 bool kstream_ok(int fmt, int64_t M, int64_t N, int64_t K)
 {
-    if (fmt != Q8_0 && fmt != Q4_K && fmt != Q6_K) return false;
+    if (!known_fmt(fmt) || q8_1_only(fmt)) return false; // kbody: Q8_0, Q4_K, Q6_K
     if (M < 16 || M % 16 != 0 || kstream_cw(N, K) == 0) return false; // (whole 16-row items)
     // 32-bit buffer offsets over the weights
-    return M * (K / 256) * (int64_t)(fmt == Q8_0 ? 272 : (fmt == Q4_K ? 144 : 210)) < ((int64_t)1 << 31);
+    return M * (K / 256) * (int64_t)fmt_info(fmt).sb_bytes() < ((int64_t)1 << 31);
 }
 
 size_t kstream_partial_bytes(const KItem *items, int n, int64_t N)
@@ -789,7 +789,7 @@ hipError_t launch_kstream(const KItem *items, int n, int64_t N, int aq, void *pa
             p.kofs = z * per;
             p.nsbp = nsb - p.kofs < per ? nsb - p.kofs : per;
             p.cw = (p.nsbp + KW - 1) / KW;
-            const int64_t sbb = it.fmt == Q8_0 ? 272 : (it.fmt == Q4_K ? 144 : 210);
+            const int64_t sbb = fmt_info(it.fmt).sb_bytes();
             // the deal's cost of a 16-row item: per super-block its bytes - 55: Q4_K 89,
             // Q6_K 155, Q8_0 217 -- a Q6_K super-block's dequantization costs more per byte than the
             // bytes alone say; the 7B layer 3-4% faster than a deal by bytes at 5..32 tokens (x16

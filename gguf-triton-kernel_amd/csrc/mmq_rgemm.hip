@@ -22,6 +22,7 @@
 // same x~, v_mfma_f32_16x16x32_f16 in the same (sub-stage, k-step) order into fp32 accumulators;
 // with one split per super-block the split-K partials are written in gemm_kernel's fp16 form and
 // summed by its reduce kernel (launch_gemm_reduce_f16).
+#include <algorithm>
 #include <type_traits>
 
 #include "gguf_blocks.hpp"
@@ -1039,29 +1040,31 @@ template <int NB> constexpr int max_slds()
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
-// Q3 = 1: the launch holds a Q3_K part.  A kernel of its own: the Q3_K body beside the others
+// SET: the case set, the largest FmtInfo::sgemm_set of the launch's parts.
+// SET = 1: the launch holds a Q3_K part.  A kernel of its own: the Q3_K body beside the others
 // raised sgemm_grouped_kernel<8>'s registers (185 -> 195), so the other formats' launches keep
-// the kernel they had.  Q3 = 2: the launch holds a Q2_K part -- a third kernel for the same
+// the kernel they had.  SET = 2: the launch holds a Q2_K part -- a third kernel for the same
 // reason, with Q3_K's body too (a Q2_K file's layers hold both).
-template <int NB, int Q3 = 0>
+constexpr int kSgemmSets = 3;
+template <int NB, int SET = 0>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a);
-template <int NB, int Q3 = 0> int grouped_occ()
+template <int NB, int SET = 0> int grouped_occ()
 {
     int n = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sgemm_grouped_kernel<NB, Q3>, 64 * RW, 0) == hipSuccess ? n : 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sgemm_grouped_kernel<NB, SET>, 64 * RW, 0) == hipSuccess ? n : 0;
 }
-template <int NB, int Q3>
+template <int NB, int SET>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
 {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[max_slds<NB>()];
     const int b = (int)blockIdx.x;
     auto run = [&](const SPart &q, const TileId &id, int64_t sb0, int64_t sb1) __attribute__((always_inline)) {
-        if constexpr (Q3 != 0)
+        if constexpr (SET != 0)
             if (q.fmt == Q3_K) {
                 sgemm_body<Q3_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
                 return;
             }
-        if constexpr (Q3 == 2)
+        if constexpr (SET == 2)
             if (q.fmt == Q2_K) {
                 sgemm_body<Q2_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
                 return;
@@ -1389,17 +1392,16 @@ hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *
                         int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
     if (!p.ok) return hipErrorInvalidValue;
-#define GQ_SG_NB(F)                                                                                                       switch (p.nb) {                                                                                                       case 1: return launch_snb<F, 1>(A, X, C, partials, p, M, N, K, ldc, s);                                               case 2: return launch_snb<F, 2>(A, X, C, partials, p, M, N, K, ldc, s);                                               case 4: return launch_snb<F, 4>(A, X, C, partials, p, M, N, K, ldc, s);                                               case 8: return launch_snb<F, 8>(A, X, C, partials, p, M, N, K, ldc, s);                                               default: return hipErrorInvalidValue;                                                                                 }
-    switch (fmt) {
-    case Q8_0: GQ_SG_NB(Q8_0)
-    case Q4_K: GQ_SG_NB(Q4_K)
-    case Q6_K: GQ_SG_NB(Q6_K)
-    case Q5_K: GQ_SG_NB(Q5_K)
-    case Q3_K: GQ_SG_NB(Q3_K)
-    case Q2_K: GQ_SG_NB(Q2_K)
-    default: return hipErrorInvalidValue;
-    }
-#undef GQ_SG_NB
+    return dispatch_fmt(fmt, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        switch (p.nb) {
+        case 1: return launch_snb<F, 1>(A, X, C, partials, p, M, N, K, ldc, s);
+        case 2: return launch_snb<F, 2>(A, X, C, partials, p, M, N, K, ldc, s);
+        case 4: return launch_snb<F, 4>(A, X, C, partials, p, M, N, K, ldc, s);
+        case 8: return launch_snb<F, 8>(A, X, C, partials, p, M, N, K, ldc, s);
+        default: return hipErrorInvalidValue;
+        }
+    });
 }
 
 // NB from host-known sizes only: plan_sgemm's thresholds at the mean pairs per expert that can
@@ -1426,24 +1428,16 @@ hipError_t launch_sgemm_id(int fmt, const uint8_t *A, const uint16_t *X, uint16_
                            hipStream_t s)
 {
     if (!p.ok) return hipErrorInvalidValue;
-#define GQ_SID_NB(F)                                                                                                   \
-    switch (p.nb) {                                                                                                    \
-    case 1: return launch_sid<F, 1>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
-    case 2: return launch_sid<F, 2>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
-    case 4: return launch_sid<F, 4>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
-    case 8: return launch_sid<F, 8>(A, X, C, perm, hdr, table, p, M, K, ldc, s);                                       \
-    default: return hipErrorInvalidValue;                                                                              \
-    }
-    switch (fmt) {
-    case Q8_0: GQ_SID_NB(Q8_0)
-    case Q4_K: GQ_SID_NB(Q4_K)
-    case Q6_K: GQ_SID_NB(Q6_K)
-    case Q5_K: GQ_SID_NB(Q5_K)
-    case Q3_K: GQ_SID_NB(Q3_K)
-    case Q2_K: GQ_SID_NB(Q2_K)
-    default: return hipErrorInvalidValue;
-    }
-#undef GQ_SID_NB
+    return dispatch_fmt(fmt, [&](auto f) {
+        constexpr int F = decltype(f)::value;
+        switch (p.nb) {
+        case 1: return launch_sid<F, 1>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
+        case 2: return launch_sid<F, 2>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
+        case 4: return launch_sid<F, 4>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
+        case 8: return launch_sid<F, 8>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
+        default: return hipErrorInvalidValue;
+        }
+    });
 }
 
 SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int splits)
@@ -1455,9 +1449,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
     int64_t units = 0, Lmax = 1;
     for (int i = 0; i < n; ++i) {
         if (items[i].M < 1 || items[i].K < 256 || items[i].K % 256 != 0) return g;
-        if (items[i].fmt != Q8_0 && items[i].fmt != Q4_K && items[i].fmt != Q6_K && items[i].fmt != Q5_K && items[i].fmt != Q3_K &&
-            items[i].fmt != Q2_K)
-            return g;
+        if (!known_fmt(items[i].fmt)) return g;
         g.tiles_m[i] = (int)((items[i].M + RBM - 1) / RBM);
         const int64_t t = (int64_t)g.tiles_m[i] * tn, nsb = items[i].K / 256;
         units += t * nsb;
@@ -1488,7 +1480,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
         // (profiles/r05/sgemm_grouped_cost_ab.txt; -55, the K-chunked stream's best, 74.6 / 76.1 / 99.2)
         int64_t ctot = 0;
         for (int i = 0; i < n; ++i) {
-            g.cost[i] = items[i].fmt == Q8_0 ? 272 : (items[i].fmt == Q4_K ? 144 : (items[i].fmt == Q5_K ? 176 : (items[i].fmt == Q3_K ? 110 : (items[i].fmt == Q2_K ? 84 : 210))));
+            g.cost[i] = fmt_info(items[i].fmt).sb_bytes();
             g.cstart[i] = (int)ctot;
             ctot += (int64_t)g.tiles_m[i] * tn * (items[i].K / 256) * g.cost[i];
         }
@@ -1573,15 +1565,13 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     a.spol = kSpol;
     a.full = tuning().sgemm_full > 0;
     a.streamk = r.streamk = g.streamk ? 1 : 0;
-    bool q3 = false, q2 = false;
-    for (int i = 0; i < n; ++i) {
-        q3 = q3 || items[i].fmt == Q3_K;
-        q2 = q2 || items[i].fmt == Q2_K;
-    }
-    static const int occ[4] = {grouped_occ<1>(), grouped_occ<2>(), grouped_occ<4>(), grouped_occ<8>()};
-    static const int occ3[4] = {grouped_occ<1, 1>(), grouped_occ<2, 1>(), grouped_occ<4, 1>(), grouped_occ<8, 1>()};
-    static const int occ2[4] = {grouped_occ<1, 2>(), grouped_occ<2, 2>(), grouped_occ<4, 2>(), grouped_occ<8, 2>()};
-    const int oc = (q2 ? occ2 : (q3 ? occ3 : occ))[g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3))];
+    int set = 0; // the kernel's case set
+    for (int i = 0; i < n; ++i) set = std::max(set, fmt_info(items[i].fmt).sgemm_set);
+    const int nbi = g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3));
+    static const int occ[kSgemmSets][4] = {{grouped_occ<1>(), grouped_occ<2>(), grouped_occ<4>(), grouped_occ<8>()},
+                                           {grouped_occ<1, 1>(), grouped_occ<2, 1>(), grouped_occ<4, 1>(), grouped_occ<8, 1>()},
+                                           {grouped_occ<1, 2>(), grouped_occ<2, 2>(), grouped_occ<4, 2>(), grouped_occ<8, 2>()}};
+    const int oc = occ[set][nbi];
     a.ilc = g.streamk && tuning().rgemm_ilc != 0 && g.blocks <= num_cus() * oc ? 1 : 0;
     a.U = r.U = g.U;
     a.W = r.W = g.blocks;
@@ -1600,12 +1590,22 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
             rb += g.tiles_m[i] * g.tiles_n * bpt;
         }
     }
-#define GQ_SGG(NB_)                                                                                                       case NB_:                                                                                                                 if (q2) sgemm_grouped_kernel<NB_, 2><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                             else if (q3) sgemm_grouped_kernel<NB_, 1><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                             else sgemm_grouped_kernel<NB_><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);                                        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;                                                    if (r.n > 0) reduce_grouped_kernel<NB_><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);                                   return hipGetLastError();
-    switch (g.nb) {
-        GQ_SGG(1) GQ_SGG(2) GQ_SGG(4) GQ_SGG(8)
-    default: return hipErrorInvalidValue;
-    }
-#undef GQ_SGG
+    auto launch = [&](auto nb, auto st) {
+        constexpr int NB = decltype(nb)::value;
+        sgemm_grouped_kernel<NB, decltype(st)::value><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);
+        if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
+        if (r.n > 0) reduce_grouped_kernel<NB><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);
+        return hipGetLastError();
+    };
+    return dispatch_upto<kSgemmSets - 1>(set, [&](auto st) {
+        switch (g.nb) {
+        case 1: return launch(ic<1>{}, st);
+        case 2: return launch(ic<2>{}, st);
+        case 4: return launch(ic<4>{}, st);
+        case 8: return launch(ic<8>{}, st);
+        default: return hipErrorInvalidValue;
+        }
+    });
 }
 
 hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *partials,

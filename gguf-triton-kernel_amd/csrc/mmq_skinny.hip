@@ -234,7 +234,7 @@ SkinnyPlan plan_skinny(int fmt, int64_t M, int64_t N, int64_t K, int rg, int d)
     SkinnyPlan p;
     p.nb = N <= 16 ? 1 : 2;
     p.d = 2;
-    if (fmt != Q8_0 && fmt != Q4_K && fmt != Q6_K) { // no plan: launch_skinny refuses rg = 0
+    if (!known_fmt(fmt) || q8_1_only(fmt)) { // (launch_skinny: Q8_0, Q4_K, Q6_K) no plan: it refuses rg = 0
         p.rg = 0;
         return p;
     }
@@ -246,8 +246,7 @@ SkinnyPlan plan_skinny(int fmt, int64_t M, int64_t N, int64_t K, int rg, int d)
     // arithmetic is the same for every rg.
     const int64_t frags = (M + 15) / 16;
     const int rmax = rg_max_of(fmt);
-    const int64_t row_bytes = fmt == Q8_0 ? K / 32 * 34 : (fmt == Q4_K ? K / 256 * 144 : K / 256 * 210);
-    const double xr = 0.5 * (double)(N * K * 2) / (double)(16 * row_bytes);
+    const double xr = 0.5 * (double)(N * K * 2) / (double)(16 * row_bytes(fmt, K));
     double best = 1e300;
     for (int r = 1; r <= rmax; ++r) {
         const int64_t units = (frags + r - 1) / r;

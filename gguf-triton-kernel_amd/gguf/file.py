@@ -18,10 +18,13 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from .blocks import BLOCK
+
 GGUF_MAGIC = b"GGUF"
 # ggml type id -> (name, block elements, block bytes)
-GGML_TYPES = {0: ("f32", 1, 4), 1: ("f16", 1, 2), 8: ("q8_0", 32, 34), 10: ("q2_k", 256, 84), 11: ("q3_k", 256, 110),
-              12: ("q4_k", 256, 144), 13: ("q5_k", 256, 176), 14: ("q6_k", 256, 210)}
+GGML_TYPES = {0: ("f32", 1, 4), 1: ("f16", 1, 2)}
+GGML_TYPES.update({i: (f, *BLOCK[f]) for i, f in ((8, "q8_0"), (10, "q2_k"), (11, "q3_k"), (12, "q4_k"), (13, "q5_k"),
+                                                  (14, "q6_k"))})
 TYPE_IDS = {v[0]: k for k, v in GGML_TYPES.items()}
 
 # metadata value types

@@ -11,6 +11,8 @@ import os
 
 import torch
 
+from gguf.blocks import BLOCK
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(os.path.dirname(_HERE), "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgguf_mmq.so")
@@ -20,8 +22,8 @@ GQ_ACT_Q8_1, GQ_ACT_FP8_E4M3 = 0, 1
 ACTS = {"q8_1": GQ_ACT_Q8_1, "fp8": GQ_ACT_FP8_E4M3}
 TYPES = {"q8_0": GQ_Q8_0, "q4_k": GQ_Q4_K, "q6_k": GQ_Q6_K, "q5_k": GQ_Q5_K, "q3_k": GQ_Q3_K,
          "q2_k": GQ_Q2_K}
-BLOCK_ELEMS = {GQ_Q8_0: 32, GQ_Q4_K: 256, GQ_Q6_K: 256, GQ_Q5_K: 256, GQ_Q3_K: 256, GQ_Q2_K: 256}
-BLOCK_BYTES = {GQ_Q8_0: 34, GQ_Q4_K: 144, GQ_Q6_K: 210, GQ_Q5_K: 176, GQ_Q3_K: 110, GQ_Q2_K: 84}
+BLOCK_ELEMS = {TYPES[f]: qk for f, (qk, _) in BLOCK.items()}
+BLOCK_BYTES = {TYPES[f]: nbytes for f, (_, nbytes) in BLOCK.items()}
 
 # symbol -> (argtypes, restype); mirrors include/gguf_mmq.h
 _P, _I64, _I, _SZ = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t
@@ -561,7 +563,7 @@ def quantize_weights_device(fmt: str, X: torch.Tensor) -> torch.Tensor:
     if not X.is_cuda or X.dtype != want:
         raise RuntimeError(f"quantize_weights_device({fmt}) needs a {want} device tensor")
     X = X.contiguous().reshape(-1)
-    qk, nbytes = (32, 34) if fmt == "q8_0" else (256, 144 if fmt == "q4_k" else 210)
+    qk, nbytes = BLOCK[fmt]
     if X.numel() % qk:
         raise RuntimeError(f"{X.numel()} elements are not whole {fmt} blocks")
     out = torch.empty(X.numel() // qk * nbytes, dtype=torch.int8, device=X.device)

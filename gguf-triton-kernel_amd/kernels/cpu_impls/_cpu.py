@@ -6,10 +6,12 @@ import ctypes
 import numpy as np
 import torch
 
+from gguf.blocks import BLOCK
 from utils.quantize._qlib import lib as _qlib
 
-_BYTES = {0: 34, 1: 144, 2: 210, 3: 176, 4: 110, 5: 84}
-_QK = {0: 32, 1: 256, 2: 256, 3: 256, 4: 256, 5: 256}
+# by gq_type (the table's order)
+_QK = {t: qk for t, (qk, _) in enumerate(BLOCK.values())}
+_BYTES = {t: nbytes for t, (_, nbytes) in enumerate(BLOCK.values())}
 
 
 def cpu_mmq(gtype: int, A: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int, threads: int = 0) -> torch.Tensor:

@@ -7,13 +7,14 @@ import os
 import numpy as np
 import torch
 
+from gguf import blocks
+
 _LIB_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "lib",
                          "libgguf_quant.so")
 _lib = None
 _P, _I64 = ctypes.c_void_p, ctypes.c_int64
 
-BLOCK = {"q8_0": (32, 34), "q8_1": (32, 36), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176),
-         "q3_k": (256, 110), "q2_k": (256, 84)}
+BLOCK = {**blocks.BLOCK, "q8_1": blocks.Q8_1}
 
 
 def lib():

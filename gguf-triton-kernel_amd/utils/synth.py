@@ -10,8 +10,7 @@ from __future__ import annotations
 
 import numpy as np
 
-BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q5_k": (256, 176), "q3_k": (256, 110),
-         "q2_k": (256, 84)}
+from gguf.blocks import BLOCK  # noqa: F401  (re-exported: utils.synth.BLOCK)
 
 
 def _scales(rng, n):
