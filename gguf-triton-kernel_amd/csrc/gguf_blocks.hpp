@@ -15,6 +15,9 @@
 //   Q2_K 256 elems / 84 B : [0:16] scales (sc = low nibble, m = high, per 16 elements) |
 //                           [16:80] qs (2-bit, Q3_K's layout) | [80:82] d | [82:84] dmin
 //                           q = (qs[32*(e/128) + e%32] >> 2*((e%128)/32)) & 3;  w = d*sc_{e/16}*q - dmin*m_{e/16}
+//   Q4_0  32 elems / 18 B : [0:2] d fp16 | [2:18] qs[16]  (element j: qs[j] & 15, element 16+j: qs[j] >> 4)
+//                           w = d*(q - 8)   (a Q8_0 block with the same d and the int8 codes q - 8;
+//                           256 weights are 144 bytes, as Q4_K's)
 //   Q8_1 (activations) 36 B: [0:2] d | [2:4] s = d*sum(q) | [4:36] qs int8[32]
 // Reference: block docs in kernels/mmq_q4_k.py:1-16, kernels/mmq_q6_k.py:1-14,
 // utils/quantize/q8_1.py:1-11; unpack rules kernels/mmq_q4_k.py:30-114, mmq_q6_k.py:28-68.
@@ -31,7 +34,7 @@
 
 namespace gq {
 
-enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3, Q3_K = 4, Q2_K = 5 };
+enum Fmt : int { Q8_0 = 0, Q4_K = 1, Q6_K = 2, Q5_K = 3, Q3_K = 4, Q2_K = 5, Q4_0 = 6 };
 
 // The cached-chunk caps of the Q3_K / Q2_K decode kernels (FmtInfo below), with their build-time
 // overrides (make variant VFLAGS=... A/B builds).
@@ -46,6 +49,15 @@ constexpr int kQ3Itc1 = 6, kQ3Itc2 = 3; // Q3_K: the most cached chunks at one /
 #define GQ_Q2_ITC2 3
 #endif
 constexpr int kQ2Itc1 = GQ_Q2_ITC1, kQ2Itc2 = GQ_Q2_ITC2;
+// Q4_0: Q8_0's unit registers after the decode (16 code words, two scales) and 10 raw registers
+// in flight where Q8_0 has 18: Q8_0's caps compile without scratch
+#ifndef GQ_Q40_ITC1
+#define GQ_Q40_ITC1 7
+#endif
+#ifndef GQ_Q40_ITC2
+#define GQ_Q40_ITC2 4
+#endif
+constexpr int kQ40Itc1 = GQ_Q40_ITC1, kQ40Itc2 = GQ_Q40_ITC2;
 
 // What the host side and the kernels' template parameters need to know of a block type: one row
 // per Fmt in kFmt[].  A new type is a row here plus its device code ("Adding a block type").
@@ -81,6 +93,8 @@ constexpr FmtInfo kFmt[] = {
     {256, 110, false, true, 4, true, {kQ3Itc1, kQ3Itc2, 1}, 2, 1, 2, 1},   // Q3_K
     // 84 = 4 * 21 bytes: every super-block and every field is 4-byte aligned
     {256, 84, false, true, 32, true, {kQ2Itc1, kQ2Itc2, 1}, 2, 1, 3, 2},   // Q2_K
+    // Q8_0's q8_1 arithmetic on the signed nibbles: no mins, no code sums (code_offset unused)
+    {32, 18, false, false, 32, true, {kQ40Itc1, kQ40Itc2, 1}, 2, 1, 4, 3}, // Q4_0
 };
 constexpr int kNumFmts = (int)(sizeof(kFmt) / sizeof(kFmt[0]));
 constexpr bool known_fmt(int f) { return f >= 0 && f < kNumFmts; }
@@ -88,7 +102,7 @@ constexpr bool known_fmt(int f) { return f >= 0 && f < kNumFmts; }
 // ABI's answer for an unknown type's row size -- with the general caps.
 constexpr FmtInfo kFmtOther = {256, 210, false, true, 32, false, {7, 4, 1}, 2, 1, 0, 0};
 constexpr const FmtInfo &fmt_info(int f) { return known_fmt(f) ? kFmt[f] : kFmtOther; }
-// packed bytes of a K-element row.  Not K / 256 * sb_bytes: a Q8_0 row may be a multiple of 32 only
+// packed bytes of a K-element row.  Not K / 256 * sb_bytes: a Q8_0 / Q4_0 row may be a multiple of 32 only
 constexpr int64_t row_bytes(int f, int64_t K) { return K / fmt_info(f).qk * fmt_info(f).bytes; }
 
 template <int F> struct Layout { static constexpr int QK = kFmt[F].qk, BYTES = kFmt[F].bytes; };

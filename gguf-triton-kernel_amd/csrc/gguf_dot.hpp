@@ -7,6 +7,7 @@
 //   Q5_K : Q4_K's expression, q = 0..31
 //   Q3_K : Q6_K's expression with (q-4), the unit's two blocks being 2u and 2u+1
 //   Q2_K : dB*(d*sc*sum(q*qB) - dmin*m*sum(qB)) per 16 elements, blocks 2u and 2u+1
+//   Q4_0 : Q8_0's expression on the codes q - 8 (d*dB*sum((q-8)*qB); not d*(dB*sum(q*qB) - 8*s))
 // with exact int32 dot products (v_dot4_i32_i8) and fp32 accumulation.
 #pragma once
 #include "gguf_blocks.hpp"
@@ -66,7 +67,7 @@ __device__ __forceinline__ void load_act(Act<F, NT> &a, const int8_t *__restrict
 template <int F, int NT>
 __device__ __forceinline__ void dot_unit(const UnitRaw<F> &r, const Act<F, NT> &a, float (&acc)[NT])
 {
-    if constexpr (F == Q8_0) {
+    if constexpr (F == Q8_0 || F == Q4_0) { // (Q4_0: UnitRaw holds the signed nibbles as Q8_0 codes)
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             int i0 = 0, i1 = 0;

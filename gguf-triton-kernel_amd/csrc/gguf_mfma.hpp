@@ -211,6 +211,39 @@ __device__ __forceinline__ void q2k_frags(const uint8_t *img, int g, int u, f16x
     }
 }
 
+// Q4_0 sub-stage u (elements 64u..64u+63) from a half image of the 144-byte group of eight blocks
+// (mmq_rgemm.hip, half h = u >> 1): group bytes 64h..64h+79, so blocks 4h..4h+3 start at image byte
+// 8h.  k-step n = block 2u+n, at image byte 8h + 18*(2(u&1) + n): d, then qs[16]; lane group g takes
+// elements 8g..8g+7 of the block = the nibbles at shift 4(g >> 1) of qs bytes 8(g&1)..+7.  Those
+// start 2, 4, 6 or 0 bytes past an 8-byte boundary (the blocks' 2-byte phase alternates), the same
+// for every lane of the k-step: aligned 8-byte reads and a byte shift, as stage_frags<Q8_0>.  The
+// block whose bytes end the image (8h + 56: phase 0) reads nothing past them.
+// One fp16 rounding per weight: fp16 d times the exact code (1024 + nibble - 1032).
+__device__ __forceinline__ void q4_0_frags(const uint8_t *img, int g, int u, f16x8 (&frag)[2])
+{
+    const int h = u >> 1;
+    const h2 bias = splat(-1032.f); // 1024 + 8
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+        const int blk = 8 * h + 18 * (2 * (u & 1) + n);
+        const h2 d = splat(h2f(*(const uint16_t *)(img + blk)));
+        const int off = blk + 2, sh = off & 7;
+        const uint8_t *al = img + (off & ~7) + 8 * (g & 1);
+        const u32x2 lo = *(const u32x2 *)al;
+        u32x2 q = lo;
+        if (sh != 0) {
+            const u32x2 hi = *(const u32x2 *)(al + 8);
+            if (sh < 4) q = (u32x2){__builtin_amdgcn_alignbyte(lo.y, lo.x, sh), __builtin_amdgcn_alignbyte(hi.x, lo.y, sh)};
+            else if (sh == 4) q = (u32x2){lo.y, hi.x};
+            else q = (u32x2){__builtin_amdgcn_alignbyte(hi.x, lo.y, sh - 4), __builtin_amdgcn_alignbyte(hi.y, hi.x, sh - 4)};
+        }
+        const int s4 = 4 * (g >> 1);
+        const uint32_t c0 = (q.x >> s4) & 0x0f0f0f0fu, c1 = (q.y >> s4) & 0x0f0f0f0fu;
+        frag[n] = frag4((pair02(c0) + bias) * d, (pair13(c0) + bias) * d, (pair02(c1) + bias) * d,
+                        (pair13(c1) + bias) * d);
+    }
+}
+
 // Q6_K sub-stage s4 = (h, v): k-step 0 = elements 128h+32v+[0,32) (ql[64h+32v..] low nibbles,
 // qh bits 2v), k-step 1 = 128h+64+32v+[0,32) (same ql bytes, high nibbles; qh bits 4+2v).
 template <>

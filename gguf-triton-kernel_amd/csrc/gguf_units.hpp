@@ -10,6 +10,7 @@
 //          qs bytes 32((u%4)/2)..+31 at shifts 4(u%2) and 4(u%2)+2, the 12 scale bytes and d
 //   Q2_K : super-block u/4, elements 64(u%4)+[0,64): qs bytes 32((u%4)/2)..+31 at shifts 4(u%2)
 //          and 4(u%2)+2, the four scale bytes 4(u%4)..+3, d and dmin (one dword)
+//   Q4_0 : blocks 2u, 2u+1 (bytes 36u .. 36u+35 of the row)
 // so two consecutive units (2c, 2c+1) tile K-chunk c of 128 elements.  Every unit needs
 // 16-byte loads only (Q8_0/Q6_K fields are 2-byte aligned: unaligned dwordx4, which
 // gfx950 serves in unaligned mode).  act_blocks() gives the two 32-element activation
@@ -108,6 +109,69 @@ template <> struct UnitRaw<Q8_0> {
             r.w[4 * i + 2] = v[i].z;
             r.w[4 * i + 3] = v[i].w;
         }
+        return r;
+    }
+};
+
+// ---- Q4_0: two blocks (36 bytes at 36u; activation blocks 2u, 2u+1) ----
+// Every read ends with its own block: the tensor's last block ends the allocation unharmed.
+template <> struct UnitLoad<Q4_0> {
+    uint32_t d0b, d1b;
+    u32x4 a0, a1; // qs bytes of block 2u and of block 2u+1
+    __device__ __forceinline__ void load(const uint8_t *__restrict__ rowp, int u, int64_t nb32)
+    {
+        // unconditional loads, as Q8_0's: a missing second block re-reads the first (its d is zeroed later)
+        const uint8_t *p = rowp + 36 * (int64_t)u;
+        const bool has0 = 2 * (int64_t)u < nb32, has1 = 2 * (int64_t)u + 1 < nb32;
+        const uint8_t *p0 = has0 ? p : rowp, *p1 = has1 ? p + 18 : p0;
+        d0b = ld2(p0);
+        d1b = ld2(p1);
+        a0 = ld16(p0 + 2);
+        a1 = ld16(p1 + 2);
+    }
+    // from LDS (the decode ring): the block pair as 9 dword-aligned words (36u is a multiple of 4;
+    // rows of K % 64 == 0 start 4-byte aligned there), the first block's codes shifted into place;
+    // a missing second block reads bytes of no consequence (its d is zeroed)
+    __device__ __forceinline__ void load_lds(const uint8_t *__restrict__ rowp, int u, int64_t /*nb32*/)
+    {
+        const uint32_t *w = (const uint32_t *)(rowp + 36 * u);
+        uint32_t x[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) x[k] = w[k];
+        d0b = x[0] & 0xffffu;
+        d1b = x[4] >> 16;
+        uint32_t c[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) c[k] = __builtin_amdgcn_alignbyte(x[k + 1], x[k], 2);
+        a0 = (u32x4){c[0], c[1], c[2], c[3]};
+        a1 = (u32x4){x[5], x[6], x[7], x[8]};
+    }
+};
+
+// UnitRaw<Q8_0>'s fields (dot_unit's Q8_0 branch serves both): the nibbles signed in registers.
+// n = four nibbles, one per byte: ((n | 0x80808080) - 0x08080808) ^ 0x80808080 is n - 8 per byte as
+// int8 -- every byte of the minuend is at least 0x80, so no subtraction borrows from its neighbour
+template <> struct UnitRaw<Q4_0> {
+    float d0, d1;
+    uint32_t w[16]; // int8 codes q - 8: w[0..7] block 2u (low nibbles, then high), w[8..15] block 2u+1
+
+    __device__ __forceinline__ static uint32_t signed4(uint32_t n)
+    {
+        return ((n | 0x80808080u) - 0x08080808u) ^ 0x80808080u;
+    }
+    __device__ __forceinline__ static UnitRaw from(const UnitLoad<Q4_0> &l, int u, int64_t nb32)
+    {
+        UnitRaw r;
+        r.d0 = 2 * (int64_t)u < nb32 ? h2f(l.d0b) : 0.f;
+        r.d1 = 2 * (int64_t)u + 1 < nb32 ? h2f(l.d1b) : 0.f;
+        const uint32_t q[8] = {l.a0.x, l.a0.y, l.a0.z, l.a0.w, l.a1.x, l.a1.y, l.a1.z, l.a1.w};
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                r.w[8 * b + i] = signed4(q[4 * b + i] & 0x0f0f0f0fu);
+                r.w[8 * b + 4 + i] = signed4((q[4 * b + i] >> 4) & 0x0f0f0f0fu);
+            }
         return r;
     }
 };

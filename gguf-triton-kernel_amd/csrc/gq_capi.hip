@@ -145,8 +145,9 @@ struct TypeInfo {
     int quant_kind;
 };
 constexpr TypeInfo kTypes[] = {{"Q8_0", "q8_0", 0},  {"Q4_K", "q4_k", 1},  {"Q6_K", "q6_k", 2},
-                               {"Q5_K", "q5_k", -1}, {"Q3_K", "q3_k", -1}, {"Q2_K", "q2_k", -1}};
-static_assert(GQ_Q8_0 == 0 && GQ_Q4_K == 1 && GQ_Q6_K == 2 && GQ_Q5_K == 3 && GQ_Q3_K == 4 && GQ_Q2_K == 5 &&
+                               {"Q5_K", "q5_k", -1}, {"Q3_K", "q3_k", -1}, {"Q2_K", "q2_k", -1},
+                               {"Q4_0", "q4_0", 4}};
+static_assert(GQ_Q8_0 == 0 && GQ_Q4_K == 1 && GQ_Q6_K == 2 && GQ_Q5_K == 3 && GQ_Q3_K == 4 && GQ_Q2_K == 5 && GQ_Q4_0 == 6 &&
                   sizeof(kTypes) / sizeof(kTypes[0]) == kNumFmts,
               "kTypes and kFmt are indexed by gq_type");
 bool known_type(int t) { return known_fmt(t); }
@@ -159,7 +160,7 @@ size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 // Decode path up to this many tokens; beyond it the fp16-MFMA GEMM.
 constexpr int64_t kGemvMaxTokens = 4; // 5..8 tokens: the MFMA GEMM (15.9 us at 16 tokens vs 22.3 us decode at 8, Q4_K 4096^2)
 
-// (K % 128 != 0 is only possible for Q8_0, so the choice depends on N and K alone and
+// (K % 128 != 0 is only possible for Q8_0 and Q4_0, so the choice depends on N and K alone and
 // gq_act_prepare, which does not know the weight type, makes the same one.)
 bool use_gemv(int64_t N, int64_t K) { return N <= kGemvMaxTokens || !gemm_supported(Q8_0, K); }
 
@@ -306,7 +307,7 @@ constexpr int64_t kSgemmMinTokens = 17, kSgemmQ6MinTokens = 5;
 bool use_sgemm(int t, int form, int64_t M, int64_t N, int64_t K, const Tuning &u)
 {
     if (form != AF_F16 || use_gemv(N, K) || use_blas(N, K, u) || K % 256 != 0) return false;
-    // Q5_K's, Q3_K's and Q2_K's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
+    // Q5_K's, Q3_K's, Q2_K's and Q4_0's only GEMM kernel: every 5..BLAS-threshold token count, whatever GQ_SGEMM or a pinned
     // knob of the other GEMMs says; rows over the per-launch limit are cut into chunks
     if (q8_1_only(t)) {
         // the call's tokens go into every launch (rows alone are cut).  Counted as the other GEMMs
@@ -506,7 +507,7 @@ Plan plan_call(const Call &c, const Tuning &u)
     } else if (sgemm) {
         p.kernel = streamk ? K_SGEMM_STREAMK : K_SGEMM;
         if (!streamk) p.rg = sg;
-    } else if (!q8_1_only(t)) { // (Q5_K / Q3_K / Q2_K: the streaming GEMM or nothing, GQ_EUNSUPPORTED)
+    } else if (!q8_1_only(t)) { // (Q5_K / Q3_K / Q2_K / Q4_0: the streaming GEMM or nothing, GQ_EUNSUPPORTED)
         p.kernel = K_GEMM;
         if (!c.prepared && act == GQ_ACT_Q8_1 && p.form == AF_F16 && p.rows >= M && p.toks >= N) {
             // 16/32-token tiles whose split fits LDS: the GEMM quantizes the activations itself (no
@@ -739,7 +740,7 @@ static int check_act(int act, int64_t K)
 }
 
 // The shape checks every MMQ entry starts with, in this order: the type and the sizes, the
-// activation format, and the pair (Q5_K, Q3_K and Q2_K run with q8_1 activations only)
+// activation format, and the pair (Q5_K, Q3_K, Q2_K and Q4_0 run with q8_1 activations only)
 static int check_mmq_shape(gq_type t, int act, int64_t M, int64_t N, int64_t K)
 {
     int rc = check_common(t, M, N, K);
@@ -1116,8 +1117,8 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
             // (the grouped launch's own route: the stream wherever it applies, GQ_KSTREAM=0 refuses)
             if (!gq::grouped_kstream_item(d.fmt, act, d.M, N, d.K, d.ldx, d.ldc, false, gq::tuning()) ||
                 gq::kstream_splits(d.K) > 1 || d.ldx % 8 != 0 || ((uintptr_t)d.X & 15) != 0)
-                return fail(GQ_EUNSUPPORTED, "item %d: not a grouped K-chunked-stream shape (N=%lld, M=%lld, K=%lld)", i,
-                            (long long)N, (long long)d.M, (long long)d.K);
+                return fail(GQ_EUNSUPPORTED, "item %d (%s): not a grouped K-chunked-stream shape (N=%lld, M=%lld, K=%lld)", i,
+                            gq::type_info(d.fmt).name, (long long)N, (long long)d.M, (long long)d.K);
             ki[i] = gq::KItem{d.fmt, d.A, d.X, d.ldx, d.C, d.ldc, d.M, d.K};
         }
         // (no K ranges)

@@ -35,6 +35,9 @@
 #ifndef GQ_Q3_LDS_PLAIN
 #define GQ_Q3_LDS_PLAIN 1 // Q3_K ring reads: 1 plain 2-byte aligned (measured faster), 0 dword-aligned (lds_words)
 #endif
+#ifndef GQ_Q40_LDS_PLAIN
+#define GQ_Q40_LDS_PLAIN 0 // Q4_0 ring reads: 0 dword-aligned words and a shift (Q8_0's form), 1 plain 2-byte aligned
+#endif
 #ifndef GQ_DECODE_NT
 #define GQ_DECODE_NT 1 // weight DMAs with the non-temporal policy (bytes read exactly once)
 #endif
@@ -107,7 +110,8 @@ struct DecodeGeom {
 template <int F>
 __device__ __forceinline__ uint32_t unit_byte(int u, int nb32)
 {
-    if constexpr (F == Q8_0) return 34u * (uint32_t)(2 * u < nb32 ? 2 * u : nb32);
+    if constexpr (Layout<F>::QK == 32) // (Q8_0, Q4_0: a row may end with half a unit)
+        return (uint32_t)Layout<F>::BYTES * (uint32_t)(2 * u < nb32 ? 2 * u : nb32);
     return (uint32_t)Layout<F>::BYTES * (uint32_t)(u >> 2);
 }
 
@@ -209,7 +213,7 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     float *sd = (float *)(codes + NT * kp * (FP8 ? 2 : 1)); // FP8: quarter sums [NT][2*nb]
     float *sx = sd + NT * nb; // Q4_K / Q5_K: s [NT][nb] (float); Q6_K / Q3_K / Q2_K: code sums [NT][2*nb] (int)
     static_assert(!FP8 || NT == 1 || ITC == 0, "fp8 decode: cached activations at one token only");
-    static_assert(!FP8 || (F != Q5_K && F != Q3_K && F != Q2_K), "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
+    static_assert(!FP8 || !q8_1_only(F), "the fp8 variant has no Q5_K / Q3_K / Q2_K / Q4_0 form");
     // FP8 at 2+ tokens: exact code pairs, no quarter sums (gguf_dot.hpp dot_unit_h NS; act_lds)
     constexpr bool F8NS = FP8 && NT >= 2;
     // FP8: x~ 16-byte piece P of a token row at piece P ^ ((P >> 4) & 7) (the lanes of a unit
@@ -532,8 +536,10 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
         // 2-byte aligned): plain reads as Q6_K's packed ring -- the dword-aligned form
         // (UnitLoad<Q3_K>::load_lds, -DGQ_Q3_LDS_PLAIN=0) measured 0.4-1.0 us slower at one token
         // (4096^2 6.31 vs 6.68 us, 11008x4096 11.91 vs 12.89, 4096x11008 11.49 vs 12.15);
-        // Q2_K (84-byte blocks, 4-byte aligned): plain reads too, two 16-byte and two 4-byte per unit
-        if constexpr (F == Q8_0 || (F == Q3_K && !GQ_Q3_LDS_PLAIN)) l.load_lds(rowp, u, nb);
+        // Q2_K (84-byte blocks, 4-byte aligned): plain reads too, two 16-byte and two 4-byte per unit;
+        // Q4_0 (18-byte blocks, 36-byte units): Q8_0's form, nine aligned dwords and a 2-byte shift
+        // (-DGQ_Q40_LDS_PLAIN=1: the GEMV's 2-byte aligned 16-byte reads, A/B builds)
+        if constexpr (F == Q8_0 || (F == Q4_0 && !GQ_Q40_LDS_PLAIN) || (F == Q3_K && !GQ_Q3_LDS_PLAIN)) l.load_lds(rowp, u, nb);
         else if constexpr (IMG) l.load_img(rowp, u);
         else l.load(rowp, u, nb);
 #endif
@@ -862,23 +868,36 @@ struct GroupedArgs {
 // keep their case sets): SET = 1's cases and Q3_K's, at one token up to kQ3GroupItc cached chunks.
 // SET = 3: the launch holds a Q2_K item.  A fourth kernel for the same reason: SET = 2's cases (a
 // Q2_K file's layer holds Q3_K items too) and Q2_K's, at one token up to kQ2GroupItc cached chunks.
+// SET = 4: the launch holds a Q4_0 item.  A fifth kernel: SET = 0's cases (Q8_0, Q4_K, Q6_K -- a
+// Q4_0 file's other tensors) and Q4_0's; at one token every format up to kQ40GroupItc cached chunks
+// (with every type's own cap, 34 cases, the allocator spills 1512 bytes per lane).  It carries no
+// Q5_K / Q3_K / Q2_K case (kGroupHas): decode_grouped_ok refuses such a mix and the caller runs the
+// items alone.
 #ifndef GQ_Q3_GROUP_ITC
 #define GQ_Q3_GROUP_ITC 3
 #endif
 #ifndef GQ_Q2_GROUP_ITC
 #define GQ_Q2_GROUP_ITC 3
 #endif
+#ifndef GQ_Q40_GROUP_ITC
+#define GQ_Q40_GROUP_ITC 5
+#endif
 constexpr int kQ5GroupItc = 4, kQ3GroupItc = GQ_Q3_GROUP_ITC, kQ2GroupItc = GQ_Q2_GROUP_ITC;
+constexpr int kQ40GroupItc = GQ_Q40_GROUP_ITC;
 // the one-token cap of every item in a launch of case set 1.. (set 0 carries every type's own cap)
-constexpr int kGroupItc[] = {7, kQ5GroupItc, kQ3GroupItc, kQ2GroupItc};
-constexpr int kGroupSets = 4;
+constexpr int kGroupItc[] = {7, kQ5GroupItc, kQ3GroupItc, kQ2GroupItc, kQ40GroupItc};
+constexpr int kGroupSets = 5;
+// bit g: the set's kernel carries the cases of the types whose FmtInfo::group_set is g
+constexpr unsigned kGroupHas[kGroupSets] = {0x01, 0x03, 0x07, 0x0f, 0x11};
+static_assert(kQ40Itc1 <= 7 && kQ40Itc2 <= 4 && kQ40GroupItc <= 6, "stream_decode_grouped_kernel carries no further Q4_0 cases");
 // (the case lists below are written out by hand: GroupedProblem::code holds itc <= 7, and the
 // two-token lists end at Q3_K's 3)
 static_assert(kQ2Itc1 <= 7 && kQ2Itc2 <= 3, "stream_decode_grouped_kernel carries no further Q2_K cases");
 template <int NT, int FP8 = 0, int SET = 0>
 __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const GroupedArgs args)
 {
-    static_assert(!(FP8 && SET), "the fp8 variant has no Q5_K / Q3_K / Q2_K form");
+    static_assert(!(FP8 && SET), "the fp8 variant has no Q5_K / Q3_K / Q2_K / Q4_0 form");
+    constexpr bool S5 = SET >= 1 && SET <= 3, S3 = SET >= 2 && SET <= 3; // the set carries Q5_K's / Q3_K's cases
     extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
     const int b = (int)blockIdx.x;
     int i = 0;
@@ -908,6 +927,22 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GF(Q8_0, 0, 0) GQ_GF(Q4_K, 0, 0) GQ_GF(Q6_K, 0, 0) GQ_GF(Q6_K, 0, 1)
         default: return;
         }
+    } else if constexpr (NT == 1 && SET == 4) { // (kQ40GroupItc)
+#define GQ_G40(itc) GQ_GB(Q8_0, itc) GQ_GB(Q4_K, itc) GQ_GB(Q6_K, itc) GQ_GBI(itc) GQ_GB(Q4_0, itc)
+        switch (q.code) {
+            GQ_G40(0) GQ_G40(1) GQ_G40(2) GQ_G40(3)
+#if GQ_Q40_GROUP_ITC >= 4
+            GQ_G40(4)
+#endif
+#if GQ_Q40_GROUP_ITC >= 5 // (Q6_K's own cap is 4)
+            GQ_GB(Q8_0, 5) GQ_GB(Q4_K, 5) GQ_GB(Q4_0, 5)
+#endif
+#if GQ_Q40_GROUP_ITC >= 6
+            GQ_GB(Q8_0, 6) GQ_GB(Q4_K, 6) GQ_GB(Q4_0, 6)
+#endif
+        default: return;
+        }
+#undef GQ_G40
     } else if constexpr (NT == 1 && SET == 3) { // (kQ2GroupItc)
 #define GQ_G2(itc) GQ_GB(Q8_0, itc) GQ_GB(Q4_K, itc) GQ_GB(Q6_K, itc) GQ_GBI(itc) GQ_GB(Q5_K, itc) GQ_GB(Q3_K, itc) GQ_GB(Q2_K, itc)
         switch (q.code) {
@@ -931,7 +966,7 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
         default: return;
         }
 #undef GQ_G3
-    } else if constexpr (NT == 1 && SET) { // (kQ5GroupItc)
+    } else if constexpr (NT == 1 && S5) { // (kQ5GroupItc)
         switch (q.code) {
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q8_0, 2) GQ_GB(Q8_0, 3) GQ_GB(Q8_0, 4) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1)
             GQ_GB(Q4_K, 2) GQ_GB(Q4_K, 3) GQ_GB(Q4_K, 4) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GB(Q6_K, 2) GQ_GB(Q6_K, 3)
@@ -953,11 +988,18 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GB(Q4_K, 2) GQ_GB(Q4_K, 3) GQ_GB(Q4_K, 4) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GBI(0) GQ_GBI(1)
         default: break;
         }
-        if constexpr (SET) switch (q.code) {
+        if constexpr (S5) switch (q.code) {
             GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1) GQ_GB(Q5_K, 2) GQ_GB(Q5_K, 3) GQ_GB(Q5_K, 4)
         default: break;
         }
-        if constexpr (SET >= 2) switch (q.code) { // (kQ3Itc2)
+        if constexpr (SET == 4) switch (q.code) { // (kQ40Itc2)
+            GQ_GB(Q4_0, 0) GQ_GB(Q4_0, 1) GQ_GB(Q4_0, 2) GQ_GB(Q4_0, 3)
+#if GQ_Q40_ITC2 >= 4
+            GQ_GB(Q4_0, 4)
+#endif
+        default: break;
+        }
+        if constexpr (S3) switch (q.code) { // (kQ3Itc2)
             GQ_GB(Q3_K, 0) GQ_GB(Q3_K, 1) GQ_GB(Q3_K, 2) GQ_GB(Q3_K, 3)
         default: break;
         }
@@ -970,11 +1012,15 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
             GQ_GB(Q8_0, 0) GQ_GB(Q8_0, 1) GQ_GB(Q4_K, 0) GQ_GB(Q4_K, 1) GQ_GB(Q6_K, 0) GQ_GB(Q6_K, 1) GQ_GBI(0) GQ_GBI(1)
         default: break;
         }
-        if constexpr (SET) switch (q.code) {
+        if constexpr (S5) switch (q.code) {
             GQ_GB(Q5_K, 0) GQ_GB(Q5_K, 1)
         default: break;
         }
-        if constexpr (SET >= 2) switch (q.code) {
+        if constexpr (SET == 4) switch (q.code) {
+            GQ_GB(Q4_0, 0) GQ_GB(Q4_0, 1)
+        default: break;
+        }
+        if constexpr (S3) switch (q.code) {
             GQ_GB(Q3_K, 0) GQ_GB(Q3_K, 1)
         default: break;
         }
@@ -1112,6 +1158,8 @@ bool decode_grouped_ok(const DecodeItem *items, int n, int64_t N, bool fp8)
     if (set > 0) {
         if (fp8) return false;
         for (int i = 0; i < n; ++i) {
+            // (a Q4_0 item beside a Q5_K, Q3_K or Q2_K one: no kernel carries both)
+            if (!(kGroupHas[set] >> fmt_info(items[i].fmt).group_set & 1u)) return false;
             Pick p;
             if (!pick(items[i].fmt, items[i].M, N, items[i].K, p)) return false;
             if (p.nt == 1 && p.itc > kGroupItc[set]) return false;

@@ -7,6 +7,7 @@
 //   Q5_K w = (d*sc_j)*q - (dmin*m_j), q = 0..31    (no reference: include/gguf_quant.h)
 //   Q3_K w = (d*sc_{e/16})*q, q = -4..3, sc = -32..31 (no reference: include/gguf_quant.h)
 //   Q2_K w = (d*sc_{e/16})*q - dmin*m_{e/16}, q = 0..3, sc, m = 0..15 (no reference: include/gguf_quant.h)
+//   Q4_0 w = d*(q - 8), q = 0..15                   (no reference: include/gguf_quant.h)
 // one thread per 32-element sub-block, 4 x 16-byte stores.  PERM stores each 4-element group
 // in the order (0,2,1,3) -- the order act_quant's DEQ form uses for x~ -- so a GEMM over
 // (W_perm, x~) sums the same products as over the natural order.
@@ -64,6 +65,19 @@ __global__ __launch_bounds__(256) void dequant_kernel(const uint8_t *__restrict_
         const uint32_t qw[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
 #pragma unroll
         for (int i = 0; i < 32; ++i) w[i] = d * (float)(int8_t)byte_of(qw[i >> 2], i & 3);
+    } else if constexpr (F == Q4_0) {
+        // block j: elements 0..15 the low nibbles of qs[0..15], 16..31 the high ones; d*(q - 8) is
+        // exact in fp32; the 16-byte load ends with the block
+        const uint8_t *b = rowp + 18 * j;
+        const float d = h2f(ld2(b));
+        const u32x4 q0 = ld16(b + 2);
+        const uint32_t qw[4] = {q0.x, q0.y, q0.z, q0.w};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t by = byte_of(qw[i >> 2], i & 3);
+            w[i] = d * (float)((int)(by & 0xf) - 8);
+            w[16 + i] = d * (float)((int)(by >> 4) - 8);
+        }
     } else if constexpr (F == Q4_K) {
         const uint8_t *b = rowp + 144 * (j >> 3);
         const int s = (int)(j & 7);

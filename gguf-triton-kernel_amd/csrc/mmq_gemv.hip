@@ -86,7 +86,7 @@ template <int F>
 hipError_t launch_fmt(const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C, int64_t M,
                       int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    // rows per wave (profiles/r02/gemv_rows_tune.txt): 1-2 tokens Q8_0 4, Q4_K / Q6_K 2 (Q5_K, Q3_K, Q2_K as Q4_K)
+    // rows per wave (profiles/r02/gemv_rows_tune.txt): 1-2 tokens Q8_0 4, Q4_K / Q6_K 2 (Q5_K, Q3_K, Q2_K, Q4_0 as Q4_K)
     // (Q4_K 4096x28672 x2 30.3 -> 23.9 us, Q6_K 8192x28672 x2 64.9 -> 58.3); 3-4 tokens 2,
     // Q6_K 4 (x4 81.7 -> 72.9)
     const int r = N <= 2 ? (F == Q8_0 ? 4 : 2) : (F == Q6_K ? 4 : 2);

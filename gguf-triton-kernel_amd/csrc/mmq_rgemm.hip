@@ -92,6 +92,9 @@ constexpr int kSpol = 16; // split-K partial stores write-through (sc1)
 //         in-block piece gives Q4_K's conflict-free 80-B stride instead of an XOR placement of the
 //         four (hpos_swz): 25% more weight DMA instructions, no address arithmetic in the reads
 //         (the 64-B image was not built; streaming GEMM only)
+//   Q4_0  5 pieces from byte 64h of the 144-byte group of eight blocks (blocks 4h..4h+3, 72 bytes
+//         from group byte 72h, at image byte 8h; the h = 1 pieces end at byte 143, inside the
+//         group).  Q4_K's conflict-free 80-B stride, no padding piece (streaming GEMM only)
 //   Q6_K  8 pieces: ql 64h.. (4), qh 128+32h.. (2), bytes 192..207 (scales), 194..209 (d at image
 //         byte 126); a 128-B stride is 2 bank sets, so row r's pieces are XOR-permuted by r & 7
 //         (hpos_swz).  (Until round 5 a ninth padding piece made the stride 144 B instead; the 8
@@ -102,6 +105,7 @@ template <> struct HImg<Q4_K> { static constexpr int NPH = 5; };
 template <> struct HImg<Q5_K> { static constexpr int NPH = 7; };
 template <> struct HImg<Q3_K> { static constexpr int NPH = 5; };
 template <> struct HImg<Q2_K> { static constexpr int NPH = 5; };
+template <> struct HImg<Q4_0> { static constexpr int NPH = 5; };
 #ifndef GQ_Q6_NPH
 #define GQ_Q6_NPH 8 // (-DGQ_Q6_NPH=9: the padded image, A/B builds)
 #endif
@@ -119,6 +123,7 @@ template <int F> __device__ __forceinline__ uint32_t hsrc(int h, int pc)
     if constexpr (F == Q5_K) return pc < 3 ? 16u * pc : 48u + 64u * h + 16u * (pc - 3);
     if constexpr (F == Q3_K) return pc < 2 ? 16u * pc : (pc < 4 ? 32u + 32u * h + 16u * (pc - 2) : 94u);
     if constexpr (F == Q2_K) return pc == 0 || pc == 4 ? 0u : (pc < 3 ? 16u + 32u * h + 16u * (pc - 1) : 68u);
+    if constexpr (F == Q4_0) return 64u * h + 16u * pc;
     return pc < 4 ? 64u * h + 16u * pc : (pc < 6 ? 128u + 32u * h + 16u * (pc - 4) : (pc == 6 ? 192u : 194u));
 }
 
@@ -188,6 +193,7 @@ template <int F> __device__ __forceinline__ void half_frags(const uint8_t *img, 
     else if constexpr (F == Q5_K) q5k_frags(img, img + 16, img + 48 + 32 * (u & 1), g, u, frag);
     else if constexpr (F == Q3_K) q3k_frags(img, g, u, frag);
     else if constexpr (F == Q2_K) q2k_frags(img, g, u, frag);
+    else if constexpr (F == Q4_0) q4_0_frags(img, g, u, frag);
     else if constexpr (HImg<F>::NPH == 8) q6k_half_frags_swz(img, g, h, u & 1, hpos_swz<F>(r), frag);
     else q6k_half_frags(img, g, h, u & 1, frag);
 }
@@ -1037,6 +1043,7 @@ template <int NB> constexpr int max_slds()
     static_assert(SCfg<Q5_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q5_K within the others' LDS");
     static_assert(SCfg<Q3_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q3_K within the others' LDS");
     static_assert(SCfg<Q2_K, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q2_K within the others' LDS");
+    static_assert(SCfg<Q4_0, NB>::LDS <= (a > b ? (a > c ? a : c) : (b > c ? b : c)), "Q4_0 within the others' LDS");
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
 }
 
@@ -1044,8 +1051,10 @@ template <int NB> constexpr int max_slds()
 // SET = 1: the launch holds a Q3_K part.  A kernel of its own: the Q3_K body beside the others
 // raised sgemm_grouped_kernel<8>'s registers (185 -> 195), so the other formats' launches keep
 // the kernel they had.  SET = 2: the launch holds a Q2_K part -- a third kernel for the same
-// reason, with Q3_K's body too (a Q2_K file's layers hold both).
-constexpr int kSgemmSets = 3;
+// reason, with Q3_K's body too (a Q2_K file's layers hold both).  SET = 3: the launch holds a Q4_0
+// part -- a fourth kernel: Q4_0's body beside the base types' (Q8_0, Q4_K, Q6_K, Q5_K), neither
+// Q3_K's nor Q2_K's (plan_sgemm_grouped refuses such a mix: the caller runs the items alone).
+constexpr int kSgemmSets = 4;
 template <int NB, int SET = 0>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a);
 template <int NB, int SET = 0> int grouped_occ()
@@ -1059,7 +1068,12 @@ __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
     __shared__ __attribute__((aligned(1024))) uint8_t lds[max_slds<NB>()];
     const int b = (int)blockIdx.x;
     auto run = [&](const SPart &q, const TileId &id, int64_t sb0, int64_t sb1) __attribute__((always_inline)) {
-        if constexpr (SET != 0)
+        if constexpr (SET == 3)
+            if (q.fmt == Q4_0) {
+                sgemm_body<Q4_0, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
+                return;
+            }
+        if constexpr (SET == 1 || SET == 2)
             if (q.fmt == Q3_K) {
                 sgemm_body<Q3_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds);
                 return;
@@ -1082,7 +1096,7 @@ __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
             return;
         case Q6_K: sgemm_body<Q6_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
         case Q5_K: sgemm_body<Q5_K, NB>(q.A, q.X, q.C, q.P, q.M, a.N, q.K, q.ldc, a.spol, id, sb0, sb1, lds); return;
-        default: return; // (plan_sgemm_grouped admits the six formats only; Q3_K, Q2_K: above)
+        default: return; // (plan_sgemm_grouped admits the table's formats only; Q3_K, Q2_K, Q4_0: above)
         }
     };
     if (!a.streamk) { // tile-granular splits: workgroup = (part, tile, split)
@@ -1447,9 +1461,14 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
     g.nb = N > 64 ? 8 : (N > 32 ? 4 : (N > 16 ? 2 : 1));
     const int tn = (int)((N + 16 * g.nb - 1) / (16 * g.nb));
     int64_t units = 0, Lmax = 1;
+    int set_lo = kSgemmSets, set_hi = 0; // the smallest and the largest case set over the parts that name one
     for (int i = 0; i < n; ++i) {
         if (items[i].M < 1 || items[i].K < 256 || items[i].K % 256 != 0) return g;
         if (!known_fmt(items[i].fmt)) return g;
+        // (case set 3, Q4_0's kernel, carries neither Q3_K's nor Q2_K's body: not a grouped shape)
+        set_lo = std::min(set_lo, fmt_info(items[i].fmt).sgemm_set ? fmt_info(items[i].fmt).sgemm_set : kSgemmSets);
+        set_hi = std::max(set_hi, fmt_info(items[i].fmt).sgemm_set);
+        if (set_hi == 3 && set_lo < 3) return g;
         g.tiles_m[i] = (int)((items[i].M + RBM - 1) / RBM);
         const int64_t t = (int64_t)g.tiles_m[i] * tn, nsb = items[i].K / 256;
         units += t * nsb;
@@ -1570,7 +1589,8 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     const int nbi = g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3));
     static const int occ[kSgemmSets][4] = {{grouped_occ<1>(), grouped_occ<2>(), grouped_occ<4>(), grouped_occ<8>()},
                                            {grouped_occ<1, 1>(), grouped_occ<2, 1>(), grouped_occ<4, 1>(), grouped_occ<8, 1>()},
-                                           {grouped_occ<1, 2>(), grouped_occ<2, 2>(), grouped_occ<4, 2>(), grouped_occ<8, 2>()}};
+                                           {grouped_occ<1, 2>(), grouped_occ<2, 2>(), grouped_occ<4, 2>(), grouped_occ<8, 2>()},
+                                           {grouped_occ<1, 3>(), grouped_occ<2, 3>(), grouped_occ<4, 3>(), grouped_occ<8, 3>()}};
     const int oc = occ[set][nbi];
     a.ilc = g.streamk && tuning().rgemm_ilc != 0 && g.blocks <= num_cus() * oc ? 1 : 0;
     a.U = r.U = g.U;

@@ -12,6 +12,7 @@
 //   Q5_K: Q4_K's term over codes 0..31 (no reference counterpart)
 //   Q6_K: term = dB*((d*sc_lo)*dot_lo + (d*sc_hi)*dot_hi) in fp32
 //   Q3_K: Q6_K's term over codes -4..3 and 6-bit scales -32..31 (no reference counterpart)
+//   Q4_0: Q8_0's term on the block's Q8_0 image (the same d, codes nibble - 8; no reference counterpart)
 //   Q2_K (no reference counterpart), per q8_1 block, every operation one fp32 rounding, in this order:
 //         a_lo = d*sc_lo, a_hi = d*sc_hi, b_lo = dmin*m_lo, b_hi = dmin*m_hi   (exact)
 //         p  = a_lo*float(i_lo) + a_hi*float(i_hi)          (two products, then their sum)
@@ -77,6 +78,22 @@ void unpack_q8_0(const uint8_t *row, int64_t K, Row &r)
         const uint8_t *b = row + 34 * j;
         r.h[j] = ld16(b);
         std::memcpy(&r.q[32 * j], b + 2, 32);
+    }
+}
+
+// Q4_0: the block's Q8_0 image -- the same d, the int8 codes nibble - 8 in element order (low
+// nibbles are elements 0..15, high nibbles 16..31) -- so rows_q8_0 serves both
+void unpack_q4_0(const uint8_t *row, int64_t K, Row &r)
+{
+    const int64_t nb = K / 32;
+    for (int64_t j = 0; j < nb; ++j) {
+        const uint8_t *b = row + 18 * j;
+        r.h[j] = ld16(b);
+        int8_t *dst = &r.q[32 * j];
+        for (int i = 0; i < 16; ++i) {
+            dst[i] = (int8_t)((b[2 + i] & 0x0f) - 8);
+            dst[16 + i] = (int8_t)((b[2 + i] >> 4) - 8);
+        }
     }
 }
 
@@ -226,15 +243,18 @@ Act unpack_act(const uint8_t *B, int64_t N, int64_t K)
 }
 
 // C[m][n] (fp16 bits, (M, N) row-major) for rows [m0, m1)
+// (Q4 = true: Q4_0 rows -- Q8_0's terms, in its operation order, on the codes nibble - 8)
+template <bool Q4 = false>
 void rows_q8_0(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N, int64_t K, uint16_t *C)
 {
     const auto &T = half_table();
-    const int64_t nb = K / 32, row_bytes = nb * 34;
+    const int64_t nb = K / 32, row_bytes = nb * (Q4 ? 18 : 34);
     Row r;
     r.q.resize((size_t)K);
     r.h.resize((size_t)nb);
     for (int64_t m = m0; m < m1; ++m) {
-        unpack_q8_0(A + m * row_bytes, K, r);
+        if (Q4) unpack_q4_0(A + m * row_bytes, K, r);
+        else unpack_q8_0(A + m * row_bytes, K, r);
         for (int64_t n = 0; n < N; ++n) {
             const int8_t *xq = &x.q[n * K];
             const uint16_t *xd = &x.d[n * nb];
@@ -352,17 +372,18 @@ void rows_q2_k(const uint8_t *A, const Act &x, int64_t m0, int64_t m1, int64_t N
 extern "C" {
 
 // C (M, N) fp16 bits = the reference CPU MMQ of packed weights A (type 0 Q8_0, 1 Q4_K,
-// 2 Q6_K, 3 Q5_K, 4 Q3_K, 5 Q2_K) and packed q8_1 activations B.  threads <= 0: all hardware threads.
+// 2 Q6_K, 3 Q5_K, 4 Q3_K, 5 Q2_K, 6 Q4_0) and packed q8_1 activations B.  threads <= 0: all hardware threads.
 // Returns 0, or -1 for an unknown type / K not a whole number of blocks.
 int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int64_t K, uint16_t *C, int threads)
 {
-    const int qk = type == 0 ? 32 : 256;
-    if (type < 0 || type > 5 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
+    const int qk = type == 0 || type == 6 ? 32 : 256;
+    if (type < 0 || type > 6 || K <= 0 || K % qk != 0 || M < 0 || N < 0) return -1;
     if (M == 0 || N == 0) return 0;
     half_table();
     const Act x = unpack_act((const uint8_t *)B, N, K);
     auto run = [&](int64_t m0, int64_t m1) {
-        if (type == 0) rows_q8_0((const uint8_t *)A, x, m0, m1, N, K, C);
+        if (type == 0) rows_q8_0<false>((const uint8_t *)A, x, m0, m1, N, K, C);
+        else if (type == 6) rows_q8_0<true>((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 1) rows_q4_k<false>((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 3) rows_q4_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);
         else if (type == 4) rows_q6_k<true>((const uint8_t *)A, x, m0, m1, N, K, C);

@@ -89,6 +89,14 @@ void gq_quantize_q2_k(const float *x, void *y, int64_t n)
     });
 }
 
+// x: n fp32 values (n % 32 == 0), y: n/32 * 18 bytes (Q4_0: include/gguf_quant.h).
+void gq_quantize_q4_0(const float *x, void *y, int64_t n)
+{
+    parallel_blocks(n / 32, [&](int64_t b0, int64_t b1) {
+        for (int64_t b = b0; b < b1; ++b) q4_0_block(x + b * 32, (uint8_t *)y + b * 18);
+    });
+}
+
 // x: n fp32 values (n % 256 == 0), y: n/256 * 210 bytes.
 void gq_quantize_q6_k(const float *x, void *y, int64_t n)
 {
@@ -119,6 +127,19 @@ void gq_dequantize_q8_0(const void *y, float *out, int64_t nblocks)
     for (int64_t b = 0; b < nblocks; ++b, p += 34) {
         float d = h2f(get16(p));
         for (int i = 0; i < 32; ++i) out[32 * b + i] = d * (float)(int8_t)p[2 + i];
+    }
+}
+
+// d*(q - 8) in fp32: exact (an 11-bit significand times at most 4 bits)
+void gq_dequantize_q4_0(const void *y, float *out, int64_t nblocks)
+{
+    const uint8_t *p = (const uint8_t *)y;
+    for (int64_t b = 0; b < nblocks; ++b, p += 18) {
+        const float d = h2f(get16(p));
+        for (int i = 0; i < 16; ++i) {
+            out[32 * b + i] = d * (float)((p[2 + i] & 0x0f) - 8);
+            out[32 * b + 16 + i] = d * (float)((p[2 + i] >> 4) - 8);
+        }
     }
 }
 

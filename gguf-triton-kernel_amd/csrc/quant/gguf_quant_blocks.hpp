@@ -11,6 +11,7 @@
 //   q3k_block  (no reference; host only) q6k_block's search over codes -4..3, Q3_K packing
 //   q2k_block  (no reference; host only) q4k_block's scale / min fit per 16 elements over codes 0..3, Q2_K packing
 //   q8_block   <- utils/quantize/q8_0.py:4-49 (Q8_0), utils/quantize/q8_1.py:18-70 (Q8_1)
+//   q4_0_block (no reference; host and device) d = extreme / -8, codes by truncation of x/d + 8.5
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -470,6 +471,30 @@ GQ_QHD inline void q8_block(const uint16_t *x, uint8_t *blk)
     if (WITH_SUM) put16(blk + 2, f2h(h2f(d) * h2f(f2h((float)sum))));
 }
 
+// ---------------- Q4_0 ----------------
+// 32 weights in 18 bytes: fp16 d, then qs[16] (element j in the low nibble of qs[j], element 16 + j
+// in the high one); w = d*(q - 8).  The rule: m = the element of largest magnitude, sign kept;
+// d = m / -8, id = d ? 1/d : 0; q = min(15, (int)(x*id + 8.5f)) (x*id >= -8 up to a rounding, so the
+// truncation is a rounding to nearest and m itself gets code 0); d stored as fp16.
+GQ_QHD inline void q4_0_block(const float *x, uint8_t *blk)
+{
+    float amax = 0.f, mx = 0.f;
+    for (int i = 0; i < 32; ++i) {
+        const float v = x[i];
+        if (amax < std::fabs(v)) {
+            amax = std::fabs(v);
+            mx = v;
+        }
+    }
+    const float d = mx / -8.f;
+    const float id = d != 0.f ? 1.f / d : 0.f;
+    put16(blk, f2h(d));
+    for (int j = 0; j < 16; ++j) {
+        const float x0 = x[j] * id, x1 = x[16 + j] * id;
+        const int q0 = std::min(15, (int)(int8_t)(x0 + 8.5f)), q1 = std::min(15, (int)(int8_t)(x1 + 8.5f));
+        blk[2 + j] = (uint8_t)(q0 | (q1 << 4));
+    }
+}
 
 } // namespace qblk
 } // namespace gq

@@ -23,7 +23,7 @@ from .blocks import BLOCK
 GGUF_MAGIC = b"GGUF"
 # ggml type id -> (name, block elements, block bytes)
 GGML_TYPES = {0: ("f32", 1, 4), 1: ("f16", 1, 2)}
-GGML_TYPES.update({i: (f, *BLOCK[f]) for i, f in ((8, "q8_0"), (10, "q2_k"), (11, "q3_k"), (12, "q4_k"), (13, "q5_k"),
+GGML_TYPES.update({i: (f, *BLOCK[f]) for i, f in ((2, "q4_0"), (8, "q8_0"), (10, "q2_k"), (11, "q3_k"), (12, "q4_k"), (13, "q5_k"),
                                                   (14, "q6_k"))})
 TYPE_IDS = {v[0]: k for k, v in GGML_TYPES.items()}
 
@@ -36,7 +36,7 @@ _SCALAR = {_U8: "<B", _I8: "<b", _U16: "<H", _I16: "<h", _U32: "<I", _I32: "<i",
 @dataclass
 class GGUFTensor:
     name: str
-    type_name: str   # "q2_k", "q3_k", "q4_k", "q5_k", "q6_k", "q8_0", "f16", "f32"
+    type_name: str   # "q4_0", "q2_k", "q3_k", "q4_k", "q5_k", "q6_k", "q8_0", "f16", "f32"
     dims: tuple      # GGUF order: innermost (K) first
     offset: int      # from the start of the data section
     data: np.ndarray  # raw bytes (uint8 memmap)

@@ -1,4 +1,4 @@
-"""The Q4_K_M (and Q5_K_M, Q3_K_M, Q2_K) layer-type mix of a Llama block (BASELINE.json configs[4]).
+"""The Q4_K_M (and Q5_K_M, Q3_K_M, Q2_K, Q4_0) layer-type mix of a Llama block (BASELINE.json configs[4]).
 
 llama.cpp's Q4_K_M recipe (not in the reference): every weight Q4_K except attn_v and
 ffn_down, which are Q6_K on a subset of layers -- the first eighth, the last eighth and every
@@ -58,3 +58,13 @@ def q2_k_layer_types(layer: int, n_layers: int = 32, n_gqa: int = 1):
             return "q3_k"
         return "q2_k"
     return {name: one(name) for name in LLAMA_LAYER_SHAPES}
+
+
+def q4_0_layer_types(layer: int, n_layers: int = 32):
+    """{projection: gguf type} of layer `layer` under llama.cpp's Q4_0 file type: every projection
+    q4_0, whatever the layer.
+
+    llama.cpp's rule for Llama models, written here from memory (nothing here can check it against
+    llama.cpp; the token embedding and output tensors, which it may store in another type, are not
+    projections of a block)."""
+    return {name: "q4_0" for name in LLAMA_LAYER_SHAPES}

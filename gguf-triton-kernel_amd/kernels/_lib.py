@@ -17,11 +17,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(os.path.dirname(_HERE), "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libgguf_mmq.so")
 
-GQ_Q8_0, GQ_Q4_K, GQ_Q6_K, GQ_Q5_K, GQ_Q3_K, GQ_Q2_K = 0, 1, 2, 3, 4, 5
+GQ_Q8_0, GQ_Q4_K, GQ_Q6_K, GQ_Q5_K, GQ_Q3_K, GQ_Q2_K, GQ_Q4_0 = 0, 1, 2, 3, 4, 5, 6
 GQ_ACT_Q8_1, GQ_ACT_FP8_E4M3 = 0, 1
 ACTS = {"q8_1": GQ_ACT_Q8_1, "fp8": GQ_ACT_FP8_E4M3}
 TYPES = {"q8_0": GQ_Q8_0, "q4_k": GQ_Q4_K, "q6_k": GQ_Q6_K, "q5_k": GQ_Q5_K, "q3_k": GQ_Q3_K,
-         "q2_k": GQ_Q2_K}
+         "q2_k": GQ_Q2_K, "q4_0": GQ_Q4_0}
 BLOCK_ELEMS = {TYPES[f]: qk for f, (qk, _) in BLOCK.items()}
 BLOCK_BYTES = {TYPES[f]: nbytes for f, (_, nbytes) in BLOCK.items()}
 
@@ -557,7 +557,7 @@ def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N
 
 def quantize_weights_device(fmt: str, X: torch.Tensor) -> torch.Tensor:
     """GGUF weight quantization on the device (gq_quantize_weights): the bytes of
-    utils.quantize.quantize_to_<fmt> (int8, flat), from an fp16 (q8_0) or fp32 (q4_k, q6_k)
+    utils.quantize.quantize_to_<fmt> (int8, flat), from an fp16 (q8_0) or fp32 (q4_k, q6_k, q4_0)
     device tensor read as flat blocks."""
     want = torch.float16 if fmt == "q8_0" else torch.float32
     if not X.is_cuda or X.dtype != want:

@@ -35,7 +35,7 @@ def lib():
 def quantize(fmt: str, x: torch.Tensor) -> torch.Tensor:
     """Host quantization of any-shape x (numel % QK == 0) -> flat int8 CPU tensor."""
     qk, nbytes = BLOCK[fmt]
-    if fmt in ("q4_k", "q6_k", "q5_k", "q3_k", "q2_k"):
+    if fmt in ("q4_k", "q6_k", "q5_k", "q3_k", "q2_k", "q4_0"):
         arr = np.ascontiguousarray(x.detach().cpu().to(torch.float32).numpy().reshape(-1))
     else:
         arr = np.ascontiguousarray(x.detach().cpu().to(torch.float16).numpy().reshape(-1)).view(np.uint16)

@@ -3,7 +3,8 @@
 Random bytes are valid blocks for every format except where a byte pair is an fp16 scale,
 so those fields are overwritten with fp16(U(0.5, 1.5) * 2^-7); Q6_K's
 int8 sub-block scales and Q3_K's 6-bit ones stay uniformly random (including negative ones), as do
-Q2_K's 4-bit scales and mins (d at bytes 80..81, dmin at 82..83).  The kernels have
+Q2_K's 4-bit scales and mins (d at bytes 80..81, dmin at 82..83).  Q4_0 (d at bytes 0..1, as
+Q8_0) keeps its random nibbles: uniform over 0..15, so the codes -8 and +7 occur.  The kernels have
 no data-dependent control flow, so timings do not depend on the values.
 """
 from __future__ import annotations
@@ -25,7 +26,7 @@ def random_blocks(fmt: str, M: int, K: int, seed: int = 0) -> np.ndarray:
     rng = np.random.default_rng(seed)
     raw = rng.integers(0, 256, size=(nb, nbytes), dtype=np.uint8)
     u16 = raw.view(np.uint8)
-    if fmt == "q8_0":
+    if fmt in ("q8_0", "q4_0"):
         d = _scales(rng, nb)
         u16[:, 0] = d & 0xFF
         u16[:, 1] = d >> 8

@@ -63,7 +63,20 @@ extern "C" {
  * 5..32 tokens answer GQ_EUNSUPPORTED and launch nothing; gq_mmq_id and gq_mmq_id_sorted take it
  * under their limits.  gq_version() did not change with it: detect it by
  * gq_block_bytes(GQ_Q2_K) == 84 (a library without it answers 210). */
-typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3, GQ_Q3_K = 4, GQ_Q2_K = 5 } gq_type;
+/* GQ_Q4_0 (GGML type 2, block_q4_0; the reference has none): 32 weights in 18 bytes, little endian,
+ * rows of K/32 blocks without padding (blocks are 2-byte aligned; 256 weights are 144 bytes) --
+ *   [0:2] d fp16 | [2:18] qs[16]
+ * element j (0..15): q = qs[j] & 15; element 16 + j: q = qs[j] >> 4;  w = d*(q - 8), exact in fp32.
+ * The block is a Q8_0 block with the same d and the int8 codes q - 8 in element order; against q8_1
+ * activations it is Q8_0's expression on that image, per block d*dB*i with i = sum((q - 8)*qB) an
+ * exact int32 (not llama.cpp's d*(dB*sum(q*qB) - 8*s) with the activation block's fp16 s, which
+ * rounds differently).  K is any multiple of 32.
+ * As GQ_Q5_K, GQ_Q3_K and GQ_Q2_K: q8_1 activations only, gq_mmq_grouped[_ex] at 5..32 tokens
+ * answers GQ_EUNSUPPORTED and launches nothing; gq_mmq_id takes it at any K % 32 == 0 under its
+ * limits, gq_mmq_id_sorted and gq_mmq_grouped_prepared at K % 256 == 0.  Unlike them it has a
+ * device quantizer (gq_quantize_weights).  gq_version() did not change with it: detect it by
+ * gq_block_bytes(GQ_Q4_0) == 18 (a library without it answers 210). */
+typedef enum { GQ_Q8_0 = 0, GQ_Q4_K = 1, GQ_Q6_K = 2, GQ_Q5_K = 3, GQ_Q3_K = 4, GQ_Q2_K = 5, GQ_Q4_0 = 6 } gq_type;
 
 /* How the activations are quantized before the matmul.
  *   GQ_ACT_Q8_1      the reference's semantics: q8_1 (int8 per 32 elements, utils/quantize/q8_1.py).
@@ -82,7 +95,7 @@ enum {
     GQ_EUNSUPPORTED = 3 /* valid but not implemented (unknown type) */
 };
 
-/* Elements per block (32 / 256 / 256 / 256 / 256 / 256) and bytes per block (34 / 144 / 210 / 176 / 110 / 84). */
+/* Elements per block (32 / 256 / 256 / 256 / 256 / 256 / 32) and bytes per block (34 / 144 / 210 / 176 / 110 / 84 / 18). */
 int gq_block_elems(gq_type t);
 int gq_block_bytes(gq_type t);
 
@@ -162,7 +175,7 @@ int gq_act_prepare_grouped(gq_act act, const gq_prep_item *items, int n, void *s
  * Dequantize packed `t` weights to fp16: W[m * ldw + k] = w (the reference's block formulas,
  * utils/quantize/{q8_0,q4_k,q6_k}.py dequantize, evaluated in fp32, rounded once to fp16).
  * GQ_Q5_K: (d*sc_j)*q - (dmin*m_j), the formula above, in that order.  GQ_Q3_K: (d*sc)*q.
- * GQ_Q2_K: (d*sc)*q - (dmin*m), one rounding.
+ * GQ_Q2_K: (d*sc)*q - (dmin*m), one rounding.  GQ_Q4_0: d*(q - 8), exact in fp32.
  * M rows of K (a multiple of the block) elements.  gq_mmq uses the same kernel for its
  * library-GEMM path (N >= a few hundred tokens: fp16 W + hipBLASLt).
  */
@@ -187,6 +200,7 @@ int gq_quantize_fp8(const void *X, void *codes, void *scales, int64_t rows, int6
  *   GQ_Q8_0: X = n fp16 values (n % 32 == 0)  -> Y = n/32 blocks of 34 bytes (quantize_to_q8_0)
  *   GQ_Q4_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 144 bytes (quantize_to_q4_k)
  *   GQ_Q6_K: X = n fp32 values (n % 256 == 0) -> Y = n/256 blocks of 210 bytes (quantize_to_q6_k)
+ *   GQ_Q4_0: X = n fp32 values (n % 32 == 0)  -> Y = n/32 blocks of 18 bytes (gq_quantize_q4_0; no reference)
  * GQ_Q5_K, GQ_Q3_K, GQ_Q2_K: GQ_EUNSUPPORTED (host only: include/gguf_quant.h gq_quantize_q5_k / _q3_k / _q2_k).
  * X is read as flat blocks (a row-major (M, K) matrix gives the packed A of gq_mmq).  One thread
  * per block runs the host producer's exact code; no host sync.

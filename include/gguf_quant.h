@@ -26,6 +26,15 @@
  *   gq_dequantize_q2_k (d*sc)*q - (dmin*m) in fp32 (both products exact: one rounding)
  *   gq_cpu_mmq type 5  per q8_1 block dB*((d*sc_lo)*i_lo + (d*sc_hi)*i_hi)
  *                      - dB*((dmin*m_lo)*sigma_lo + (dmin*m_hi)*sigma_hi), the fp16 running sum
+ * and Q4_0 (GGML type 2; the layout in include/gguf_mmq.h) --
+ *   gq_quantize_q4_0   per 32 elements d = m / -8 with m the element of largest magnitude, sign kept;
+ *                      id = d ? 1/d : 0; code min(15, (int8)(x*id + 8.5f)); d stored as fp16.  This
+ *                      is llama.cpp's rule written from memory: nothing here can check it against
+ *                      llama.cpp (no byte contract).  The same code runs on the device
+ *                      (gq_quantize_weights(GQ_Q4_0)), byte for byte.
+ *   gq_dequantize_q4_0 d*(q - 8) in fp32 (exact)
+ *   gq_cpu_mmq type 6  Q8_0's terms, in its operation order, on the codes q - 8: bit for bit
+ *                      type 0 on the block's Q8_0 image
  */
 #ifndef GGUF_QUANT_H
 #define GGUF_QUANT_H
@@ -45,6 +54,8 @@ void gq_quantize_q5_k(const float *x, void *y, int64_t n);
 void gq_quantize_q3_k(const float *x, void *y, int64_t n);
 /* x: n fp32 (n % 256 == 0) -> y: n/256 blocks of 84 bytes (Q2_K) */
 void gq_quantize_q2_k(const float *x, void *y, int64_t n);
+/* x: n fp32 (n % 32 == 0) -> y: n/32 blocks of 18 bytes (Q4_0) */
+void gq_quantize_q4_0(const float *x, void *y, int64_t n);
 
 /* x: n fp16 bit patterns (n % 32 == 0) -> y: n/32 blocks of 34 (Q8_0) / 36 (Q8_1) bytes */
 void gq_quantize_q8_0(const uint16_t *x, void *y, int64_t n);
@@ -58,9 +69,10 @@ void gq_dequantize_q6_k(const void *y, float *out, int64_t nblocks);
 void gq_dequantize_q5_k(const void *y, float *out, int64_t nblocks);
 void gq_dequantize_q3_k(const void *y, float *out, int64_t nblocks);
 void gq_dequantize_q2_k(const void *y, float *out, int64_t nblocks);
+void gq_dequantize_q4_0(const void *y, float *out, int64_t nblocks);
 
 /* C (M, N) fp16 bits, row-major = the reference CPU MMQ of packed weights A (type 0 Q8_0,
- * 1 Q4_K, 2 Q6_K, 3 Q5_K, 4 Q3_K, 5 Q2_K; M rows of K) and packed q8_1 activations B (N rows of K).  threads <= 0:
+ * 1 Q4_K, 2 Q6_K, 3 Q5_K, 4 Q3_K, 5 Q2_K, 6 Q4_0; M rows of K) and packed q8_1 activations B (N rows of K).  threads <= 0:
  * every hardware thread (the result does not depend on it).  0 = OK, -1 = bad type or K. */
 int gq_cpu_mmq(int type, const void *A, const void *B, int64_t M, int64_t N, int64_t K, uint16_t *C, int threads);
 
