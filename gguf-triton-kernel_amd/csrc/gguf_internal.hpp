@@ -211,6 +211,21 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
                             int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc,
                             hipStream_t s);
 
+// Expert-indexed gate / up with SwiGLU (mmq_decode.hip; gq_mmq_id_glu): launch_decode_id's pairs,
+// grid and geometry on two expert tensors of one type and shape, one launch, one activation
+// prologue per workgroup.  With g and u the fp16 values launch_decode_id writes for a pair's row
+// from A_gate and A_up, H + p*ldh holds fp16(g / (1 + expf(-g)) * u), evaluated in fp32.
+// decode_id_glu_ok: decode_id_ok, and the waves' stash of g values fits the launch's LDS.
+bool decode_id_glu_ok(int fmt, int64_t M, int64_t pairs, int64_t K);
+hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const int32_t *ids, const uint16_t *B,
+                                uint16_t *H, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb,
+                                int64_t ldb_slot, int64_t ldh, hipStream_t s);
+
+// Router-weighted sum over slots (moe_combine.hip; gq_moe_combine): Y[n][m] = fp16(sum_s W[n*S+s] *
+// D[(n*S+s)*ldd + m]), the products and sums in fp32 in slot order, uncontracted; no atomics.
+hipError_t launch_moe_combine(const uint16_t *D, const void *W, bool w_f32, uint16_t *Y, int64_t N, int64_t S, int64_t M,
+                              int64_t ldd, int64_t ldy, hipStream_t s);
+
 // Sorted expert GEMM (gq_mmq_id_sorted; any pair count): three launches whose grids depend on
 // host-known sizes only.
 //   launch_id_sort (mmq_idsort.hip): one workgroup; perm[P] = the pair indices grouped by expert

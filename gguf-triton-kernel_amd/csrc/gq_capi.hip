@@ -1171,6 +1171,41 @@ int gq_mmq_id(gq_type t, const void *A, const int32_t *ids, const void *B, void 
                   "id decode");
 }
 
+int gq_mmq_id_glu(gq_type t, const void *A_gate, const void *A_up, const int32_t *ids, const void *B, void *H, int64_t E,
+                  int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldh, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    // gq_mmq_id's checks in its order (a null A_up counts as a null A)
+    const int rc = check_id_args(t, A_up ? A_gate : nullptr, ids, B, H, E, M, N, S, K, ldb, ldb_slot, ldh, empty);
+    if (rc != GQ_OK || empty) return rc;
+    if (N > gq::kMaxIdPairs || S > gq::kMaxIdPairs || !gq::decode_id_glu_ok(t, M, N * S, K) || E > INT32_MAX)
+        return fail(GQ_EUNSUPPORTED,
+                    "not an expert-indexed gate/up shape (N=%lld x S=%lld pairs, at most %d; K=%lld must fit the "
+                    "one-token decode; one expert < 2 GiB)",
+                    (long long)N, (long long)S, gq::kMaxIdPairs, (long long)K);
+    return hip_rc(gq::launch_decode_id_glu(t, (const uint8_t *)A_gate, (const uint8_t *)A_up, ids, (const uint16_t *)B,
+                                           (uint16_t *)H, E, M, N, S, K, ldb, ldb_slot, ldh, (hipStream_t)stream),
+                  "id glu decode");
+}
+
+int gq_moe_combine(const void *D, const void *W, int w_is_f32, void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd,
+                   int64_t ldy, void *stream)
+{
+    g_err.clear();
+    if (N < 0 || S < 0 || M < 0) return fail(GQ_EINVAL, "negative size N=%lld S=%lld M=%lld", (long long)N, (long long)S, (long long)M);
+    if (N == 0 || S == 0 || M == 0) return GQ_OK;
+    if (!D || !W || !Y) return fail(GQ_EINVAL, "null pointer (D=%p W=%p Y=%p)", D, W, Y);
+    if (ldd < M) return fail(GQ_EINVAL, "ldd=%lld < M=%lld", (long long)ldd, (long long)M);
+    if (ldy < M) return fail(GQ_EINVAL, "ldy=%lld < M=%lld", (long long)ldy, (long long)M);
+    if (S > gq::kMaxIdPairs || M > INT32_MAX)
+        return fail(GQ_EUNSUPPORTED, "not a combine shape (S=%lld, at most %d; M=%lld < 2^31)", (long long)S, gq::kMaxIdPairs,
+                    (long long)M);
+    return hip_rc(gq::launch_moe_combine((const uint16_t *)D, W, w_is_f32 != 0, (uint16_t *)Y, N, S, M, ldd, ldy,
+                                         (hipStream_t)stream),
+                  "moe combine");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

@@ -189,11 +189,22 @@ __device__ __forceinline__ void act_from_lds(Act<F, NT> &a, const uint8_t *codes
 // and widens them back (gguf_q8_1.hpp f8_quad: the bytes act_quant's F8DEQ form writes), the
 // LDS image is fp16 x~ + the x~ sums of every 16-element quarter, and the units multiply by
 // v_dot2_f32_f16 (gguf_dot.hpp dot_unit_h); no register cache of activations (ITC = 0).
-template <int F, int NT, int ITC, int IM = 0, int FP8 = 0>
+// GLU = 1 (stream_decode_id_glu_kernel, one token): two matrices A (gate) and A2 (up) of one type
+// and shape against the same activations, C = fp16(silu(g) * u) of their fp16 outputs g and u.
+// Every wave's task list is doubled -- task (row group, segment) of A, then the same task of A2,
+// through the same ring, the buffer resource chosen by the task's parity -- behind one activation
+// prologue.  The lane that would store a row's g keeps its fp16 bits in the wave's LDS stash
+// (stash_rows uint16 per wave from smem + stash_off, indexed by the row within the task) and, one
+// task later, the same lane holds the same row's u: it reads its own g back and stores the
+// product.  No lane reads another's entry, so no barrier.
+template <int F, int NT, int ITC, int IM = 0, int FP8 = 0, int GLU = 0>
 __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const uint16_t *__restrict__ X, int64_t ldx,
                                             uint16_t *__restrict__ C, int M, int64_t N, int K, int64_t ldc,
-                                            DecodeGeom geo, int bx, int gx, int by, uint8_t *smem)
+                                            DecodeGeom geo, int bx, int gx, int by, uint8_t *smem,
+                                            const uint8_t *__restrict__ A2 = nullptr, int stash_off = 0,
+                                            int stash_rows = 0)
 {
+    static_assert(!GLU || (NT == 1 && !FP8), "the GLU form: one token, q8_1 activations");
     using L = Layout<F>;
     constexpr int UPC = UPC_OF<F, NT>;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -222,6 +233,9 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
 
     const __amdgpu_buffer_rsrc_t wrs =
         __builtin_amdgcn_make_buffer_rsrc((void *)A, 0, (int)(((uint32_t)M * RB + 15u) & ~15u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs2 = // GLU: the up matrix, the odd tasks' source
+        __builtin_amdgcn_make_buffer_rsrc((void *)(GLU ? A2 : A), 0, (int)(((uint32_t)M * RB + 15u) & ~15u), 0x00020000);
+    uint16_t *stash = GLU ? (uint16_t *)(smem + stash_off) + wave * stash_rows : nullptr;
     constexpr bool IMG = F == Q6_K && IM != 0;
     const uint32_t RBI = IMG ? (uint32_t)(K / 256) * kImgSB : RB; // ring bytes per row
     // IMG: the source offset, from the task's first byte, of the piece this lane moves in DMA
@@ -240,7 +254,7 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     const int gw = bx * DW + wave;
     const int per = geo.ngroups / W, rem = geo.ngroups % W;
     const int g_begin = gw * per + (gw < rem ? gw : rem);
-    const int ntask = (per + (gw < rem ? 1 : 0)) * geo.nseg;
+    const int ntask = (per + (gw < rem ? 1 : 0)) * geo.nseg * (GLU ? 2 : 1); // (GLU: gate, up, gate, ...)
 
     // task = (row group g, segment s); cursors advance without divisions
     auto window = [&](int g, int s, uint32_t &start, uint32_t &len) {
@@ -266,14 +280,15 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     auto issue = [&](int j) {
         uint32_t st, len;
         window(gi, si, st, len);
-        next(gi, si);
+        if (!GLU || (j & 1)) next(gi, si); // (GLU: the same window of the up matrix first)
+        const __amdgpu_buffer_rsrc_t rs = GLU && (j & 1) ? wrs2 : wrs;
         const uint32_t ws = st & ~15u, we = st + len;
         uint8_t *dst = ring + (j % NS) * SLOT;
         const bool real = j < ntask;
         if constexpr (IMG) {
 #pragma unroll
             for (int k = 0; k < NI; ++k) // pieces past the task re-read its first bytes (L2 hit)
-                dma16(wrs, dst + 1024 * k, real ? st + (rel[k] < len ? rel[k] : 0u) : 0x80000000u);
+                dma16(rs, dst + 1024 * k, real ? st + (rel[k] < len ? rel[k] : 0u) : 0x80000000u);
             return;
         }
 #pragma unroll
@@ -281,7 +296,7 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
             uint32_t o = ws + 1024u * k + 16u * lane;
             if (o >= we) o = ws; // past the window: re-read its first line (L2 hit), never past the tensor
             // no task: an offset past the buffer's range (>= 2^31) -- zeros, no memory access
-            dma16(wrs, dst + 1024 * k, real ? o : 0x80000000u);
+            dma16(rs, dst + 1024 * k, real ? o : 0x80000000u);
         }
     };
 
@@ -435,6 +450,20 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     float acc[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) acc[t] = 0.f;
+    float acc2[NT]; // GLU, segmented rows: the other matrix's partial sum of the row
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc2[t] = 0.f;
+    // GLU: a completed row sum v.  Gate task: its fp16 bits into the lane's stash entry.  Up task:
+    // h = fp16(g / (1 + expf(-g)) * u) in fp32 from the two fp16 values, rounded once.
+    auto glu_out = [](bool up, uint16_t *slot, uint16_t *dst, float v) {
+        const uint16_t hb = f2h_bits(v);
+        if (!up) {
+            *slot = hb;
+        } else {
+            const float gv = h2f(*slot), uv = h2f(hb);
+            *dst = f2h_bits(__fmul_rn(__fdiv_rn(gv, __fadd_rn(1.f, expf(-gv))), uv));
+        }
+    };
 
     // FP8: the unit's x~ (two 32-element runs: Q6_K A and B, else elements 64u..64u+63) and quarter sums
     auto act_h = [&](ActH<NT> &a, int u) {
@@ -578,7 +607,8 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
         uint32_t st, len;
         const int g = gc, s = sc;
         window(g, s, st, len);
-        next(gc, sc);
+        if (!GLU || (j & 1)) next(gc, sc);
+        const bool up = GLU && (j & 1); // GLU: this task completes rows of u (else of g)
         const uint8_t *base = ring + (j % NS) * SLOT + (IMG ? 0u : (st & 15u));
 #ifdef GQ_ABL_NOCOMP
         acc[0] += (float)base[lane];
@@ -611,7 +641,11 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                     for (int t = 0; t < NT; ++t) {
                         const float v = wave_sum_dpp(a[t]);
                         a[t] = 0.f;
-                        if (lane == 0 && t < ntok) C[(tok0 + t) * ldc + r0 + r] = f2h_bits(v);
+                        if constexpr (GLU) {
+                            if (lane == 0 && t < ntok) glu_out(up, stash + r, C + (tok0 + t) * ldc + r0 + r, v);
+                        } else {
+                            if (lane == 0 && t < ntok) C[(tok0 + t) * ldc + r0 + r] = f2h_bits(v);
+                        }
                     }
                 } else {
 #pragma unroll
@@ -619,7 +653,11 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                         float v = a[t];
                         for (int off = P >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
                         a[t] = 0.f;
-                        if (lunit == 0 && r < nr && t < ntok) C[(tok0 + t) * ldc + r0 + r] = f2h_bits(v);
+                        if constexpr (GLU) {
+                            if (lunit == 0 && r < nr && t < ntok) glu_out(up, stash + r, C + (tok0 + t) * ldc + r0 + r, v);
+                        } else {
+                            if (lunit == 0 && r < nr && t < ntok) C[(tok0 + t) * ldc + r0 + r] = f2h_bits(v);
+                        }
                     }
                 }
             };
@@ -647,7 +685,19 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                 for (int t = 0; t < NT; ++t) {
                     const float v = wave_sum_dpp(acc[t]);
                     acc[t] = 0.f;
-                    if (lane == 0 && t < ntok) C[(tok0 + t) * ldc + g] = f2h_bits(v);
+                    if constexpr (GLU) {
+                        if (lane == 0 && t < ntok) glu_out(up, stash, C + (tok0 + t) * ldc + g, v);
+                    } else {
+                        if (lane == 0 && t < ntok) C[(tok0 + t) * ldc + g] = f2h_bits(v);
+                    }
+                }
+            }
+            if constexpr (GLU) { // the row's segments alternate between g and u: acc is this task's sum
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    const float o = acc[t];
+                    acc[t] = acc2[t];
+                    acc2[t] = o;
                 }
             }
         }
@@ -1111,6 +1161,86 @@ hipError_t launch_id_f(const IdArgs &a, int pairs, const Pick &p, hipStream_t s)
     return ring(ic<0>{});
 }
 
+// ---- expert-indexed gate / up with SwiGLU (gq_mmq_id_glu) ----
+// stream_decode_id_kernel's pairs, grid and geometry on two expert tensors of one type and shape:
+// pair p's workgroups run decode_body's GLU form on expert ids[p] of A (gate) and of A2 (up) and
+// store H + p*ldh = fp16(silu(g) * u).  A struct of its own: stream_decode_id_kernel's arguments
+// stay as they are.
+struct IdGluArgs {
+    const uint8_t *A, *A2;
+    const int32_t *ids;
+    const uint16_t *B;
+    uint16_t *H;
+    int64_t expert_bytes, ldb, ldb_slot, ldh;
+    int E, M, K, S, gx;
+    int stash_off, stash_rows; // the waves' g stash: byte offset in LDS, uint16 entries per wave
+    DecodeGeom geo;
+};
+
+template <int F, int ITC, int IM>
+__global__ __launch_bounds__(DW * 64) void stream_decode_id_glu_kernel(const IdGluArgs a)
+{
+    extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
+    const int p = (int)blockIdx.x / a.gx, bx = (int)blockIdx.x - p * a.gx;
+    const int e = __builtin_amdgcn_readfirstlane(a.ids[p]);
+    uint16_t *Hp = a.H + (int64_t)p * a.ldh;
+    if (e < 0 || e >= a.E) {
+        for (int m = bx * (DW * 64) + (int)threadIdx.x; m < a.M; m += a.gx * (DW * 64)) Hp[m] = 0;
+        return;
+    }
+    const int n = p / a.S, s = p - n * a.S;
+    decode_body<F, 1, ITC, IM, 0, 1>(a.A + (int64_t)e * a.expert_bytes,
+                                     a.B + (int64_t)n * a.ldb + (int64_t)s * a.ldb_slot, a.ldb, Hp, a.M, 1, a.K, a.ldh,
+                                     a.geo, bx, a.gx, 0, smem, a.A2 + (int64_t)e * a.expert_bytes, a.stash_off,
+                                     a.stash_rows);
+}
+
+template <int F, int ITC, int IM = 0>
+hipError_t launch_id_glu_t(const IdGluArgs &a, int pairs, size_t lds, hipStream_t s)
+{
+    static bool attr = false; // raise the dynamic LDS limit once per instantiation
+    if (!attr) {
+        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_id_glu_kernel<F, ITC, IM>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    stream_decode_id_glu_kernel<F, ITC, IM><<<dim3((unsigned)(pairs * a.gx)), dim3(DW * 64), lds, s>>>(a);
+    return hipGetLastError();
+}
+
+// launch_id_f's (ITC, IM) set
+template <int F>
+hipError_t launch_id_glu_f(const IdGluArgs &a, int pairs, const Pick &p, size_t lds, hipStream_t s)
+{
+    auto ring = [&](auto im) {
+        return dispatch_upto<itc_max(F, 1)>(p.itc, [&](auto itc) {
+            return launch_id_glu_t<F, decltype(itc)::value, decltype(im)::value>(a, pairs, lds, s);
+        });
+    };
+    if constexpr (F == Q6_K)
+        if (p.img) return ring(ic<1>{});
+    return ring(ic<0>{});
+}
+
+// launch_decode_id's plan (the one-token pick on the pairs' share of the chip) and the GLU form's
+// LDS: the launch's own image, then every wave's stash -- one uint16 per row of a task (G rows;
+// a segmented row: one), rounded up to 16 bytes.  False: no such launch (the stash does not fit).
+bool plan_id_glu(int fmt, int64_t M, int64_t pairs, int64_t K, Pick &p, int &stash_off, int &stash_rows, size_t &lds)
+{
+    Pick solo;
+    if (!decode_id_ok(fmt, M, pairs, K) || !pick(fmt, M, 1, K, solo)) return false;
+    const int per_cu = (int)(LDS_CAP / solo.lds) > 0 ? (int)(LDS_CAP / solo.lds) : 1;
+    const int64_t budget = (int64_t)num_cus() * per_cu;
+    const int wgs = (int)(budget / pairs > 1 ? budget / pairs : 1);
+    if (!pick(fmt, M, 1, K, p, wgs) || p.nt != 1 || p.itc != solo.itc || p.img != solo.img) return false;
+    stash_rows = ((p.geo.nseg == 1 ? p.geo.G : 1) + 7) & ~7;
+    stash_off = (int)((p.lds + 15) & ~(size_t)15);
+    lds = (size_t)stash_off + (size_t)DW * stash_rows * 2;
+    // (the workgroups per CU, hence the geometry, are the plain launch's: the stash may not cost one)
+    return lds <= (size_t)LDS_CAP && (int)(LDS_CAP / lds) == (int)(LDS_CAP / p.lds);
+}
+
 } // namespace
 
 bool decode_fused_ok(int fmt, int64_t N, int64_t K, bool fp8)
@@ -1321,6 +1451,42 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
     a.gx = p.grid;
     a.geo = p.geo;
     return dispatch_fmt(fmt, [&](auto f) { return launch_id_f<decltype(f)::value>(a, (int)pairs, p, s); });
+}
+
+bool decode_id_glu_ok(int fmt, int64_t M, int64_t pairs, int64_t K)
+{
+    Pick p;
+    int off, rows;
+    size_t lds;
+    return plan_id_glu(fmt, M, pairs, K, p, off, rows, lds);
+}
+
+hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const int32_t *ids, const uint16_t *B,
+                                uint16_t *H, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb,
+                                int64_t ldb_slot, int64_t ldh, hipStream_t s)
+{
+    const int64_t pairs = N * S;
+    Pick p;
+    IdGluArgs a{};
+    size_t lds;
+    if (E < 1 || E > INT32_MAX || !plan_id_glu(fmt, M, pairs, K, p, a.stash_off, a.stash_rows, lds))
+        return hipErrorInvalidValue;
+    a.A = A_gate;
+    a.A2 = A_up;
+    a.ids = ids;
+    a.B = B;
+    a.H = H;
+    a.expert_bytes = M * row_bytes(fmt, K);
+    a.ldb = ldb;
+    a.ldb_slot = ldb_slot;
+    a.ldh = ldh;
+    a.E = (int)E;
+    a.M = (int)M;
+    a.K = (int)K;
+    a.S = (int)S;
+    a.gx = p.grid;
+    a.geo = p.geo;
+    return dispatch_fmt(fmt, [&](auto f) { return launch_id_glu_f<decltype(f)::value>(a, (int)pairs, p, lds, s); });
 }
 
 } // namespace gq

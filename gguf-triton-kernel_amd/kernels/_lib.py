@@ -72,6 +72,8 @@ SIGNATURES = {
     "gq_mmq_id": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_mmq_id_sorted_workspace_size": ([_I, _I64, _I64, _I64, _I64, _I64], _SZ),
     "gq_mmq_id_sorted": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
+    "gq_mmq_id_glu": ([_I, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_moe_combine": ([_P, _P, _I, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_mmq_grouped_prepared_workspace_size": ([_I, ctypes.POINTER(GemmItem), _I, _I64], _SZ),
@@ -446,6 +448,75 @@ def mmq_id(gtype: int, A: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: i
     if flat is None:
         C.copy_(res.view(N, S, M))
     return C
+
+
+def glu_torch(g: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    """gq_mmq_id_glu's definition on fp16 g and u with torch ops: fp16(silu(g) * u) in fp32."""
+    return (torch.nn.functional.silu(g.float()) * u.float()).half()
+
+
+def mmq_id_glu(gtype: int, A_gate: torch.Tensor, A_up: torch.Tensor, ids: torch.Tensor, B: torch.Tensor, E: int, M: int,
+               K: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Gate and up of every (token, slot) pair with SwiGLU (gq_mmq_id_glu): A_gate and A_up two
+    expert tensors of one type, E, M and K (mmq_id's A), ids and B as mmq_id's.  Returns (N, S, M)
+    fp16 H = fp16(silu(g) * u), evaluated in fp32 from the fp16 g and u that mmq_id gives for
+    A_gate and A_up.  Up to 64 pairs: one launch, the token's row quantized once for both streams.
+    Where the entry refuses the shape (GQ_EUNSUPPORTED: more than 64 pairs, a long K) the same
+    definition is made from two mmq_id calls and torch ops (mmq_id's own fallbacks apply)."""
+    B, N, S, per_slot, ldb, ldb_slot, C, ldc, ebytes = _id_args(gtype, A_gate, ids, B, E, M, K, out)
+    _require_device(A_up, "A_up")
+    if A_up.dtype not in (torch.int8, torch.uint8) or not A_up.is_contiguous() or A_up.numel() != E * ebytes or \
+            A_up.device != A_gate.device:
+        raise RuntimeError("A_up must be a packed expert tensor of A_gate's type, E, M, K and device")
+    if ldc is None:
+        return C
+    dev = A_gate.device
+    with torch.cuda.device(dev):
+        rc = lib().gq_mmq_id_glu(gtype, A_gate.data_ptr(), A_up.data_ptr(), ids.data_ptr(), B.data_ptr(), C.data_ptr(), E,
+                                 M, N, S, K, ldb, ldb_slot, ldc, _stream(dev))
+    if rc == GQ_EUNSUPPORTED:
+        C.copy_(glu_torch(mmq_id(gtype, A_gate, ids, B, E, M, K), mmq_id(gtype, A_up, ids, B, E, M, K)))
+        return C
+    _check(rc)
+    return C
+
+
+def moe_combine(D: torch.Tensor, W: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The router-weighted sum over slots (gq_moe_combine): D fp16 (N, S, M), W (N, S) fp16 or fp32
+    -> fp16 (N, M), Y[n] = fp16(sum_s W[n, s] * D[n, s]) with the products and the sum in fp32 in
+    slot order, unfused -- one launch, deterministic.  More than 64 slots: the same definition
+    with torch ops."""
+    _require_device(D, "D")
+    _require_device(W, "W")
+    if D.dtype != torch.float16 or D.dim() != 3:
+        raise RuntimeError("D must be an fp16 (N, S, M) tensor")
+    N, S, M = D.shape
+    if tuple(W.shape) != (N, S) or W.device != D.device:
+        raise RuntimeError(f"W is {tuple(W.shape)} on {W.device}, expected ({N}, {S}) on {D.device}")
+    if W.dtype not in (torch.float16, torch.float32):
+        W = W.float()
+    W = W.contiguous()
+    Y = _check_out(out, N, M, D.device)
+    if N * S * M == 0:
+        if S == 0:
+            Y.zero_()
+        return Y
+    ldd = D.stride(1) if S > 1 else (D.stride(0) if N > 1 else M)
+    if (M > 1 and D.stride(2) != 1) or ldd < M or (S > 1 and N > 1 and D.stride(0) != S * ldd):
+        D = D.contiguous()
+        ldd = M
+    dev = D.device
+    with torch.cuda.device(dev):
+        rc = lib().gq_moe_combine(D.data_ptr(), W.data_ptr(), int(W.dtype == torch.float32), Y.data_ptr(), N, S, M, ldd,
+                                  Y.stride(0) if N > 1 else max(Y.stride(0), M), _stream(dev))
+    if rc == GQ_EUNSUPPORTED:
+        acc = torch.zeros((N, M), dtype=torch.float32, device=dev)
+        for s in range(S):
+            acc = acc + W[:, s, None].float() * D[:, s].float()
+        Y.copy_(acc.half())
+        return Y
+    _check(rc)
+    return Y
 
 
 def mmq_grouped_prepared(items, N: int, act: str = "q8_1"):

@@ -21,6 +21,8 @@
  *   gq_quantize_fp8                     its activation quantizer
  *   gq_mmq_id                           expert-indexed MMQ for mixture-of-experts blocks (mul_mat_id)
  *   gq_mmq_id_sorted                    the same at any pair count: device-sorted expert GEMM (prefill)
+ *   gq_mmq_id_glu                       gate and up of every pair with SwiGLU in one launch (decode)
+ *   gq_moe_combine                      the router-weighted sum over a block's slots
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -331,6 +333,46 @@ size_t gq_mmq_id_sorted_workspace_size(gq_type t, int64_t E, int64_t M, int64_t 
 int gq_mmq_id_sorted(gq_type t, const void *A, const int32_t *ids, const void *B, void *C, int64_t E, int64_t M, int64_t N,
                      int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldc, void *workspace,
                      size_t workspace_bytes, void *stream);
+
+/*
+ * Fused gate / up of a mixture-of-experts FFN block at decode: both expert-indexed products of
+ * every (token, slot) pair and their SwiGLU in ONE launch (llama.cpp's mul_mat_id + GLU).  The
+ * token's row is quantized once per workgroup and serves both weight streams.
+ *   A_gate, A_up : two expert tensors of the same type `t`, E, M and K, each laid out as
+ *                  gq_mmq_id's A.
+ *   ids, B, ldb, ldb_slot : as gq_mmq_id.
+ *   H            : fp16; pair p's M values start at element p*ldh (ldh >= M).
+ * Defined result, for pair p and row m: with g and u the fp16 values, bit for bit, that gq_mmq_id
+ * writes for that pair and row from A_gate and from A_up,
+ *   H = fp16_rne( (float)g / (1 + expf(-(float)g)) * (float)u )
+ * evaluated in fp32 and rounded once.  (g and u are rounded to fp16 first on purpose: the fused
+ * entry is a function of bits the library already produces.)  An id outside [0, E) reads no
+ * weights and writes M zeros.
+ * Limits, checks, return codes and their order are gq_mmq_id's (at most 64 pairs, a K that fits
+ * the one-token decode, q8_1 activations only, one expert < 2 GiB; a null A_up is a null pointer).
+ * GQ_EUNSUPPORTED launches nothing and leaves H untouched: the caller then makes the same result
+ * from two gq_mmq_id (or gq_mmq_id_sorted) calls (kernels/_lib.py mmq_id_glu does).
+ * Asynchronous, no host sync, no allocation, graph-capturable: a replay follows `ids`.
+ * gq_version() did not change with it: a caller detects the entry by its symbol (dlsym).
+ */
+int gq_mmq_id_glu(gq_type t, const void *A_gate, const void *A_up, const int32_t *ids, const void *B, void *H, int64_t E,
+                  int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb, int64_t ldb_slot, int64_t ldh, void *stream);
+
+/*
+ * The router-weighted sum over slots that ends a mixture-of-experts block, one launch:
+ *   D : fp16, pair p = n*S + s's M values at element p*ldd (ldd >= M) -- gq_mmq_id's output of
+ *       the down projection.
+ *   W : N*S router weights, fp16 (w_is_f32 == 0) or fp32 (w_is_f32 != 0), pair p's at W[p].
+ *   Y : fp16 (N, M), token n's row at element n*ldy (ldy >= M).
+ * Y[n][m] = fp16_rne(acc), acc = 0.f and, for s = 0..S-1 in that order, acc = acc + w*d with the
+ * product and the sum each rounded to fp32 (no fused multiply-add); with fp16 weights the product
+ * is exact.  Deterministic: every output is summed by one thread in slot order, no atomics.
+ * Any N, S <= 64, M < 2^31.  N == 0, S == 0 or M == 0: a no-op.  GQ_EINVAL: a negative size, a
+ * null pointer, ldd < M, ldy < M.  GQ_EUNSUPPORTED (nothing launched): S > 64 or M >= 2^31.
+ * Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol.
+ */
+int gq_moe_combine(const void *D, const void *W, int w_is_f32, void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd,
+                   int64_t ldy, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE
