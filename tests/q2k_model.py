@@ -13,20 +13,12 @@ super-blocks, both exact (split_q6_k): W1 carries d, the scales and the codes, W
 the mins under the constant code 1.  That ties the format to the reference's Q6_K oracle with no
 code of this project in between.
 """
-import functools
-
 import numpy as np
 
-import oracle as O
-from utils.synth import random_activations, random_blocks
+from type_models import (ALL_SHAPES, BLAS_SHAPES, DECODE_SHAPES, GEMM_SHAPES, GEMV_SHAPES, LONG_SHAPES,  # noqa: F401
+                         SPLITK_SHAPES, TIGHT_GEMM, TIGHT_GEMV, make_case, pack_q6_k, q81, rel_err, tight)
 
-TIGHT_GEMV = 1.5e-3
-TIGHT_GEMM = 4e-3
 BYTES = 84
-
-
-def tight(N):
-    return TIGHT_GEMV if N <= 4 else TIGHT_GEMM
 
 
 def unpack(raw, M, K):
@@ -56,25 +48,6 @@ def dequant_f32(raw, M, K):
     return dequant_exact(raw, M, K).astype(np.float32)
 
 
-def _q6_k(d_bytes, sc, codes):
-    """Q6_K super-blocks (210 B) with fp16 d bytes (nblk, 2), int8 scales (nblk, 16) and 6-bit
-    codes (nblk, 256) at Q6_K's positions: ql nibble (e%128)/64 of byte 64*(e/128) + e%64, qh bits
-    2*((e%128)/32) of byte 32*(e/128) + e%32."""
-    nblk = codes.shape[0]
-    out = np.zeros((nblk, 210), np.uint8)
-    c = codes.astype(np.uint8)
-    for h in range(2):
-        for j in range(4):
-            e0 = 128 * h + 32 * j
-            ce = c[:, e0:e0 + 32]
-            lo = 64 * h + 32 * (j & 1)
-            out[:, lo:lo + 32] |= (ce & 15) << (4 * (j >> 1))
-            out[:, 128 + 32 * h:128 + 32 * h + 32] |= (ce >> 4) << (2 * j)
-    out[:, 192:208] = sc.astype(np.int8).view(np.uint8)
-    out[:, 208:210] = d_bytes
-    return out.reshape(-1)
-
-
 def split_q6_k(raw):
     """(W1, W2), two Q6_K tensors with W = W1 - W2, both parts exact: W1 has d6 = d, int8
     sc6 = sc and codes q + 32 (so d*sc*q); W2 has d6 = dmin, sc6 = m and every code 33 (dmin*m)."""
@@ -82,17 +55,9 @@ def split_q6_k(raw):
     nblk = raw.size // BYTES
     blk = raw.reshape(nblk, BYTES)
     _, _, sc, m, q = unpack(raw, 1, 256 * nblk)
-    w1 = _q6_k(blk[:, 80:82], sc[0], q[0] + 32)
-    w2 = _q6_k(blk[:, 82:84], m[0], np.full((nblk, 256), 33, np.int64))
+    w1 = pack_q6_k(blk[:, 80:82], sc[0], q[0] + 32)
+    w2 = pack_q6_k(blk[:, 82:84], m[0], np.full((nblk, 256), 33, np.int64))
     return w1, w2
-
-
-def q81(B):
-    """The oracle's q8_1 quantizer on fp16 (N, K): d, s as fp32 (N, K/32); codes int (N, K/32, 32)."""
-    N, K = B.shape
-    blk = O.quantize_q8_1(np.ascontiguousarray(B)).reshape(N, K // 32, 36)
-    ds = np.ascontiguousarray(blk[..., 0:4]).view(np.float16).astype(np.float32)
-    return ds[..., 0], ds[..., 1], blk[..., 4:].view(np.int8).astype(np.int64)
 
 
 def ideal(raw, B, M, N, K):
@@ -100,11 +65,6 @@ def ideal(raw, B, M, N, K):
     d, _, q = q81(B)
     xt = (d.astype(np.float64)[..., None] * q).reshape(N, K)
     return xt @ dequant_exact(raw, M, K).T
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
 
 
 def model_mfma(raw, B, M, N, K):
@@ -189,28 +149,7 @@ def naive_quantize(x):
     return out.reshape(-1)
 
 
-# ---- the GPU tests' inputs (the CPU model test checks the same ones) ----
-# The streaming decode's LDS activation image is Q3_K's (codes, d, two per-16 code sums per block:
-# 1.375 K bytes per token beside the 112 KiB ring), so the token and K limits are Q3_K's and so are
-# the shapes: (16, 4, 8704) is the last multiple of 256 on the decode at four tokens, (16, 4, 8960)
-# the first on the GEMV; one token of K = 16640 fits, 3 tokens of 16384 and 2 of 28672 do not.
-DECODE_SHAPES = [(1, 1, 256), (5, 3, 512), (63, 2, 768), (65, 4, 1024), (96, 1, 2816), (16, 4, 8704)]
-LONG_SHAPES = [(4, 1, 16640), (4, 3, 16384), (8, 2, 28672)]
-GEMV_SHAPES = [(32, 4, 11008), (16, 4, 8960)]
-GEMM_SHAPES = [(130, 5, 256), (7, 8, 512), (33, 9, 256), (70, 16, 512), (129, 17, 768), (64, 64, 1024),
-               (200, 130, 512)]
-SPLITK_SHAPES = [(256, 32, 4096), (300, 128, 2048)]
-BLAS_SHAPES = [(65, 24, 1024), (130, 33, 256)]
-ALL_SHAPES = DECODE_SHAPES + LONG_SHAPES + GEMV_SHAPES + GEMM_SHAPES + SPLITK_SHAPES + BLAS_SHAPES
+# ---- the GPU tests' inputs: the shared K % 256 lists, which are Q3_K's (tests/type_models.py) ----
 
 
-@functools.lru_cache(maxsize=None)
-def case(M, N, K):
-    """(packed Q2_K weights, fp16 activations, the fp64 ideal) of a shape: computed once, never
-    written to."""
-    raw = random_blocks("q2_k", M, K, seed=M * 7 + N)
-    B = random_activations(N, K, seed=K + N)
-    want = ideal(raw, B, M, N, K)
-    for a in (raw, B, want):
-        a.setflags(write=False)
-    return raw, B, want
+case = make_case("q2_k", ideal)  # (the fp64 ideal)

@@ -10,20 +10,13 @@ h = e / 128, j = (e % 128) / 32, l = e % 32, s = e / 16:
 Q3_K has Q6_K's arithmetic (sixteen signed scales, one d, no mins), so a Q3_K super-block
 re-encodes as a Q6_K super-block without loss (to_q6_k) and the reference's Q6_K oracle judges it.
 """
-import functools
-
 import numpy as np
 
 import oracle as O
-from utils.synth import random_activations, random_blocks
+from type_models import (ALL_SHAPES, BLAS_SHAPES, DECODE_SHAPES, GEMM_SHAPES, GEMV_SHAPES, LONG_SHAPES,  # noqa: F401
+                         SPLITK_SHAPES, TIGHT_GEMM, TIGHT_GEMV, make_case, pack_q6_k, q81, rel_err, tight)
 
-TIGHT_GEMV = 1.5e-3
-TIGHT_GEMM = 4e-3
 BYTES = 110
-
-
-def tight(N):
-    return TIGHT_GEMV if N <= 4 else TIGHT_GEMM
 
 
 def unpack(raw, M, K):
@@ -61,32 +54,11 @@ def dequant_exact(raw, M, K):
 
 def to_q6_k(raw):
     """The same weights as Q6_K super-blocks (210 B): the same d, int8 scales = sc, 6-bit codes
-    q + 32 at Q6_K's positions for the same element (ql nibble e%128/64 of byte 64*(e/128) + e%64,
-    qh bits 2*(e%128/32) of byte 32*(e/128) + e%32)."""
+    q + 32 at Q6_K's positions for the same element (type_models.pack_q6_k)."""
     raw = np.asarray(raw).view(np.uint8)
     nblk = raw.size // BYTES
     d, sc, q = unpack(raw, 1, 256 * nblk)
-    blk3 = raw.reshape(nblk, BYTES)
-    out = np.zeros((nblk, 210), np.uint8)
-    c = (q[0] + 32).astype(np.uint8)  # (nblk, 256), 28..35
-    for h in range(2):
-        for j in range(4):
-            e0 = 128 * h + 32 * j
-            ce = c[:, e0:e0 + 32]
-            lo = 64 * h + 32 * (j & 1)
-            out[:, lo:lo + 32] |= (ce & 15) << (4 * (j >> 1))
-            out[:, 128 + 32 * h:128 + 32 * h + 32] |= (ce >> 4) << (2 * j)
-    out[:, 192:208] = sc[0].astype(np.int8).view(np.uint8)
-    out[:, 208:210] = blk3[:, 108:110]
-    return out.reshape(-1)
-
-
-def q81(B):
-    """The project's own q8_1 quantizer on fp16 (N, K): d, s as fp32 (N, K/32); codes int (N, K/32, 32)."""
-    N, K = B.shape
-    blk = O.quantize_q8_1(np.ascontiguousarray(B)).reshape(N, K // 32, 36)
-    ds = np.ascontiguousarray(blk[..., 0:4]).view(np.float16).astype(np.float32)
-    return ds[..., 0], ds[..., 1], blk[..., 4:].view(np.int8).astype(np.int64)
+    return pack_q6_k(raw.reshape(nblk, BYTES)[:, 108:110], sc[0], q[0] + 32)  # (codes 28..35)
 
 
 def ideal(raw, B, M, N, K):
@@ -99,11 +71,6 @@ def ideal(raw, B, M, N, K):
 def oracle_ideal(raw, B, M, N, K):
     """The judge of the GPU tests: the reference's Q6_K arithmetic on the transcoded blocks."""
     return O.mmq_from_fp16("q6_k", to_q6_k(raw), B, M, N, K, O.IDEAL)
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
 
 
 def model_mfma(raw, B, M, N, K):
@@ -163,31 +130,9 @@ def naive_quantize(x):
     return out.reshape(-1)
 
 
-# ---- the GPU tests' inputs (the CPU model test checks the same ones) ----
-# The streaming decode keeps codes, d and the two per-16 code sums of every token in LDS beside
-# the 112 KiB ring: 1.375 K bytes per token in the 48 KiB left (Q5_K: 1.25 K).  Four tokens fit up
-# to K = 8936: (16, 4, 8704) is the last multiple of 256 on the decode, (16, 4, 8960) the first on
-# the GEMV (Q5_K's own threshold, K = 9830, lies above both).  The long rows stand as Q5_K's:
-# one token of K = 16640 fits (five cached units per lane); 3 tokens of 16384 and 2 of 28672 do
-# not (they would run as two token groups) and take the GEMV, as do 4 tokens of 11008.
-DECODE_SHAPES = [(1, 1, 256), (5, 3, 512), (63, 2, 768), (65, 4, 1024), (96, 1, 2816), (16, 4, 8704)]
-LONG_SHAPES = [(4, 1, 16640), (4, 3, 16384), (8, 2, 28672)]
-GEMV_SHAPES = [(32, 4, 11008), (16, 4, 8960)]
-GEMM_SHAPES = [(130, 5, 256), (7, 8, 512), (33, 9, 256), (70, 16, 512), (129, 17, 768), (64, 64, 1024),
-               (200, 130, 512)]
-SPLITK_SHAPES = [(256, 32, 4096), (300, 128, 2048)]
-BLAS_SHAPES = [(65, 24, 1024), (130, 33, 256)]
-ALL_SHAPES = DECODE_SHAPES + LONG_SHAPES + GEMV_SHAPES + GEMM_SHAPES + SPLITK_SHAPES + BLAS_SHAPES
+# ---- the GPU tests' inputs: the shared K % 256 lists (tests/type_models.py) ----
 
 
-@functools.lru_cache(maxsize=None)
-def case(M, N, K):
-    """(packed Q3_K weights, fp16 activations, the oracle's ideal as fp64) of a shape: computed
-    once, never written to.  The ideal is the reference's Q6_K arithmetic on the transcoded blocks
-    (one final fp16 rounding), not code of this project."""
-    raw = random_blocks("q3_k", M, K, seed=M * 7 + N)
-    B = random_activations(N, K, seed=K + N)
-    want = oracle_ideal(raw, B, M, N, K).astype(np.float64)
-    for a in (raw, B, want):
-        a.setflags(write=False)
-    return raw, B, want
+# the ideal as fp64: the reference's Q6_K arithmetic on the transcoded blocks (one final fp16
+# rounding), not code of this project
+case = make_case("q3_k", lambda *a: oracle_ideal(*a).astype(np.float64))

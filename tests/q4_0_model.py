@@ -7,20 +7,13 @@ fp32.  A Q4_0 block is a Q8_0 block with the same two d bytes and the int8 codes
 order (widen): that ties the format, the CPU product and the GPU tests' judge to the reference's
 Q8_0 oracle bit for bit, with no code of this project in between.
 """
-import functools
-
 import numpy as np
 
 import oracle as O
-from utils.synth import random_activations, random_blocks
+from type_models import BLAS_SHAPES, SPLITK_SHAPES, TIGHT_GEMM, TIGHT_GEMV, make_case, q81, rel_err, tight  # noqa: F401
+from utils.synth import random_blocks
 
-TIGHT_GEMV = 1.5e-3
-TIGHT_GEMM = 4e-3
 BYTES = 18
-
-
-def tight(N):
-    return TIGHT_GEMV if N <= 4 else TIGHT_GEMM
 
 
 def _blocks(raw):
@@ -64,25 +57,12 @@ def ideal(raw, B, M, N, K):
     return O.mmq_from_fp16("q8_0", widen(raw), np.ascontiguousarray(B), M, N, K, O.IDEAL)
 
 
-def q81(B):
-    """The oracle's q8_1 quantizer on fp16 (N, K): d fp32 (N, K/32); codes int64 (N, K/32, 32)."""
-    N, K = B.shape
-    blk = O.quantize_q8_1(np.ascontiguousarray(B)).reshape(N, K // 32, 36)
-    d = np.ascontiguousarray(blk[..., 0:2]).view(np.float16).astype(np.float32)
-    return d[..., 0], blk[..., 4:].view(np.int8).astype(np.int64)
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
-
-
 def model_decode(raw, B, M, N, K):
     """The decode / GEMV order: per block (d*dB)*i in fp32 with i the exact integer dot product, the
     blocks added in fp32, one rounding to fp16.  (The lanes' summation tree is not modelled: fp32
     sums of at most K/32 terms differ from it by a few fp32 ulps.)"""
     d, q = unpack(raw, M, K)
-    xd, xq = q81(B)
+    xd, _, xq = q81(B)
     i = np.einsum("mbl,nbl->nmb", q, xq).astype(np.float32)
     t = ((d[None] * xd[:, None]).astype(np.float32) * i).astype(np.float32)
     return t.sum(axis=2, dtype=np.float32).astype(np.float16)
@@ -93,7 +73,7 @@ def model_mfma(raw, B, M, N, K):
     x~ = dB*qB, fp32 sums, fp16 output."""
     d, q = unpack(raw, M, K)
     w = (d[..., None].astype(np.float64) * q).astype(np.float16).astype(np.float32).reshape(M, K)
-    xd, xq = q81(B)
+    xd, _, xq = q81(B)
     xt = (xd[..., None] * xq.astype(np.float32)).astype(np.float16).astype(np.float32).reshape(N, K)
     return (xt @ w.T).astype(np.float32).astype(np.float16)
 
@@ -141,21 +121,10 @@ def new_rule_quantize(x):
 DECODE_SHAPES = [(1, 1, 32), (5, 3, 96), (63, 2, 160), (65, 4, 1024), (96, 1, 2848), (16, 4, 10880), (8, 1, 28672)]
 GEMV_SHAPES = [(32, 4, 11008), (16, 4, 10912), (70, 16, 160), (33, 130, 1120)]
 GEMM_SHAPES = [(130, 5, 256), (7, 8, 512), (70, 16, 512), (129, 17, 768), (64, 64, 1024), (200, 130, 512)]
-SPLITK_SHAPES = [(256, 32, 4096), (300, 128, 2048)]
-BLAS_SHAPES = [(65, 24, 1024), (130, 33, 256)]
 ALL_SHAPES = DECODE_SHAPES + GEMV_SHAPES + GEMM_SHAPES + SPLITK_SHAPES + BLAS_SHAPES
 
 
-@functools.lru_cache(maxsize=None)
-def case(M, N, K):
-    """(packed Q4_0 weights, fp16 activations, the oracle's ideal) of a shape: computed once, never
-    written to."""
-    raw = random_blocks("q4_0", M, K, seed=M * 7 + N)
-    B = random_activations(N, K, seed=K + N)
-    want = ideal(raw, B, M, N, K)
-    for a in (raw, B, want):
-        a.setflags(write=False)
-    return raw, B, want
+case = make_case("q4_0", ideal)  # (the oracle's ideal, fp16)
 
 
 def edge_blocks(M, K, seed=0):

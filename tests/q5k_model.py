@@ -7,20 +7,13 @@ The reference project has no Q5_K, so the format is pinned here, from its defini
     q = ((qs[32*(j/2) + l] >> 4*(j&1)) & 15) + 16*((qh[l] >> j) & 1)      (0..31)
     w = d*sc_j*q - dmin*m_j
 """
-import functools
-
 import numpy as np
 
-import oracle as O
-from utils.synth import random_activations, random_blocks
+import type_models as TM
+from type_models import (BLAS_SHAPES, GEMM_SHAPES, LONG_SHAPES, SPLITK_SHAPES, TIGHT_GEMM, TIGHT_GEMV,  # noqa: F401
+                         make_case, q81, rel_err, tight)
 
-TIGHT_GEMV = 1.5e-3
-TIGHT_GEMM = 4e-3
 BYTES = 176
-
-
-def tight(N):
-    return TIGHT_GEMV if N <= 4 else TIGHT_GEMM
 
 
 def unpack(raw, M, K):
@@ -55,14 +48,6 @@ def dequant_f32(raw, M, K):
     return w.astype(np.float32).reshape(M, K)
 
 
-def q81(B):
-    """The project's own q8_1 quantizer on fp16 (N, K): d, s as fp32 (N, K/32); codes int (N, K/32, 32)."""
-    N, K = B.shape
-    blk = O.quantize_q8_1(np.ascontiguousarray(B)).reshape(N, K // 32, 36)
-    ds = np.ascontiguousarray(blk[..., 0:4]).view(np.float16).astype(np.float32)
-    return ds[..., 0], ds[..., 1], blk[..., 4:].view(np.int8).astype(np.int64)
-
-
 def ideal(raw, B, M, N, K):
     """x~ @ W^T in fp64, x~ = d*q of the q8_1 blocks; (N, M) float64."""
     d, _, q = q81(B)
@@ -74,11 +59,6 @@ def dequant_exact(raw, M, K):
     d, dmin, sc, mn, q = unpack(raw, M, K)
     d, dmin = d.astype(np.float64), dmin.astype(np.float64)
     return ((d[..., None] * sc)[..., None] * q - (dmin[..., None] * mn)[..., None]).reshape(M, K)
-
-
-def rel_err(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.max(np.abs(got - want)) / np.max(np.abs(want)))
 
 
 def model_mfma(raw, B, M, N, K):
@@ -105,23 +85,11 @@ def model_decode(raw, B, M, N, K):
     return t.astype(np.float32).sum(axis=2, dtype=np.float32).astype(np.float16)
 
 
-# ---- the GPU tests' inputs (the CPU model test checks the same ones) ----
-DECODE_SHAPES = [(1, 1, 256), (5, 3, 512), (63, 2, 768), (65, 4, 1024), (96, 1, 2816)]
-LONG_SHAPES = [(4, 1, 16640), (4, 3, 16384), (8, 2, 28672)]
-GEMV_SHAPES = [(32, 4, 11008)]
-GEMM_SHAPES = [(130, 5, 256), (7, 8, 512), (33, 9, 256), (70, 16, 512), (129, 17, 768), (64, 64, 1024),
-               (200, 130, 512)]
-SPLITK_SHAPES = [(256, 32, 4096), (300, 128, 2048)]
-BLAS_SHAPES = [(65, 24, 1024), (130, 33, 256)]
+# ---- the GPU tests' inputs (the CPU model test checks the same ones): the shared K % 256 lists
+# without the two shapes at Q3_K's four-token limit (tests/type_models.py) ----
+DECODE_SHAPES = [s for s in TM.DECODE_SHAPES if s != (16, 4, 8704)]
+GEMV_SHAPES = [s for s in TM.GEMV_SHAPES if s != (16, 4, 8960)]
 ALL_SHAPES = DECODE_SHAPES + LONG_SHAPES + GEMV_SHAPES + GEMM_SHAPES + SPLITK_SHAPES + BLAS_SHAPES
 
 
-@functools.lru_cache(maxsize=None)
-def case(M, N, K):
-    """(packed Q5_K weights, fp16 activations, fp64 ideal) of a shape: computed once, never written to."""
-    raw = random_blocks("q5_k", M, K, seed=M * 7 + N)
-    B = random_activations(N, K, seed=K + N)
-    want = ideal(raw, B, M, N, K)
-    for a in (raw, B, want):
-        a.setflags(write=False)
-    return raw, B, want
+case = make_case("q5_k", ideal)  # (the fp64 ideal)

@@ -12,7 +12,8 @@ import pytest
 import torch
 
 import oracle as O
-import q5k_model as Q
+import type_models as TM
+from gpu_types import dev as _dev, no_timeouts as _no_timeouts, same_bits as _same_bits, to_w as _w
 from utils.synth import random_activations, random_blocks
 
 pytestmark = pytest.mark.gpu
@@ -31,26 +32,12 @@ CASES = [("q4_k", 4, 200, 1024),
 PAIRS = [(1, 1), (1, 8), (4, 2), (8, 8)]
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return torch.device("cuda:0")
-
-
-def _no_timeouts():
-    import kernels._lib as kl
-    assert kl.lib().gq_debug_sync_timeouts() == 0
-
-
 @functools.lru_cache(maxsize=None)
 def _experts(fmt, E, M, K):
     """E packed matrices back to back (exactly E experts: nothing to read past them), read-only."""
     raw = np.concatenate([random_blocks(fmt, M, K, seed=1000 * E + 10 * M + e) for e in range(E)])
     raw.setflags(write=False)
     return raw
-
-
-def _w(raw):
-    return torch.from_numpy(np.array(raw).view(np.int8)).to(_dev())
 
 
 def _ids(N, S, E, seed=0):
@@ -74,10 +61,6 @@ def _solo(kl, gtype, A, E, ids, rows, M, K):
                 x = (rows[n, s] if rows.dim() == 3 else rows[n]).reshape(1, K).contiguous()
                 want[n, s] = kl.mmq(gtype, A[e * per:(e + 1) * per], x, M, 1, K)[0]
     return want
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int16), b.contiguous().view(torch.int16))
 
 
 @pytest.mark.parametrize("N,S", PAIRS)
@@ -105,9 +88,9 @@ def test_id_bit_identical_and_oracle(fmt, E, M, K, N, S):
         sub = np.concatenate([raw[e * per + r * rb:e * per + (r + 1) * rb] for r in rows])
         B = x[n:n + 1]
         if fmt == "q5_k":
-            err = Q.rel_err(g[n, s][None, rows], Q.ideal(sub, B, len(rows), 1, K))
+            err = TM.rel_err(g[n, s][None, rows], TM.judge(fmt, sub, B, len(rows), 1, K))
             print(f"{fmt} E={E} {M}x{K} pair ({n},{s}) expert {e}: max|d|/max|C| = {err:.2e}")
-            assert err <= Q.TIGHT_GEMV, (p, err)
+            assert err <= TM.TIGHT_GEMV, (p, err)
             continue
         ideal = O.mmq_from_fp16(fmt, sub, B, len(rows), 1, K, O.IDEAL)
         err = O.max_rel_err(g[n, s][None, rows], ideal)

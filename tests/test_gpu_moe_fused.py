@@ -18,6 +18,7 @@ import q2k_model as Q2
 import q3k_model as Q3
 import q4_0_model as Q40
 import q5k_model as Q5
+from gpu_types import dev as _dev, no_timeouts as _no_timeouts, same_bits as _same_bits, to_w as _w
 from utils.synth import random_activations, random_blocks
 
 pytestmark = pytest.mark.gpu
@@ -36,26 +37,12 @@ CASES = [("q4_k", 4, 200, 1024),
 PAIRS = [(1, 1), (4, 2), (8, 8)]
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return torch.device("cuda:0")
-
-
-def _no_timeouts():
-    import kernels._lib as kl
-    assert kl.lib().gq_debug_sync_timeouts() == 0
-
-
 @functools.lru_cache(maxsize=None)
 def _experts(fmt, E, M, K, which=0):
     """E packed matrices back to back, read-only (which: 0 gate, 1 up, 2 down)."""
     raw = np.concatenate([random_blocks(fmt, M, K, seed=7000 * which + 1000 * E + 10 * M + e) for e in range(E)])
     raw.setflags(write=False)
     return raw
-
-
-def _w(raw):
-    return torch.from_numpy(np.array(raw).view(np.int8)).to(_dev())
 
 
 def _ids(N, S, E, seed=0):
@@ -72,10 +59,6 @@ def _x(N, K, seed):
 
 def _bits(t):
     return t.contiguous().view(torch.int16)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
 
 
 def _check_glu(H, g, u, what):

@@ -14,7 +14,8 @@ import pytest
 import torch
 
 import oracle as O
-import q5k_model as Q
+import type_models as TM
+from gpu_types import dev as _dev, no_timeouts as _no_timeouts, same_bits as _same_bits, to_w as _w
 from utils.synth import random_activations, random_blocks
 
 pytestmark = pytest.mark.gpu
@@ -35,30 +36,12 @@ EXPECT_NB = {(3, 5, 1): 1, (4, 5, 1): 1, (5, 5, 1): 1,      # 2 pairs per expert
 PINS = dict(GQ_SGEMM=1, GQ_SGEMM_SPLITS=1, GQ_SKINNY=0, GQ_RGEMM=0, GQ_KSTREAM=0)
 
 
-def _dev():
-    assert torch.cuda.is_available(), "GPU tests need a ROCm device"
-    return torch.device("cuda:0")
-
-
-def _no_timeouts():
-    import kernels._lib as kl
-    assert kl.lib().gq_debug_sync_timeouts() == 0
-
-
 @functools.lru_cache(maxsize=None)
 def _experts(fmt, E, M, K):
     """E packed matrices back to back (exactly E experts: nothing to read past them), read-only."""
     raw = np.concatenate([random_blocks(fmt, M, K, seed=2000 * E + 10 * M + e) for e in range(E)])
     raw.setflags(write=False)
     return raw
-
-
-def _w(raw):
-    return torch.from_numpy(np.array(raw).view(np.int8)).to(_dev())
-
-
-def _same_bits(a, b):
-    return torch.equal(a.contiguous().view(torch.int16), b.contiguous().view(torch.int16))
 
 
 def _nb(P, E):
@@ -156,9 +139,9 @@ def test_sorted_oracle_and_bit_identity(fmt, E, M, K, N, S):
         B = x[[p // S for p in pairs]]
         sel = g[pairs][:, wr]
         if fmt == "q5_k":
-            err = Q.rel_err(sel, Q.ideal(sub, B, len(wr), len(pairs), K))
+            err = TM.rel_err(sel, TM.judge(fmt, sub, B, len(wr), len(pairs), K))
             print(f"{fmt} E={E} {M}x{K} ({N},{S}) expert {e}: {len(pairs)} pairs, max|d|/max|C| = {err:.2e}")
-            assert err <= Q.TIGHT_GEMM, (e, err)
+            assert err <= TM.TIGHT_GEMM, (e, err)
             continue
         err = O.max_rel_err(sel, O.mmq_from_fp16(fmt, sub, B, len(wr), len(pairs), K, O.IDEAL))
         print(f"{fmt} E={E} {M}x{K} ({N},{S}) expert {e}: {len(pairs)} pairs, max|d|/max|C| = {err:.2e}")
