@@ -226,6 +226,23 @@ hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A
 hipError_t launch_moe_combine(const uint16_t *D, const void *W, bool w_f32, uint16_t *Y, int64_t N, int64_t S, int64_t M,
                               int64_t ldd, int64_t ldy, hipStream_t s);
 
+// The router (moe_route.hip; gq_moe_topk, gq_moe_route), one launch each.
+//   launch_moe_topk: token n's S experts of largest key out of logits[n*ldl + e] (descending, the
+//     lower index first on ties, NaN last; always S distinct ids in [0, E)) into ids[n*S + s], and
+//     their weights (softmax over all E or sigmoid, optionally renormalised over the S, times
+//     scale) into W[n*S + s]; one wave per token, any N.  moe_topk_ok: 1 <= S <= E <=
+//     kMaxSortExperts and S <= kMaxIdPairs.
+//   launch_moe_logits: L[n*ldl + e] = sum_k X[n*ldx + k] * Wr[e*H + k] in fp32, one workgroup per
+//     expert row, the summation order of an (n, e) fixed whatever N is.  moe_logits_ok: N <=
+//     kMaxRouteTokens and H % 32 == 0.
+constexpr int kMaxRouteTokens = 64;
+bool moe_topk_ok(int64_t E, int64_t S);
+bool moe_logits_ok(int64_t N, int64_t H);
+hipError_t launch_moe_topk(const float *logits, int64_t ldl, const float *bias, int func, bool norm, float scale, int32_t *ids,
+                           void *W, bool w_f32, int64_t N, int64_t E, int64_t S, hipStream_t s);
+hipError_t launch_moe_logits(const void *Wr, bool wr_f16, const uint16_t *X, int64_t ldx, float *L, int64_t ldl, int64_t N,
+                             int64_t E, int64_t H, hipStream_t s);
+
 // Sorted expert GEMM (gq_mmq_id_sorted; any pair count): three launches whose grids depend on
 // host-known sizes only.
 //   launch_id_sort (mmq_idsort.hip): one workgroup; perm[P] = the pair indices grouped by expert

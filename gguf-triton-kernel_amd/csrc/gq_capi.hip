@@ -1206,6 +1206,63 @@ int gq_moe_combine(const void *D, const void *W, int w_is_f32, void *Y, int64_t 
                   "moe combine");
 }
 
+// The checks gq_moe_topk and gq_moe_route share, in their order; route: gq_moe_route's Wr, X, ldx
+// and H are checked beside their counterparts (topk passes route = false).  empty: N == 0.
+static int check_route_args(bool route, const void *Wr, const void *X, int64_t ldx, int64_t H, const float *logits,
+                            int64_t ldl, const float *bias, int func, const int32_t *ids, const void *W, int64_t N, int64_t E,
+                            int64_t S, bool &empty)
+{
+    empty = false;
+    if (N < 0 || E < 0 || S < 0 || (route && H < 0))
+        return fail(GQ_EINVAL, "negative size N=%lld E=%lld S=%lld H=%lld", (long long)N, (long long)E, (long long)S,
+                    (long long)(route ? H : 0));
+    empty = N == 0;
+    if (empty) return GQ_OK;
+    if (route && (!Wr || !X)) return fail(GQ_EINVAL, "null pointer (Wr=%p X=%p)", Wr, X);
+    if (!logits || !ids || !W) return fail(GQ_EINVAL, "null pointer (logits=%p ids=%p W=%p)", (const void *)logits, (const void *)ids, W);
+    if (ldl < E) return fail(GQ_EINVAL, "ldl=%lld < E=%lld", (long long)ldl, (long long)E);
+    if (route && ldx < H) return fail(GQ_EINVAL, "ldx=%lld < H=%lld", (long long)ldx, (long long)H);
+    if (func != 0 && func != 1) return fail(GQ_EINVAL, "func=%d is neither 0 (softmax) nor 1 (sigmoid)", func);
+    if (func == 0 && bias) return fail(GQ_EINVAL, "a selection bias goes with sigmoid gating (func 1) only");
+    if (!gq::moe_topk_ok(E, S))
+        return fail(GQ_EUNSUPPORTED, "not a router shape (1 <= S=%lld <= E=%lld, E at most %d, S at most %d)", (long long)S,
+                    (long long)E, gq::kMaxSortExperts, gq::kMaxIdPairs);
+    return GQ_OK;
+}
+
+int gq_moe_topk(const float *logits, int64_t ldl, const float *bias, int func, int norm, float scale, int32_t *ids, void *W,
+                int w_is_f32, int64_t N, int64_t E, int64_t S, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    const int rc = check_route_args(false, nullptr, nullptr, 0, 0, logits, ldl, bias, func, ids, W, N, E, S, empty);
+    if (rc != GQ_OK || empty) return rc;
+    return hip_rc(gq::launch_moe_topk(logits, ldl, bias, func, norm != 0, scale, ids, W, w_is_f32 != 0, N, E, S,
+                                      (hipStream_t)stream),
+                  "moe topk");
+}
+
+int gq_moe_route(const void *Wr, int wr_is_f16, const void *X, int64_t ldx, float *logits, int64_t ldl, const float *bias,
+                 int func, int norm, float scale, int32_t *ids, void *W, int w_is_f32, int64_t N, int64_t E, int64_t H,
+                 int64_t S, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    const int rc = check_route_args(true, Wr, X, ldx, H, logits, ldl, bias, func, ids, W, N, E, S, empty);
+    if (rc != GQ_OK || empty) return rc;
+    if (!gq::moe_logits_ok(N, H))
+        return fail(GQ_EUNSUPPORTED,
+                    "not a device router product (N=%lld, at most %d; H=%lld %% 32 == 0): multiply outside and call "
+                    "gq_moe_topk",
+                    (long long)N, gq::kMaxRouteTokens, (long long)H);
+    const hipError_t e = gq::launch_moe_logits(Wr, wr_is_f16 != 0, (const uint16_t *)X, ldx, logits, ldl, N, E, H,
+                                               (hipStream_t)stream);
+    if (e != hipSuccess) return hip_rc(e, "moe logits");
+    return hip_rc(gq::launch_moe_topk(logits, ldl, bias, func, norm != 0, scale, ids, W, w_is_f32 != 0, N, E, S,
+                                      (hipStream_t)stream),
+                  "moe topk");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

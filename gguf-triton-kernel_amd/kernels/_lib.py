@@ -74,6 +74,8 @@ SIGNATURES = {
     "gq_mmq_id_sorted": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
     "gq_mmq_id_glu": ([_I, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_moe_combine": ([_P, _P, _I, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_moe_topk": ([_P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _P], _I),
+    "gq_moe_route": ([_P, _I, _P, _I64, _P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_mmq_grouped_prepared_workspace_size": ([_I, ctypes.POINTER(GemmItem), _I, _I64], _SZ),
@@ -517,6 +519,141 @@ def moe_combine(D: torch.Tensor, W: torch.Tensor, out: torch.Tensor | None = Non
         return Y
     _check(rc)
     return Y
+
+
+GATING = {"softmax": 0, "sigmoid": 1}
+
+
+def moe_topk_torch(logits, S, bias=None, func="softmax", norm=True, scale=1.0, w_dtype=torch.float32):
+    """gq_moe_topk's definition with torch ops, for the shapes the entry refuses (E > 1024, S > 64):
+    keys (the logits; sigmoid + bias when a bias is given), a stable descending sort (the lower
+    index first among equal keys; a NaN key is ranked with -inf), the values (softmax over all E,
+    or sigmoid) gathered at the S first ids, optionally divided by their sum, times scale.  Several
+    launches, no host sync."""
+    L = logits.float()
+    s = torch.sigmoid(L) if func == "sigmoid" else None
+    key = L if bias is None else s + bias.float()
+    key = torch.where(torch.isnan(key), torch.full_like(key, float("-inf")), key)
+    ids = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :S]
+    v = (torch.softmax(L, dim=1) if func == "softmax" else s).gather(1, ids)
+    if norm:
+        v = v / v.sum(1, keepdim=True)
+    return ids.to(torch.int32), (v * scale).to(w_dtype)
+
+
+def _route_args(S, E, N, bias, func, w_dtype, out, dev, n_out):
+    if func not in GATING:
+        raise ValueError(f"func is {func!r}, expected 'softmax' or 'sigmoid'")
+    if bias is not None:
+        if func != "sigmoid":
+            raise ValueError("a selection bias goes with sigmoid gating only")
+        if bias.device != dev or bias.numel() != E:
+            raise RuntimeError(f"bias has {bias.numel()} elements on {bias.device}, expected {E} on {dev}")
+        bias = bias.to(torch.float32).contiguous()
+    if w_dtype not in (torch.float32, torch.float16):
+        raise ValueError("w_dtype is torch.float32 or torch.float16")
+    if not 1 <= S <= E:
+        raise ValueError(f"S={S} outside 1..E={E}")
+    if out is None:
+        out = (torch.empty((N, S), dtype=torch.int32, device=dev), torch.empty((N, S), dtype=w_dtype, device=dev),
+               torch.empty((N, E), dtype=torch.float32, device=dev))[:n_out]
+    if len(out) != n_out:
+        raise RuntimeError(f"out must hold {n_out} tensors")
+    ids, W = out[0], out[1]
+    if ids.dtype != torch.int32 or tuple(ids.shape) != (N, S) or not ids.is_contiguous() or ids.device != dev:
+        raise RuntimeError(f"out ids must be a contiguous int32 ({N}, {S}) tensor on {dev}")
+    if W.dtype != w_dtype or tuple(W.shape) != (N, S) or not W.is_contiguous() or W.device != dev:
+        raise RuntimeError(f"out weights must be a contiguous {w_dtype} ({N}, {S}) tensor on {dev}")
+    if n_out == 3:
+        lg = out[2]
+        if lg.dtype != torch.float32 or tuple(lg.shape) != (N, E) or lg.device != dev or (E > 1 and lg.stride(1) != 1) or \
+                (N > 1 and lg.stride(0) < E):
+            raise RuntimeError(f"out logits must be an fp32 ({N}, {E}) tensor on {dev} with unit column stride")
+    return bias, out
+
+
+def moe_topk(logits: torch.Tensor, S: int, bias: torch.Tensor | None = None, func: str = "softmax", norm: bool = True,
+             scale: float = 1.0, w_dtype=torch.float32, out=None):
+    """The router's selection (gq_moe_topk): logits fp32 (N, E) -> (ids int32 (N, S), weights (N, S)
+    of w_dtype, fp32 or fp16).  Token n's ids are the S experts of largest key in descending order,
+    the lower index first on ties -- key = the logit, or with func="sigmoid" and a bias (E fp32)
+    sigmoid(logit) + bias; the weights are softmax(logits) over all E (func="softmax") or
+    sigmoid(logit) at the chosen ids, divided by their sum when norm, times scale.  One launch at
+    any N, deterministic, no host sync.  out = (ids, weights) to write into.  Only E > 1024 or
+    S > 64 (GQ_EUNSUPPORTED) takes moe_topk_torch, the same definition in torch ops."""
+    _require_device(logits, "logits")
+    if logits.dim() != 2:
+        raise RuntimeError("logits must be an (N, E) tensor")
+    if logits.dtype != torch.float32:
+        logits = logits.float()
+    N, E = logits.shape
+    if (E > 1 and logits.stride(1) != 1) or (N > 1 and logits.stride(0) < E):
+        logits = logits.contiguous()
+    dev = logits.device
+    bias, (ids, W) = _route_args(S, E, N, bias, func, w_dtype, out, dev, 2)
+    if N == 0:
+        return ids, W
+    with torch.cuda.device(dev):
+        rc = lib().gq_moe_topk(logits.data_ptr(), logits.stride(0) if N > 1 else max(logits.stride(0), E),
+                               bias.data_ptr() if bias is not None else None, GATING[func], int(bool(norm)), float(scale),
+                               ids.data_ptr(), W.data_ptr(), int(w_dtype == torch.float32), N, E, S, _stream(dev))
+    if rc == GQ_EUNSUPPORTED:
+        i, w = moe_topk_torch(logits, S, bias, func, norm, scale, w_dtype)
+        ids.copy_(i)
+        W.copy_(w)
+        return ids, W
+    _check(rc)
+    return ids, W
+
+
+def moe_route(Wr: torch.Tensor, x: torch.Tensor, S: int, bias: torch.Tensor | None = None, func: str = "softmax",
+              norm: bool = True, scale: float = 1.0, w_dtype=torch.float32, out=None):
+    """The router of a MoE block (gq_moe_route): Wr the (E, H) router matrix, fp32 or fp16, x fp16
+    (N, H) -> (ids, weights, logits): logits = x @ Wr^T accumulated in fp32, stored as fp32 (N, E),
+    and moe_topk's selection on exactly those stored values.  Two launches, no host sync; a token's
+    logits, ids and weights are the bits of its own one-token call.  out = (ids, weights, logits).
+    Where the entry refuses the product (GQ_EUNSUPPORTED: more than 64 tokens, H % 32 != 0) the
+    logits are torch.matmul(x.float(), Wr.float().T) and moe_topk does the rest."""
+    _require_device(Wr, "Wr")
+    _require_device(x, "x")
+    if Wr.dim() != 2 or Wr.dtype not in (torch.float32, torch.float16):
+        raise RuntimeError("Wr must be an fp32 or fp16 (E, H) tensor")
+    E, H = Wr.shape
+    dev = Wr.device
+    if x.device != dev:
+        raise RuntimeError(f"Wr on {dev} but x on {x.device}")
+    if x.dim() != 2 or x.shape[1] != H:
+        raise RuntimeError(f"x is {tuple(x.shape)}, expected (N, {H})")
+    if x.dtype != torch.float16:
+        x = x.to(torch.float16)
+    N = x.shape[0]
+    if (H > 1 and x.stride(1) != 1) or (N > 1 and x.stride(0) < H):
+        x = x.contiguous()
+    Wr = Wr.contiguous()
+    bias, (ids, W, logits) = _route_args(S, E, N, bias, func, w_dtype, out, dev, 3)
+    if N == 0:
+        return ids, W, logits
+    def entry():
+        return lib().gq_moe_route(Wr.data_ptr(), int(Wr.dtype == torch.float16), x.data_ptr(),
+                                  x.stride(0) if N > 1 else max(x.stride(0), H), logits.data_ptr(),
+                                  logits.stride(0) if N > 1 else max(logits.stride(0), E),
+                                  bias.data_ptr() if bias is not None else None, GATING[func], int(bool(norm)),
+                                  float(scale), ids.data_ptr(), W.data_ptr(), int(w_dtype == torch.float32), N, E, H, S,
+                                  _stream(dev))
+
+    with torch.cuda.device(dev):
+        rc = entry()
+    if rc == GQ_EUNSUPPORTED:
+        logits.copy_(torch.matmul(x.float(), Wr.float().T))
+        moe_topk(logits, S, bias, func, norm, scale, w_dtype, out=(ids, W))
+        # (moe_topk's own call reset the thread's error text: the refused entry is asked again -- it
+        # answers from its host-side checks, launching nothing -- so that gq_last_error() still says
+        # why this call took the torch product)
+        with torch.cuda.device(dev):
+            entry()
+        return ids, W, logits
+    _check(rc)
+    return ids, W, logits
 
 
 def mmq_grouped_prepared(items, N: int, act: str = "q8_1"):

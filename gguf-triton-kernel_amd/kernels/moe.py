@@ -15,9 +15,15 @@ MoEFFN(..., fused=True) runs the decode block as three launches instead of seven
 SwiGLU in one (gq_mmq_id_glu, the token's row quantized once for both weight streams), down
 (gq_mmq_id), and the router-weighted sum over the slots (gq_moe_combine).  Opt-in: the default
 keeps the unfused lines and their bits.
+
+MoERouter makes ids and weights on the device from the token's hidden state (gq_moe_route: the
+router product and the top-S selection, two launches), reading the gating function, the
+renormalisation, the scale and the selection bias from the file's metadata; MoEBlock is a router
+and its MoEFFN: MoEBlock.from_gguf(meta, tensors, layer).forward(x) is the FFN of a MoE layer.
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -78,5 +84,117 @@ class MoEFFN:
         h = torch.nn.functional.silu(g) * u
         d = self.down(h, ids)
         return (weights[..., None] * d).sum(1)
+
+    __call__ = forward
+
+
+SHARED_EXPERT_NAMES = ("ffn_gate_shexp", "ffn_up_shexp", "ffn_down_shexp")
+
+
+def _refuse_shared_experts(tensors: dict, layer: int):
+    found = [f"blk.{layer}.{n}.weight" for n in SHARED_EXPERT_NAMES if f"blk.{layer}.{n}.weight" in tensors]
+    if found:
+        raise NotImplementedError("layer %d has shared-expert tensors (%s): their output is added to the routed "
+                                  "experts' and this block does not compute it" % (layer, ", ".join(found)))
+
+
+class MoERouter:
+    """The router of a MoE block on the device: x (N, hidden) fp16 -> (ids (N, S) int32, weights
+    (N, S) fp32), the arguments MoEFFN.forward takes.  Wr is the (E, hidden) router matrix, fp32 or
+    fp16; func "softmax" or "sigmoid"; norm renormalises the S weights to sum 1; scale multiplies
+    them; bias (E fp32, sigmoid gating only) moves the selection and never the weights.  The
+    definition is gq_moe_topk's (include/gguf_mmq.h).  Two launches up to 64 tokens
+    (kernels._lib.moe_route), no host sync: graph-capturable, a replay follows x."""
+
+    def __init__(self, Wr: torch.Tensor, S: int, bias: torch.Tensor | None = None, func: str = "softmax",
+                 norm: bool = True, scale: float = 1.0):
+        if Wr.dim() != 2 or Wr.dtype not in (torch.float32, torch.float16):
+            raise ValueError("Wr must be an fp32 or fp16 (E, hidden) tensor")
+        if func not in _lib.GATING:
+            raise ValueError(f"func is {func!r}, expected 'softmax' or 'sigmoid'")
+        self.Wr, self.E, self.H = Wr.contiguous(), Wr.shape[0], Wr.shape[1]
+        if not 1 <= S <= self.E:
+            raise ValueError(f"S={S} outside 1..E={self.E}")
+        if bias is not None:
+            if func != "sigmoid":
+                raise ValueError("a selection bias goes with sigmoid gating only")
+            if bias.numel() != self.E:
+                raise ValueError(f"bias has {bias.numel()} elements, expected E={self.E}")
+            bias = bias.to(torch.float32).contiguous()
+        self.S, self.bias, self.func, self.norm, self.scale = int(S), bias, func, bool(norm), float(scale)
+
+    @classmethod
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda"):
+        """From read_gguf()'s metadata and tensors: blk.<layer>.ffn_gate_inp.weight (f32 or f16,
+        GGUF dims (hidden, E)), the optional blk.<layer>.exp_probs_b.bias (f32, E) and, with arch =
+        meta["general.architecture"],
+            {arch}.expert_count          E; required, must equal the tensor's
+            {arch}.expert_used_count     S; required
+            {arch}.expert_gating_func    1 softmax, 2 sigmoid; absent or 0: softmax
+            {arch}.expert_weights_norm   renormalise the S weights; absent: True with softmax gating
+                                         (what Mixtral's graph does), False with sigmoid gating
+            {arch}.expert_weights_scale  absent or 0: 1.0
+        These key names, values and defaults are written from memory of llama.cpp; nothing here
+        can check them against it.  In particular a Qwen-MoE file written without
+        expert_weights_norm may want norm=False: build MoERouter(...) by hand when in doubt.
+        A layer that also holds shared-expert tensors raises NotImplementedError."""
+        _refuse_shared_experts(tensors, layer)
+        arch = meta.get("general.architecture")
+        if not isinstance(arch, str):
+            raise ValueError("the file's metadata has no general.architecture")
+        t = tensors[f"blk.{layer}.ffn_gate_inp.weight"]
+        if t.type_name not in ("f32", "f16") or len(t.dims) != 2:
+            raise ValueError(f"{t.name}: expected a 2-D f32 or f16 router matrix, got {t.type_name} dims {t.dims}")
+        E, H = t.shape
+        for key in ("expert_count", "expert_used_count"):
+            if f"{arch}.{key}" not in meta:
+                raise ValueError(f"the file's metadata has no {arch}.{key}")
+        if int(meta[f"{arch}.expert_count"]) != E:
+            raise ValueError(f"{arch}.expert_count is {meta[f'{arch}.expert_count']} but {t.name} has {E} rows")
+        S = int(meta[f"{arch}.expert_used_count"])
+        gating = int(meta.get(f"{arch}.expert_gating_func", 0))
+        if gating not in (0, 1, 2):
+            raise ValueError(f"{arch}.expert_gating_func is {gating}: neither 1 (softmax) nor 2 (sigmoid)")
+        func = "sigmoid" if gating == 2 else "softmax"
+        norm = bool(meta.get(f"{arch}.expert_weights_norm", func == "softmax"))
+        scale = float(meta.get(f"{arch}.expert_weights_scale", 0.0)) or 1.0
+        np_dtype = np.float32 if t.type_name == "f32" else np.float16
+        Wr = torch.from_numpy(np.array(t.data, dtype=np.uint8).view(np_dtype).reshape(E, H)).to(device)
+        bias = None
+        b = tensors.get(f"blk.{layer}.exp_probs_b.bias")
+        if b is not None:
+            if b.type_name != "f32" or int(np.prod(b.dims)) != E:
+                raise ValueError(f"{b.name}: expected {E} f32 values, got {b.type_name} dims {b.dims}")
+            if func != "sigmoid":
+                raise ValueError(f"{b.name}: a selection bias in a file whose gating is softmax")
+            bias = torch.from_numpy(np.array(b.data, dtype=np.uint8).view(np.float32).reshape(E)).to(device)
+        return cls(Wr, S, bias, func, norm, scale)
+
+    def __call__(self, x: torch.Tensor):
+        ids, weights, _ = _lib.moe_route(self.Wr, x, self.S, self.bias, self.func, self.norm, self.scale)
+        return ids, weights
+
+
+class MoEBlock:
+    """The whole FFN of a MoE layer: forward(x) = ffn(x, *router(x)), x (N, hidden) fp16 ->
+    (N, hidden).  With MoEFFN(fused=True) five launches at decode (two for the router, three for
+    the experts), no host sync: graph-capturable, a replay routes the x it finds.  Shared experts
+    are not part of it."""
+
+    def __init__(self, router: MoERouter, ffn: MoEFFN):
+        if router.E != ffn.gate.E or router.H != ffn.gate.K:
+            raise ValueError(f"router is {router.E} x {router.H} but the experts are {ffn.gate.E} x (ffn, {ffn.gate.K})")
+        self.router, self.ffn = router, ffn
+
+    @classmethod
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", fused: bool = True):
+        """From read_gguf()'s metadata and tensors: MoERouter.from_gguf and MoEFFN.from_gguf of the
+        layer.  A layer with shared-expert tensors (blk.<layer>.ffn_*_shexp.weight) raises
+        NotImplementedError: their output belongs in the sum and nothing here computes it."""
+        _refuse_shared_experts(tensors, layer)
+        return cls(MoERouter.from_gguf(meta, tensors, layer, device), MoEFFN.from_gguf(tensors, layer, device, fused=fused))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.ffn(x, *self.router(x))
 
     __call__ = forward

@@ -23,6 +23,8 @@
  *   gq_mmq_id_sorted                    the same at any pair count: device-sorted expert GEMM (prefill)
  *   gq_mmq_id_glu                       gate and up of every pair with SwiGLU in one launch (decode)
  *   gq_moe_combine                      the router-weighted sum over a block's slots
+ *   gq_moe_topk                         a block's router selection: S expert ids and weights from fp32 logits
+ *   gq_moe_route                        the router product and that selection, for decode
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -373,6 +375,52 @@ int gq_mmq_id_glu(gq_type t, const void *A_gate, const void *A_up, const int32_t
  */
 int gq_moe_combine(const void *D, const void *W, int w_is_f32, void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd,
                    int64_t ldy, void *stream);
+
+/*
+ * The router's selection, one launch at any N: from each token's E fp32 logits to its S expert ids
+ * and their weights, the two arrays gq_mmq_id[_glu|_sorted] and gq_moe_combine read.
+ *   logits : fp32, token n's E values at element n*ldl (ldl >= E).
+ *   bias   : NULL, or E fp32 selection biases (func 1 only).
+ *   ids    : int32 (N, S), token n's at ids[n*S].      W : (N, S), fp32 (w_is_f32 != 0) or fp16.
+ * Key of expert e, with L its logit:   func 0 (softmax): L.   func 1 (sigmoid): L without a bias
+ * (sigmoid is monotone; selecting on L makes no ties that rounding would), else
+ * s_e + bias[e] in fp32 with s_e = 1 / (1 + expf(-L)).
+ * Selection: the S experts of largest key in descending key order, the lower index first among
+ * equal keys (-0 equals +0), a NaN key below every number.  Whatever the logits hold, the ids are S
+ * distinct values in [0, E).
+ * Value v_e: func 0, softmax(L)_e over all E experts in fp32 with the row maximum subtracted;
+ * func 1, s_e (the bias selects, it never weighs).  Weight of slot s: v_{id_s}, divided by the sum
+ * of the S selected values when norm != 0, times scale, rounded once to W's type.  (With func 0
+ * and norm the softmax denominator cancels and is not formed.)  Weights are meant for finite
+ * logits; a row with NaN or infinite entries still gets valid ids.
+ * N == 0: a no-op.  GQ_EINVAL: a negative size, a null logits / ids / W, ldl < E, func not 0 or 1,
+ * a bias with func 0.  GQ_EUNSUPPORTED (nothing launched): outside 1 <= S <= E, E > 1024
+ * (gq_mmq_id_sorted's limit) or S > 64 (gq_moe_combine's).
+ * Deterministic (one wave per token, no atomics): a token's ids and weights depend on its own row
+ * alone.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol.
+ */
+int gq_moe_topk(const float *logits, int64_t ldl, const float *bias, int func, int norm, float scale, int32_t *ids, void *W,
+                int w_is_f32, int64_t N, int64_t E, int64_t S, void *stream);
+
+/*
+ * The router of a mixture-of-experts block at decode, two launches: the product with the router
+ * matrix, then gq_moe_topk's selection.
+ *   Wr     : the (E, H) router matrix, contiguous, fp32 (wr_is_f16 == 0; GGUF's
+ *            blk.L.ffn_gate_inp.weight as stored) or fp16.
+ *   X      : fp16 (N, H), token n's row at element n*ldx (ldx >= H).
+ *   logits : fp32, required; the call writes L[n][e] = sum_k X[n][k] * Wr[e][k], accumulated in fp32,
+ *            at element n*ldl + e.  It is the router's one piece of workspace and the caller's to keep.
+ *   bias, func, norm, scale, ids, W, w_is_f32 : gq_moe_topk's, applied to exactly the stored logits.
+ * The summation order of an (n, e) is fixed whatever N is: a token's logits, ids and weights are
+ * the bits of its own one-token call.
+ * Checks, limits and their order are gq_moe_topk's (Wr and X with the pointers, ldx < H with ldl,
+ * H < 0 with the sizes), and then N <= 64 and H % 32 == 0, else GQ_EUNSUPPORTED with nothing
+ * launched and nothing written: multiply outside and call gq_moe_topk (kernels/_lib.py moe_route
+ * does).  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol.
+ */
+int gq_moe_route(const void *Wr, int wr_is_f16, const void *X, int64_t ldx, float *logits, int64_t ldl, const float *bias,
+                 int func, int norm, float scale, int32_t *ids, void *W, int w_is_f32, int64_t N, int64_t E, int64_t H,
+                 int64_t S, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE
