@@ -28,6 +28,8 @@ struct Tuning {
     int sgemm_streamk = -1;                   // GQ_SGEMM_STREAMK: stream-K unit split of the auto plan: 1 every
                                               // streaming GEMM, 0 none, -1 the grouped plans (the measured gain)
     int rgemm_ilc = 0;                        // GQ_RGEMM_ILC: split-K sums inside the GEMM launch (measured slower: opt-in)
+    int rgemm_estore = -1;                    // GQ_RGEMM_ESTORE: resident GEMM's partial stores under its second half
+                                              // multiply: 1 every tile that has the form, 0 none, -1 where measured faster
     int sgemm_full = -1;                      // GQ_SGEMM_FULL: Q4_K 16/32-token tiles stream whole super-blocks:
                                               // 1 every streaming GEMM, 0 none, -1 single matrices (measured gain)
     int kstream = -1;                         // GQ_KSTREAM: K-chunked streaming MMQ -1 auto / 0 off / 1 wherever it applies
@@ -134,6 +136,8 @@ struct RGemmPlan {
 RGemmPlan plan_rgemm(int64_t M, int64_t N, int64_t K);
 // the split-K partials summed inside the launch (no reduce launch): plans whose grid the chip holds
 bool rgemm_ilc(int fmt, const RGemmPlan &p);
+// whether the resident GEMM at nb token tiles (RGemmPlan::nb) runs its early-store form (GQ_RGEMM_ESTORE)
+bool rgemm_estore(int nb);
 // in-launch combine polls that gave up since the library loaded (0 unless a grid was not resident)
 unsigned int ilc_timeouts();
 // the K-chunked stream's cross-wave hand-off waits that gave up (0 unless broken)

@@ -64,7 +64,10 @@ bool parse_key(Tuning &t, const char *key, long long v)
         if (v < 0 || v > 4096) return false;
         t.sgemm_splits = (int)v;
     } else if (k == "GQ_RGEMM_ILC") t.rgemm_ilc = v != 0;
-    else if (k == "GQ_SGEMM_FULL") {
+    else if (k == "GQ_RGEMM_ESTORE") {
+        if (!in({-1, 0, 1})) return false;
+        t.rgemm_estore = (int)v;
+    } else if (k == "GQ_SGEMM_FULL") {
         t.sgemm_full = v < 0 ? -1 : (v != 0);
     } else if (k == "GQ_CUS") {
         if (v < 0 || v > 1024) return false;
@@ -83,7 +86,7 @@ void tuning_from_env(Tuning &t)
     static const char *const keys[] = {"GQ_BLAS_MIN_TOKENS", "GQ_GEMM_MAX_BYTES", "GQ_GEMM_I8", "GQ_NO_FUSED_DECODE",
                                        "GQ_DECODE_Q6_IMG", "GQ_DECODE_F8_ITC", "GQ_GEMM_AQ", "GQ_GEMM_RG", "GQ_GEMM_SPLITS",
                                        "GQ_GEMM_PARTIAL", "GQ_SKINNY", "GQ_SKINNY_RG", "GQ_RGEMM", "GQ_SGEMM",
-                                       "GQ_SGEMM_SPLITS", "GQ_SGEMM_STREAMK", "GQ_RGEMM_ILC", "GQ_SGEMM_FULL", "GQ_CUS",
+                                       "GQ_SGEMM_SPLITS", "GQ_SGEMM_STREAMK", "GQ_RGEMM_ILC", "GQ_RGEMM_ESTORE", "GQ_SGEMM_FULL", "GQ_CUS",
                                        "GQ_KSTREAM", "GQ_ABLATE"};
     for (const char *k : keys) {
         const char *e = getenv(k); // the only getenv of the library: once per process

@@ -35,12 +35,15 @@ namespace gq {
 #ifdef GQ_RGEMM_STAMPS // diagnostic build: per-wave timeline of rgemm_kernel (never the product)
 // [0] s_memrealtime at entry (100 MHz, chip-wide), [1] s_memtime at entry, then s_memtime at:
 // [2] loads issued, [3] x~ written (AQ), [4] past the activation barrier, [5] own half 0 landed,
-// [6] half 0 multiplied, [7] half 1 landed, [8] multiply done, [9] partial stores issued,
+// [6] half 0 multiplied, [7] half 1 landed, [8] multiply done (the early-store form: its last
+// token group's MFMAs; the earlier groups' stores are issued before it), [9] partial stores issued,
 // [10] stores complete, [11] s_memrealtime at the end; [12] workgroup id, [13] XCC id
 __device__ unsigned long long g_rstamps[65536][14];
 #define GQ_RST(i) (st[i] = __builtin_amdgcn_s_memtime())
+#define GQ_RST_PTR(i) (&st[i])
 #else
 #define GQ_RST(i) ((void)0)
+#define GQ_RST_PTR(i) nullptr
 #endif
 
 // polls of the in-launch combine that gave up (ilc_combine; gq_debug_sync_timeouts)
@@ -68,6 +71,10 @@ constexpr int RRG = 2;                // 16-row groups per wave
 constexpr int RBM = 16 * RW * RRG;    // 256 rows per tile
 constexpr int LDS_CAP = 160 * 1024;
 constexpr int kSpol = 16; // split-K partial stores write-through (sc1)
+// GQ_RGEMM_ESTORE's auto: the early-store form from this many token tiles (rgemm_estore) -- every
+// tile that has the form: the step at 32 / 64 / 128 tokens 11.17 / 12.57 / 16.39 -> 10.87 / 12.12 /
+// 15.65 us on Q8_0 4096^2 (profiles/r07/estore_egrp_ab.txt; per format: estore_ab.txt)
+constexpr int kEstoreAutoNb = 2;
 
 // The split's weights as two half-super-block images (K elements 0..127 and 128..255 of every
 // row), so that the multiply of the first half runs while the second half is still in flight.
@@ -408,48 +415,62 @@ __device__ __forceinline__ void ilc_combine(uint16_t *__restrict__ C, uint16_t *
     ilc_sum<NB>(C, P, M, N, ldc, (int64_t)id.x * RBM, (int64_t)id.y * BN, tile, gz, (int64_t)id.gx * id.gy * gz, gz, z,
                 gz);
 }
-template <int NB>
-__device__ __forceinline__ void store_tile(const f32x4 (&acc)[RRG][NB], uint16_t *__restrict__ C,
-                                           uint16_t *__restrict__ P, int64_t M, int64_t N, int64_t ldc, int spol,
-                                           const TileId &id)
+// Pieces of the epilogue, shared by store_tile and the early stores of rgemm_kernel's ES form.
+// The exponent of a wave's split-K partial from its lanes' max |acc|: the maximum over the wave
+// (DPP), e = its binary exponent - 14, clamped to [0, 126] (|value| * 2^-e < 2^15: a finite fp16)
+__device__ __forceinline__ int wave_exponent(float mx)
 {
-    constexpr int BN = 16 * NB;
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int g = lane >> 4, l16 = lane & 15;
-    const int64_t m0 = (int64_t)id.x * RBM, n0 = (int64_t)id.y * BN;
-    if (id.gz > 1) {
-        // split-K partial, gemm_kernel's fp16 form (its reduce kernel sums it): per (tile, split)
-        // a block of 256 x BN halves in accumulator order, each wave's values scaled by 2^-e
-        const int64_t tile = (int64_t)id.y * id.gx + id.x;
-        const int64_t bidx = tile * id.gz + id.z;
-        float mx = 0.f;
+    int m = __builtin_bit_cast(int, mx);
+    m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x111, 0xf, 0xf, true))));
+    m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x112, 0xf, 0xf, true))));
+    m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x114, 0xf, 0xf, true))));
+    m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x118, 0xf, 0xf, true))));
+    m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x142, 0xa, 0xf, true))));
+    m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x143, 0xc, 0xf, true))));
+    const uint32_t mb = (uint32_t)__builtin_amdgcn_readlane(m, 63);
+    const int E = (int)((mb >> 23) & 0xff) - 127;
+    return E - 14 > 0 ? (E - 14 < 127 ? E - 14 : 126) : 0;
+}
+template <int NB> __device__ __forceinline__ float tile_absmax(const f32x4 (&acc)[RRG][NB], int t0, int t1, float mx)
+{
 #pragma unroll
-        for (int rg = 0; rg < RRG; ++rg)
+    for (int rg = 0; rg < RRG; ++rg)
 #pragma unroll
-            for (int t = 0; t < NB; ++t)
+        for (int t = t0; t < t1; ++t)
 #pragma unroll
-                for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fabsf(acc[rg][t][i]));
-        int m = __builtin_bit_cast(int, mx);
-        m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x111, 0xf, 0xf, true))));
-        m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x112, 0xf, 0xf, true))));
-        m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x114, 0xf, 0xf, true))));
-        m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x118, 0xf, 0xf, true))));
-        m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x142, 0xa, 0xf, true))));
-        m = __builtin_bit_cast(int, fmaxf(__builtin_bit_cast(float, m), __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, m, 0x143, 0xc, 0xf, true))));
-        const uint32_t mb = (uint32_t)__builtin_amdgcn_readlane(m, 63);
-        const int E = (int)((mb >> 23) & 0xff) - 127;
-        const int e = E - 14 > 0 ? (E - 14 < 127 ? E - 14 : 126) : 0;
-        const float down = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);
+            for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fabsf(acc[rg][t][i]));
+    return mx;
+}
+// A workgroup's block of the split-K partial (gemm_kernel's fp16 form, summed by its reduce
+// kernel): per (tile, split) 256 x BN halves in accumulator order -- a 16-byte unit holds one
+// lane's values of two token tiles -- each wave's values scaled by 2^-e, the e's after all blocks.
+// SP: the store cache policy where the caller knows it at compile time (then no branch between the
+// stores), or -1: the constructor's.
+template <int NB, int SP = -1> struct PartBlock {
+    __amdgpu_buffer_rsrc_t prs;
+    uint32_t bo, eo; // byte offsets of the block and of this wave's exponent word
+    int spol;
+    __device__ __forceinline__ PartBlock(uint16_t *P, const TileId &id, int spol_) : spol(SP < 0 ? spol_ : SP)
+    {
+        constexpr int BN = 16 * NB;
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const int64_t bidx = ((int64_t)id.y * id.gx + id.x) * id.gz + id.z;
         const int64_t nblk = (int64_t)id.gx * id.gy * id.gz;
-        const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-            (void *)P, 0, (int)(uint32_t)(nblk * (RBM * BN * 2 + RW * 4)), 0x00020000);
-        const uint32_t bo = (uint32_t)(bidx * (RBM * BN * 2));
-        if (lane == 0) {
-            const uint32_t eo = (uint32_t)(nblk * (RBM * BN * 2) + (bidx * RW + wave) * 4);
-            if (spol == 2) __builtin_amdgcn_raw_buffer_store_b32((uint32_t)e, prs, eo, 0, 2);
-            else if (spol == 16) __builtin_amdgcn_raw_buffer_store_b32((uint32_t)e, prs, eo, 0, 16);
-            else __builtin_amdgcn_raw_buffer_store_b32((uint32_t)e, prs, eo, 0, 0);
-        }
+        prs = __builtin_amdgcn_make_buffer_rsrc((void *)P, 0, (int)(uint32_t)(nblk * (RBM * BN * 2 + RW * 4)), 0x00020000);
+        bo = (uint32_t)(bidx * (RBM * BN * 2));
+        eo = (uint32_t)(nblk * (RBM * BN * 2) + (bidx * RW + wave) * 4);
+    }
+    __device__ __forceinline__ void exponent(int e) const
+    {
+        if ((threadIdx.x & 63) != 0) return;
+        if (spol == 2) __builtin_amdgcn_raw_buffer_store_b32((uint32_t)e, prs, eo, 0, 2);
+        else if (spol == 16) __builtin_amdgcn_raw_buffer_store_b32((uint32_t)e, prs, eo, 0, 16);
+        else __builtin_amdgcn_raw_buffer_store_b32((uint32_t)e, prs, eo, 0, 0);
+    }
+    // token tiles [t0, t1) of both row groups, scaled by down = 2^-e (t0, t1 even unless NB == 1)
+    __device__ __forceinline__ void tiles(const f32x4 (&acc)[RRG][NB], int t0, int t1, float down) const
+    {
+        const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         auto pk = [down](const f32x4 &v) {
             return (u32x2){(uint32_t)f2h_bits(v[0] * down) | ((uint32_t)f2h_bits(v[1] * down) << 16),
                            (uint32_t)f2h_bits(v[2] * down) | ((uint32_t)f2h_bits(v[3] * down) << 16)};
@@ -463,7 +484,7 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[RRG][NB], uint16_t
                 else __builtin_amdgcn_raw_buffer_store_b64(pk(acc[rg][0]), prs, vo, 0, 0);
             } else {
 #pragma unroll
-                for (int uu = 0; uu < NB / 2; ++uu) {
+                for (int uu = t0 / 2; uu < t1 / 2; ++uu) {
                     const u32x2 lo = pk(acc[rg][2 * uu]), hi = pk(acc[rg][2 * uu + 1]);
                     const u32x4 w = {lo.x, lo.y, hi.x, hi.y};
                     const uint32_t vo = bo + 16u * (uint32_t)(((RRG * wave + rg) * (NB / 2) + uu) * 64 + lane);
@@ -473,14 +494,22 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[RRG][NB], uint16_t
                 }
             }
         }
-        return;
     }
+};
+// one split: token tiles [t0, t1) of both row groups as fp16 into C (rows and tokens clipped)
+template <int NB>
+__device__ __forceinline__ void store_c_tiles(const f32x4 (&acc)[RRG][NB], int t0, int t1, uint16_t *__restrict__ C,
+                                              int64_t M, int64_t N, int64_t ldc, const TileId &id)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int g = lane >> 4, l16 = lane & 15;
+    const int64_t m0 = (int64_t)id.x * RBM, n0 = (int64_t)id.y * (16 * NB);
 #pragma unroll
     for (int rg = 0; rg < RRG; ++rg) {
         const int64_t row = m0 + 16 * (RRG * wave + rg) + 4 * g;
         if (row >= M) continue;
 #pragma unroll
-        for (int t = 0; t < NB; ++t) {
+        for (int t = t0; t < t1; ++t) {
             const int64_t tok = n0 + 16 * t + l16;
             if (tok >= N) continue;
             const f32x4 v = acc[rg][t];
@@ -493,6 +522,105 @@ __device__ __forceinline__ void store_tile(const f32x4 (&acc)[RRG][NB], uint16_t
             }
         }
     }
+}
+template <int NB>
+__device__ __forceinline__ void store_tile(const f32x4 (&acc)[RRG][NB], uint16_t *__restrict__ C,
+                                           uint16_t *__restrict__ P, int64_t M, int64_t N, int64_t ldc, int spol,
+                                           const TileId &id)
+{
+    if (id.gz > 1) { // split-K partial
+        const int e = wave_exponent(tile_absmax<NB>(acc, 0, NB, 0.f));
+        const PartBlock<NB> pb(P, id, spol);
+        pb.exponent(e);
+        pb.tiles(acc, 0, NB, __builtin_bit_cast(float, (uint32_t)(127 - e) << 23));
+        return;
+    }
+    store_c_tiles<NB>(acc, 0, NB, C, M, N, ldc, id);
+}
+
+// The second half multiply (sub-stages 2, 3) and the epilogue of rgemm_kernel's early-store (ES)
+// form.  mul_substage walks K outermost, so every accumulator is final only at the last k-step and
+// the partial stores -- write-through, bound by their ack latency -- run after the last MFMA with
+// nothing under them.  Here the half's A fragments (both sub-stages, 8 x f16x8) are dequantized
+// first and the token tiles go outermost in groups of GQ_RGEMM_EGRP: a group's accumulators take
+// their four MFMAs in mul_substage's order -- (u2,s0), (u2,s1), (u3,s0), (u3,s1), the same operand
+// bits, each B fragment still read once and shared by both row groups -- and are stored at once,
+// under the next group's MFMAs.  The partial format scales a wave's values by 2^-e, e from the
+// maximum over ALL its tiles: the stores go out for e = 0 (down = 1: every |partial| < 2^15, any
+// realistic data) while the maximum is kept; only a wave whose e turns out > 0 waits for its
+// stores (two stores of one wave to one address may complete in either order) and writes every
+// unit again with the true scale.  Either way the bytes in memory are store_tile's.
+// mfma_done (the stamps build; else null): s_memtime once the last group's MFMAs have completed.
+#ifndef GQ_RGEMM_EGRP
+#define GQ_RGEMM_EGRP 2 // token tiles per group (A/B builds: -DGQ_RGEMM_EGRP=4)
+#endif
+template <int F, int NB, int SP>
+__device__ __forceinline__ void mul_half1_early(const uint8_t *wimg1, const uint8_t *xs2, f32x4 (&acc)[RRG][NB],
+                                                uint16_t *__restrict__ C, uint16_t *__restrict__ P, int64_t M,
+                                                int64_t N, int64_t ldc, const TileId &id,
+                                                unsigned long long *mfma_done)
+{
+    constexpr int BN = 16 * NB, GT = GQ_RGEMM_EGRP < NB ? GQ_RGEMM_EGRP : NB;
+    static_assert(GT % 2 == 0 && NB % GT == 0, "whole 16-byte units per group, whole groups per tile");
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 4, l16 = lane & 15;
+    f16x8 af[2][RRG][2];
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+        for (int rg = 0; rg < RRG; ++rg)
+            half_frags<F>(wimg1 + (16 * HImg<F>::NPH) * (16 * rg + l16), g, 2 + v, l16, af[v][rg]);
+    const PartBlock<NB, SP> pb(P, id, SP);
+    float mx = 0.f;
+    // (split: a constant of each call below, so that a form's groups are one straight run of code
+    // and a group's conversions and stores can be scheduled among the next group's MFMAs)
+    auto groups = [&](auto split) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t0 = 0; t0 < NB; t0 += GT) {
+#pragma unroll
+            for (int v = 0; v < 2; ++v) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    f16x8 bk[GT];
+#pragma unroll
+                    for (int t = 0; t < GT; ++t) {
+                        const int r = 16 * (t0 + t) + l16;
+                        bk[t] = *(const f16x8 *)(xs2 + v * (BN * 128) + 128 * r + 16 * ((4 * s + g) ^ act_swz(r)));
+                    }
+#pragma unroll
+                    for (int rg = 0; rg < RRG; ++rg)
+#pragma unroll
+                        for (int t = 0; t < GT; ++t)
+                            acc[rg][t0 + t] =
+                                __builtin_amdgcn_mfma_f32_16x16x32_f16(af[v][rg][s], bk[t], acc[rg][t0 + t], 0, 0, 0);
+                }
+            }
+            if (mfma_done != nullptr && t0 + GT == NB) {
+#pragma unroll
+                for (int rg = 0; rg < RRG; ++rg)
+#pragma unroll
+                    for (int t = 0; t < GT; ++t) asm volatile("" ::"v"(acc[rg][t0 + t]));
+                *mfma_done = __builtin_amdgcn_s_memtime();
+            }
+            if constexpr (decltype(split)::value) {
+                mx = tile_absmax<NB>(acc, t0, t0 + GT, mx);
+                pb.tiles(acc, t0, t0 + GT, 1.f);
+            } else {
+                store_c_tiles<NB>(acc, t0, t0 + GT, C, M, N, ldc, id);
+            }
+        }
+    };
+    if (id.gz == 1) { // one split: fp16 C, no exponent
+        groups(std::false_type{});
+        return;
+    }
+    groups(std::true_type{});
+    const int e = wave_exponent(mx);
+    if (e != 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        pb.tiles(acc, 0, NB, __builtin_bit_cast(float, (uint32_t)(127 - e) << 23));
+    }
+    pb.exponent(e);
 }
 
 // store_tile's one-split form with the output rows taken through a map (the sorted expert GEMM):
@@ -534,7 +662,8 @@ __device__ __forceinline__ void store_tile_rows(const f32x4 (&acc)[RRG][NB], uin
 // ilc_gx > 0: the in-launch combine (1-D grid of ilc_gx x ilc_gy tiles x the splits, ilc_tile;
 // P's partials stored sc1 and summed in this launch by ilc_combine); else the 3-D grid, the
 // partials summed by the reduce launch.
-template <int F, int NB, int AQ>
+// ES: the early-store form of the second half multiply and the epilogue (mul_half1_early).
+template <int F, int NB, int AQ, int ES = 0>
 __global__ __launch_bounds__(64 * RW) void rgemm_kernel(const uint8_t *__restrict__ A, const uint16_t *__restrict__ X,
                                                        int64_t ldx, uint16_t *__restrict__ C, uint16_t *__restrict__ P,
                                                        int64_t M, int64_t N, int64_t K, int64_t ldc, int spol,
@@ -659,33 +788,46 @@ __global__ __launch_bounds__(64 * RW) void rgemm_kernel(const uint8_t *__restric
     constexpr int H1N = (ABL & 1) ? 0 : G::WWI - G::H0I;
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(H1N) : "memory");
     GQ_RST(5);
+    static_assert(ES == 0 || (NB > 1 && ABL == 0), "the early-store form: two token tiles or more, no ablation");
+    auto half1_landed = [&]() __attribute__((always_inline)) { // before the second half: every DMA landed
+#ifdef GQ_RGEMM_STAMPS
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        for (int rg = 0; rg < RRG; ++rg)
+            for (int t = 0; t < NB; ++t) asm volatile("" ::"v"(acc[rg][t]));
+#endif
+        GQ_RST(6);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        GQ_RST(7);
+    };
+    if constexpr (ES != 0) {
+        // the first half as below; 5b + 6. the second half by token groups, each group's tiles
+        // stored as they become final ([8]: the last group's MFMAs done, its stores still to issue)
 #pragma unroll
-    for (int u = 0; u < 4 && !(ABL & 4); ++u) {
-        if (u == 2) { // the second half
-#ifdef GQ_RGEMM_STAMPS
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            for (int rg = 0; rg < RRG; ++rg)
-                for (int t = 0; t < NB; ++t) asm volatile("" ::"v"(acc[rg][t]));
-#endif
-            GQ_RST(6);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            GQ_RST(7);
+        for (int u = 0; u < 2; ++u) mul_substage<F, NB>(wimg, ximg + u * (G::BN * 128), u, acc, 0);
+        half1_landed();
+        static_assert(kSpol == 16, "the early stores take one policy, at compile time: the launches' and the combine's");
+        mul_half1_early<F, NB, kSpol>(wimg + 32 * G::HRB, ximg + 2 * (G::BN * 128), acc, C, P, M, N, ldc, tile,
+                                      GQ_RST_PTR(8));
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4 && !(ABL & 4); ++u) {
+            if (u == 2) half1_landed();
+            mul_substage<F, NB>(wimg + (u >> 1) * (32 * G::HRB), ximg + u * (G::BN * 128), u, acc, 0);
         }
-        mul_substage<F, NB>(wimg + (u >> 1) * (32 * G::HRB), ximg + u * (G::BN * 128), u, acc, 0);
-    }
 #ifdef GQ_RGEMM_STAMPS
-    for (int rg = 0; rg < RRG; ++rg)
-        for (int t = 0; t < NB; ++t) asm volatile("" ::"v"(acc[rg][t]));
+        for (int rg = 0; rg < RRG; ++rg)
+            for (int t = 0; t < NB; ++t) asm volatile("" ::"v"(acc[rg][t]));
 #endif
-    GQ_RST(8);
-    if constexpr ((ABL & 4) != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        GQ_RST(8);
+        if constexpr ((ABL & 4) != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-    // 6. epilogue
-    if constexpr ((ABL & 8) != 0) {
-        if (acc[0][0][0] == 1234.5f) C[0] = 0;
-        return;
+        // 6. epilogue
+        if constexpr ((ABL & 8) != 0) {
+            if (acc[0][0][0] == 1234.5f) C[0] = 0;
+            return;
+        }
+        store_tile<NB>(acc, C, P, M, N, ldc, ilc ? 16 : spol, tile);
     }
-    store_tile<NB>(acc, C, P, M, N, ldc, ilc ? 16 : spol, tile);
     if (ilc && tile.gz > 1) ilc_combine<NB>(C, P, M, N, ldc, tile, nonce);
 #ifdef GQ_RGEMM_STAMPS
     GQ_RST(9);
@@ -1292,27 +1434,36 @@ hipError_t launch_snb(const uint8_t *A, const uint16_t *X, uint16_t *C, void *P,
     return launch_gemm_reduce_f16(NB, RRG, (const uint16_t *)P, C, M, N, ldc, p.splits, p.tiles_m, p.tiles_n, s);
 }
 
-template <int F, int NB, int AQ>
-hipError_t launch_nb(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *P, const RGemmPlan &p,
+template <int F, int NB, int AQ, int ES>
+hipError_t launch_es(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *P, const RGemmPlan &p,
                      int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
     // workgroups a CU admits at once (the runtime's answer: registers as well as LDS)
     static const int occ = [] {
         int n = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, rgemm_kernel<F, NB, AQ>, 64 * RW, 0) == hipSuccess ? n : 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, rgemm_kernel<F, NB, AQ, ES>, 64 * RW, 0) == hipSuccess ? n : 0;
     }();
     const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n * p.splits;
     if (rgemm_ilc(F, p) && blocks <= (int64_t)num_cus() * occ) { // the split-K sum inside the launch: one kernel
-        rgemm_kernel<F, NB, AQ><<<dim3((unsigned)blocks), dim3(64 * RW), 0, s>>>(A, X, ldx, C, (uint16_t *)P, M, N, K, ldc,
-                                                                                 16, p.tiles_m, p.tiles_n);
+        rgemm_kernel<F, NB, AQ, ES><<<dim3((unsigned)blocks), dim3(64 * RW), 0, s>>>(A, X, ldx, C, (uint16_t *)P, M, N, K,
+                                                                                     ldc, 16, p.tiles_m, p.tiles_n);
         return hipGetLastError();
     }
     const dim3 grid((unsigned)p.tiles_m, (unsigned)p.tiles_n, (unsigned)p.splits);
-    rgemm_kernel<F, NB, AQ><<<grid, dim3(64 * RW), 0, s>>>(A, X, ldx, C, (uint16_t *)P, M, N, K, ldc, kSpol,
-                                                           0, 0);
+    rgemm_kernel<F, NB, AQ, ES><<<grid, dim3(64 * RW), 0, s>>>(A, X, ldx, C, (uint16_t *)P, M, N, K, ldc, kSpol, 0, 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.splits == 1) return e;
     return launch_gemm_reduce_f16(NB, RRG, (const uint16_t *)P, C, M, N, ldc, p.splits, p.tiles_m, p.tiles_n, s);
+}
+
+// the early-store form by template parameter, so that the classic form's registers stay its own
+template <int F, int NB, int AQ>
+hipError_t launch_nb(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *P, const RGemmPlan &p,
+                     int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
+{
+    if constexpr (NB > 1 && ABL == 0)
+        if (rgemm_estore(NB)) return launch_es<F, NB, AQ, 1>(A, X, ldx, C, P, p, M, N, K, ldc, s);
+    return launch_es<F, NB, AQ, 0>(A, X, ldx, C, P, p, M, N, K, ldc, s);
 }
 
 template <int F, int AQ>
@@ -1370,6 +1521,15 @@ bool rgemm_ilc(int fmt, const RGemmPlan &p)
 {
     if (!p.ok || p.splits < 2 || tuning().rgemm_ilc == 0) return false;
     return (int64_t)p.tiles_m * p.tiles_n * p.splits <= (int64_t)num_cus() * rgemm_per_cu(fmt, p.nb);
+}
+
+// The early-store form of the resident GEMM (rgemm_kernel's ES; mul_half1_early) at nb token tiles.
+// GQ_RGEMM_ESTORE: 1 wherever the kernel has it (two token tiles or more), 0 the classic epilogue
+// everywhere, -1 the token tiles where it measured faster (kEstoreAutoNb).
+bool rgemm_estore(int nb)
+{
+    const int v = tuning().rgemm_estore;
+    return nb > 1 && (v < 0 ? nb >= kEstoreAutoNb : v != 0);
 }
 
 bool sgemm_ilc(const RGemmPlan &p)
