@@ -285,17 +285,22 @@ bool use_kstream(int t, int form, int64_t M, int64_t N, int64_t K, int act, bool
     // 23.98) -- profiles/r05/raw_kstream_ab.txt
     return act == GQ_ACT_Q8_1 && N <= 16 && M >= 8192;
 }
-// its 32-bit buffer offsets over the activations (rows ldx apart) and the output (rows ldc apart)
-bool kstream_fits(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldc)
+// its 32-bit buffer offsets over the activations (rows ldx apart) and the output (rows ldc apart),
+// and its 8-byte buffer stores of four outputs at C + tok*ldc + row (row % 4 == 0): aligned only
+// with ldc % 4 == 0 and C on an 8-byte boundary (c_aligned; c8()).  Every other C takes the call's
+// next route, whose epilogues are plain global stores.
+bool c8(const void *C) { return ((uintptr_t)C & 7) == 0; }
+bool kstream_fits(int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldc, bool c_aligned)
 {
-    return ((N - 1) * ldx + K) * 2 < ((int64_t)1 << 31) && ((N - 1) * ldc + M) * 4 < ((int64_t)1 << 31) && ldc % 4 == 0;
+    return ((N - 1) * ldx + K) * 2 < ((int64_t)1 << 31) && ((N - 1) * ldc + M) * 4 < ((int64_t)1 << 31) && ldc % 4 == 0 &&
+           c_aligned;
 }
 // An item of a grouped launch (gq_mmq_grouped_ex, gq_mmq_grouped_prepared): the stream wherever
 // it applies (the prepared rule; split: K ranges allowed)
-bool grouped_kstream_item(int t, int act, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldc, bool split,
-                          const Tuning &u)
+bool grouped_kstream_item(int t, int act, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldc, const void *C,
+                          bool split, const Tuning &u)
 {
-    return use_kstream(t, AF_F16, M, N, K, act, true, split, u) && kstream_fits(M, N, K, ldx, ldc);
+    return use_kstream(t, AF_F16, M, N, K, act, true, split, u) && kstream_fits(M, N, K, ldx, ldc, c8(C));
 }
 
 // Streaming 256-row GEMM (mmq_rgemm.hip sgemm_kernel) on the prepared x~, where the resident
@@ -404,17 +409,18 @@ size_t act_bytes(int act, int64_t N, int64_t K) { return carve(act, nullptr, N, 
 
 // One call as the planner sees it.  A raw call (gq_mmq_ex) is routed by the strides and the
 // alignment of its activations too; a shape-only query (the workspace sizes, gq_debug_route)
-// assumes what shape_call() fills in: contiguous rows, B 16-byte aligned.
+// assumes what shape_call() fills in: contiguous rows, B 16-byte aligned, C 8-byte aligned.
 struct Call {
     int t, act;
     int64_t M, N, K;
     bool prepared;   // gq_mmq_prepared: x~ is in the workspace as gq_act_prepare wrote it
     int64_t ldb, ldc;
     bool b_aligned;  // raw: 16-byte rows (ldb % 8 == 0, B & 15 == 0), what the in-kernel quantizers load
+    bool c_aligned;  // C & 7 == 0 (kstream_fits)
 };
 Call shape_call(int t, int act, int64_t M, int64_t N, int64_t K, bool prepared)
 {
-    return Call{t, act, M, N, K, prepared, K, M, true};
+    return Call{t, act, M, N, K, prepared, K, M, true, true};
 }
 
 // The kernel family (gq_debug_route: route_name()).  K_NONE: nothing to run (M or N zero) or no
@@ -481,7 +487,7 @@ Plan plan_call(const Call &c, const Tuning &u)
         rgemm = use_rgemm(t, p.form, M, N, K, u, rg);
         sgemm = use_sgemm(t, p.form, M, N, K, u);
         kstream = use_kstream(t, p.form, M, N, K, act, c.prepared, false, u) &&
-                  kstream_fits(M, N, K, c.prepared ? K : c.ldb, c.ldc);
+                  kstream_fits(M, N, K, c.prepared ? K : c.ldb, c.ldc, c.c_aligned);
         if (sgemm) {
             streamk = p.rows >= M && sgemm_streamk(t, M, N, K, u, p.item, p.sg);
             sg = plan_sgemm(M, N, K, u.sgemm_splits);
@@ -892,7 +898,7 @@ static int run_prepared(gq_type t, int act, const void *A, void *workspace, size
 {
     if (!A || !C || !workspace) return fail(GQ_EINVAL, "null pointer (A=%p C=%p workspace=%p)", A, C, workspace);
     if (ldc < M) return fail(GQ_EINVAL, "ldc=%lld < M=%lld", (long long)ldc, (long long)M);
-    const gq::Call c{t, act, M, N, K, true, K, ldc, true};
+    const gq::Call c{t, act, M, N, K, true, K, ldc, true, gq::c8(C)};
     const gq::Plan p = gq::plan_call(c, gq::tuning());
     if (workspace_bytes < p.ws_bytes()) return fail_workspace(workspace, workspace_bytes, p.ws_bytes());
     return launch_plan(c, p, A, nullptr, workspace, C, s);
@@ -909,7 +915,7 @@ int gq_mmq_ex(gq_type t, gq_act act, const void *A, const void *B, void *C, int6
     if (!A || !B || !C) return fail(GQ_EINVAL, "null pointer (A=%p B=%p C=%p)", A, B, C);
     if (ldc < M) return fail(GQ_EINVAL, "ldc=%lld < M=%lld", (long long)ldc, (long long)M);
     if (ldb < K) return fail(GQ_EINVAL, "ldb=%lld < K=%lld", (long long)ldb, (long long)K);
-    const gq::Call c{t, act, M, N, K, false, ldb, ldc, ldb % 8 == 0 && ((uintptr_t)B & 15) == 0};
+    const gq::Call c{t, act, M, N, K, false, ldb, ldc, ldb % 8 == 0 && ((uintptr_t)B & 15) == 0, gq::c8(C)};
     const gq::Plan p = gq::plan_call(c, gq::tuning());
     const size_t need = p.ws_bytes();
     if (need && (!workspace || workspace_bytes < need)) return fail_workspace(workspace, workspace_bytes, need);
@@ -1118,7 +1124,7 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
         for (int i = 0; i < m; ++i) {
             const gq::DecodeItem &d = di[i];
             // (the grouped launch's own route: the stream wherever it applies, GQ_KSTREAM=0 refuses)
-            if (!gq::grouped_kstream_item(d.fmt, act, d.M, N, d.K, d.ldx, d.ldc, false, gq::tuning()) ||
+            if (!gq::grouped_kstream_item(d.fmt, act, d.M, N, d.K, d.ldx, d.ldc, d.C, false, gq::tuning()) ||
                 gq::kstream_splits(d.K) > 1 || d.ldx % 8 != 0 || ((uintptr_t)d.X & 15) != 0)
                 return fail(GQ_EUNSUPPORTED, "item %d (%s): not a grouped K-chunked-stream shape (N=%lld, M=%lld, K=%lld)", i,
                             gq::type_info(d.fmt).name, (long long)N, (long long)d.M, (long long)d.K);
@@ -1349,7 +1355,7 @@ static void grouped_split(gq_act act, gq::SGroupItem *g, int n, int64_t N, gq::K
     for (int i = 0; i < n; ++i) {
         if (g[i].M <= 0) continue;
         const int np = gq::kstream_splits(g[i].K);
-        if (gq::grouped_kstream_item(g[i].fmt, act, g[i].M, N, g[i].K, g[i].K, g[i].ldc, true, gq::tuning()) &&
+        if (gq::grouped_kstream_item(g[i].fmt, act, g[i].M, N, g[i].K, g[i].K, g[i].ldc, g[i].C, true, gq::tuning()) &&
             parts + np <= gq::kKMaxParts && (parts += np, true))
             ks[nk++] = gq::KItem{g[i].fmt, g[i].A, g[i].X, g[i].K, g[i].C, g[i].ldc, g[i].M, g[i].K};
         else

@@ -121,6 +121,30 @@ size_t gq_mmq_call_workspace_size(gq_type t, gq_act act, int64_t M, int64_t N, i
  * workspace: >= gq_mmq_workspace_size(t, M, N, K) bytes of device memory
  *            (exactly: gq_mmq_call_workspace_size(t, GQ_ACT_Q8_1, M, N, K); NULL when that is 0).
  * Returns GQ_OK or an error code (gq_last_error() has the text; nothing was launched).
+ *
+ * Pointers and strides (gq_mmq[_ex], gq_act_prepare[_ex], gq_mmq_prepared[_ex], gq_dequantize,
+ * gq_quantize_q8_1, gq_quantize_fp8; tests/test_gpu_strides.py holds every dense route to this):
+ *   - B, C, W and X need fp16's 2-byte alignment and nothing more, and any row stride >= the row
+ *     length (ldb >= K, ldc >= M, ldw >= K, ldx >= K; shorter: GQ_EINVAL).  Only the row's own K
+ *     (M) elements are read (written): the ld - K pad columns, rows >= N and whatever lies in front
+ *     of the base are never read into a result, and the ld - M pad columns of C are never written.
+ *     A needs no alignment beyond its blocks' (a 16-byte load may read up to 15 bytes past its end).
+ *   - The result does not depend on ldc or on where C starts: every ldc and base give the bits of
+ *     ldc = M on an aligned base.  One exception, the K-chunked streaming MMQ, stores 8 bytes at a
+ *     time through a buffer resource and takes a call only with ldc % 4 == 0 and C on an 8-byte
+ *     boundary; any other C goes to the route the same call has under GQ_KSTREAM=0 (that call's
+ *     bits, within the GEMM tolerance of the stream's; a grouped launch refuses the item,
+ *     GQ_EUNSUPPORTED).  gq_debug_route sees the shape alone and reports the aligned call's kernel.
+ *   - 16-byte rows of B (B on a 16-byte boundary and ldb % 8 == 0) select the kernels that
+ *     quantize B inside their one launch (the K-chunked stream, the resident GEMM).  Any other B
+ *     is quantized by act_quant first and the call is gq_mmq_prepared's: the bits of
+ *     gq_act_prepare + gq_mmq_prepared on a contiguous copy.  The one-launch decode, the GEMV, the
+ *     LDS-DMA GEMM and everything that reads act_quant's output take any B, with the same bits.
+ *   - The workspace need does not depend on strides or alignment: exactly
+ *     gq_mmq_call_workspace_size (gq_mmq_workspace_size_ex for the split form) bytes suffice for
+ *     every case above, and nothing behind them is written.
+ *   - Not tested: a C that is not 8-byte aligned on the dequantize + hipBLASLt route (from
+ *     GQ_BLAS_MIN_TOKENS tokens); hipBLASLt is given ldc = M, M + 24 and M + 3 on aligned bases.
  */
 int gq_mmq(gq_type t, const void *A, const void *B, void *C, int64_t M, int64_t N, int64_t K, int64_t ldb,
            int64_t ldc, void *workspace, size_t workspace_bytes, void *stream);
@@ -251,7 +275,7 @@ int gq_mmq_sharded(gq_type t, const void *A_shard, const void *B, void *C, int64
  * output C (N x M, row stride ldc); items may share B.  N = 1..4: the streaming decode kernel,
  * every item's output bit-identical to its own gq_mmq call; N = 5..32: the K-chunked streaming
  * MMQ (every item bit-identical to its own gq_mmq_ex on that kernel, GQ_KSTREAM=1), which needs
- * K % 256 == 0, K <= 4096, M % 16 == 0, B 16-byte aligned and ldb % 8 == 0.  The chip's workgroups are split over the items by weight bytes.  No workspace, no host
+ * K % 256 == 0, K <= 4096, M % 16 == 0, B 16-byte aligned and ldb % 8 == 0, C 8-byte aligned and ldc % 4 == 0.  The chip's workgroups are split over the items by weight bytes.  No workspace, no host
  * sync.  GQ_EUNSUPPORTED (nothing launched) when N > 32, or an item is not a shape of that
  * launch (decode: activations that do not fit LDS, >= 2 GiB of weights, more than 16 parts =
  * item x token group; 5..32: the conditions above, more than 16 items): call gq_mmq per item then.

@@ -73,6 +73,13 @@ def test_raw_call_alignment_fallback(tune, knob, kernel, fmt):
         err = O.max_rel_err(got, ref)
         print(f"{fmt} {knob}=1 {M}x{N}x{K} {name}: max rel err {err:.3g}")
         assert err <= GEMM_TOL, (name, err)
+    # and every one of them against the oracle, at the GEMM gate of the type tests
+    import type_models as TM
+    want = O.mmq_from_fp16(fmt, random_blocks(fmt, M, K, seed=11), random_activations(N, K, seed=12), M, N, K, O.IDEAL)
+    for name, o in zip(("aligned", "ldb % 8 != 0", "B & 15 != 0"), outs):
+        err = TM.rel_err(o.cpu().numpy(), want)
+        print(f"{fmt} {knob}=1 {M}x{N}x{K} {name}: max|d|/max|C| = {err:.2e} vs the oracle")
+        assert err <= TM.tight(N), (name, err)
 
 
 def test_route_knobs(tune):
