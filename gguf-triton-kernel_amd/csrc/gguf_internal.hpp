@@ -225,10 +225,28 @@ hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A
                                 uint16_t *H, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K, int64_t ldb,
                                 int64_t ldb_slot, int64_t ldh, hipStream_t s);
 
+// Dense gate / up with SwiGLU (mmq_decode.hip; gq_mmq_glu): launch_decode_fused's grid, geometry and
+// token tile on two matrices of one type and shape, one launch, one activation prologue per
+// workgroup.  With g and u the fp16 values launch_decode_fused writes at this N from A_gate and
+// A_up, H[n*ldh + m] holds fp16(g / (1 + expf(-g)) * u), evaluated in fp32.
+// decode_glu_ok: N <= kGluMaxTokens, decode_fused_ok, one matrix < 2 GiB, a kernel exists for the
+// pick's cached chunks (the instantiations that would spill are left out) and the waves' stash of
+// g values fits the launch's LDS without costing a workgroup per CU.  The caller asks the call's
+// route first (gq_capi.hip plan_call: the one-launch decode).
+constexpr int kGluMaxTokens = 4;
+bool decode_glu_ok(int fmt, int64_t M, int64_t N, int64_t K);
+hipError_t launch_decode_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const uint16_t *X, int64_t ldx,
+                             uint16_t *H, int64_t M, int64_t N, int64_t K, int64_t ldh, hipStream_t s);
+
 // Router-weighted sum over slots (moe_combine.hip; gq_moe_combine): Y[n][m] = fp16(sum_s W[n*S+s] *
 // D[(n*S+s)*ldd + m]), the products and sums in fp32 in slot order, uncontracted; no atomics.
 hipError_t launch_moe_combine(const uint16_t *D, const void *W, bool w_f32, uint16_t *Y, int64_t N, int64_t S, int64_t M,
                               int64_t ldd, int64_t ldy, hipStream_t s);
+// The same with a shared expert's term after the slots (gq_moe_combine_shared): acc = acc + dsh, or
+// acc + gate[n] * dsh (uncontracted) when gate is not null; Dsh fp16, token n's M values at n*ldsh.
+hipError_t launch_moe_combine_shared(const uint16_t *D, const void *W, bool w_f32, const uint16_t *Dsh, int64_t ldsh,
+                                     const float *gate, uint16_t *Y, int64_t N, int64_t S, int64_t M, int64_t ldd,
+                                     int64_t ldy, hipStream_t s);
 
 // The router (moe_route.hip; gq_moe_topk, gq_moe_route), one launch each.
 //   launch_moe_topk: token n's S experts of largest key out of logits[n*ldl + e] (descending, the

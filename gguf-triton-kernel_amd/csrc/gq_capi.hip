@@ -1198,6 +1198,50 @@ int gq_mmq_id_glu(gq_type t, const void *A_gate, const void *A_up, const int32_t
                   "id glu decode");
 }
 
+int gq_mmq_glu(gq_type t, const void *A_gate, const void *A_up, const void *B, void *H, int64_t M, int64_t N, int64_t K,
+               int64_t ldb, int64_t ldh, void *stream)
+{
+    g_err.clear();
+    const int rc = check_mmq_shape(t, GQ_ACT_Q8_1, M, N, K);
+    if (rc != GQ_OK) return rc;
+    if (M == 0 || N == 0) return GQ_OK;
+    if (K == 0) return fail(GQ_EINVAL, "K must be positive");
+    if (!A_gate || !A_up || !B || !H)
+        return fail(GQ_EINVAL, "null pointer (A_gate=%p A_up=%p B=%p H=%p)", A_gate, A_up, B, H);
+    if (ldb < K) return fail(GQ_EINVAL, "ldb=%lld < K=%lld", (long long)ldb, (long long)K);
+    if (ldh < M) return fail(GQ_EINVAL, "ldh=%lld < M=%lld", (long long)ldh, (long long)M);
+    // gq_mmq's own route for the shape (the one-launch decode on the caller's activations), then the
+    // GLU form's limits
+    const gq::Plan p = gq::plan_call(gq::shape_call(t, GQ_ACT_Q8_1, M, N, K, false), gq::tuning());
+    if (N > gq::kGluMaxTokens || p.kernel != gq::K_DECODE || !p.raw || !gq::decode_glu_ok(t, M, N, K))
+        return fail(GQ_EUNSUPPORTED,
+                    "not a dense gate/up decode shape (N=%lld, at most %d; gq_mmq's route for M=%lld K=%lld must be the "
+                    "one-launch decode; a matrix < 2 GiB; a kernel without spills whose g stash fits LDS)",
+                    (long long)N, gq::kGluMaxTokens, (long long)M, (long long)K);
+    return hip_rc(gq::launch_decode_glu(t, (const uint8_t *)A_gate, (const uint8_t *)A_up, (const uint16_t *)B, ldb,
+                                        (uint16_t *)H, M, N, K, ldh, (hipStream_t)stream),
+                  "glu decode");
+}
+
+int gq_moe_combine_shared(const void *D, const void *W, int w_is_f32, const void *Dsh, int64_t ldsh, const float *gate,
+                          void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd, int64_t ldy, void *stream)
+{
+    g_err.clear();
+    if (N < 0 || S < 0 || M < 0) return fail(GQ_EINVAL, "negative size N=%lld S=%lld M=%lld", (long long)N, (long long)S, (long long)M);
+    if (S == 0) return fail(GQ_EINVAL, "S must be positive: with a shared term an empty slot sum is not a no-op");
+    if (N == 0 || M == 0) return GQ_OK;
+    if (!D || !W || !Dsh || !Y) return fail(GQ_EINVAL, "null pointer (D=%p W=%p Dsh=%p Y=%p)", D, W, Dsh, Y);
+    if (ldd < M) return fail(GQ_EINVAL, "ldd=%lld < M=%lld", (long long)ldd, (long long)M);
+    if (ldsh < M) return fail(GQ_EINVAL, "ldsh=%lld < M=%lld", (long long)ldsh, (long long)M);
+    if (ldy < M) return fail(GQ_EINVAL, "ldy=%lld < M=%lld", (long long)ldy, (long long)M);
+    if (S > gq::kMaxIdPairs || M > INT32_MAX)
+        return fail(GQ_EUNSUPPORTED, "not a combine shape (S=%lld, at most %d; M=%lld < 2^31)", (long long)S, gq::kMaxIdPairs,
+                    (long long)M);
+    return hip_rc(gq::launch_moe_combine_shared((const uint16_t *)D, W, w_is_f32 != 0, (const uint16_t *)Dsh, ldsh, gate,
+                                                (uint16_t *)Y, N, S, M, ldd, ldy, (hipStream_t)stream),
+                  "moe combine shared");
+}
+
 int gq_moe_combine(const void *D, const void *W, int w_is_f32, void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd,
                    int64_t ldy, void *stream)
 {

@@ -189,14 +189,18 @@ __device__ __forceinline__ void act_from_lds(Act<F, NT> &a, const uint8_t *codes
 // and widens them back (gguf_q8_1.hpp f8_quad: the bytes act_quant's F8DEQ form writes), the
 // LDS image is fp16 x~ + the x~ sums of every 16-element quarter, and the units multiply by
 // v_dot2_f32_f16 (gguf_dot.hpp dot_unit_h); no register cache of activations (ITC = 0).
-// GLU = 1 (stream_decode_id_glu_kernel, one token): two matrices A (gate) and A2 (up) of one type
-// and shape against the same activations, C = fp16(silu(g) * u) of their fp16 outputs g and u.
+// GLU = 1 (stream_decode_id_glu_kernel: one token) and GLU = 2 (stream_decode_glu_kernel: the dense
+// call's NT; the same form under a value of its own, so that its one-token instantiations are not
+// the expert-indexed kernels' -- sharing them gives this body's lambdas a second caller, which
+// changes what the inliner does with them and so the expert-indexed kernels' code):
+// two matrices A (gate) and A2 (up) of one type and shape against the same activations,
+// C = fp16(silu(g) * u) of their fp16 outputs g and u.
 // Every wave's task list is doubled -- task (row group, segment) of A, then the same task of A2,
 // through the same ring, the buffer resource chosen by the task's parity -- behind one activation
 // prologue.  The lane that would store a row's g keeps its fp16 bits in the wave's LDS stash
-// (stash_rows uint16 per wave from smem + stash_off, indexed by the row within the task) and, one
-// task later, the same lane holds the same row's u: it reads its own g back and stores the
-// product.  No lane reads another's entry, so no barrier.
+// (NT * stash_rows uint16 per wave from smem + stash_off: token t's entry of row r within the task
+// at t * stash_rows + r) and, one task later, the same lane holds the same row's u: it reads its
+// own g back and stores the product.  No lane reads another's entry, so no barrier.
 template <int F, int NT, int ITC, int IM = 0, int FP8 = 0, int GLU = 0>
 __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const uint16_t *__restrict__ X, int64_t ldx,
                                             uint16_t *__restrict__ C, int M, int64_t N, int K, int64_t ldc,
@@ -204,7 +208,7 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                                             const uint8_t *__restrict__ A2 = nullptr, int stash_off = 0,
                                             int stash_rows = 0)
 {
-    static_assert(!GLU || (NT == 1 && !FP8), "the GLU form: one token, q8_1 activations");
+    static_assert(!GLU || !FP8, "the GLU form: q8_1 activations");
     using L = Layout<F>;
     constexpr int UPC = UPC_OF<F, NT>;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -235,7 +239,7 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
         __builtin_amdgcn_make_buffer_rsrc((void *)A, 0, (int)(((uint32_t)M * RB + 15u) & ~15u), 0x00020000);
     const __amdgpu_buffer_rsrc_t wrs2 = // GLU: the up matrix, the odd tasks' source
         __builtin_amdgcn_make_buffer_rsrc((void *)(GLU ? A2 : A), 0, (int)(((uint32_t)M * RB + 15u) & ~15u), 0x00020000);
-    uint16_t *stash = GLU ? (uint16_t *)(smem + stash_off) + wave * stash_rows : nullptr;
+    uint16_t *stash = GLU ? (uint16_t *)(smem + stash_off) + wave * (NT == 1 ? stash_rows : NT * stash_rows) : nullptr;
     constexpr bool IMG = F == Q6_K && IM != 0;
     const uint32_t RBI = IMG ? (uint32_t)(K / 256) * kImgSB : RB; // ring bytes per row
     // IMG: the source offset, from the task's first byte, of the piece this lane moves in DMA
@@ -455,6 +459,8 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
     for (int t = 0; t < NT; ++t) acc2[t] = 0.f;
     // GLU: a completed row sum v.  Gate task: its fp16 bits into the lane's stash entry.  Up task:
     // h = fp16(g / (1 + expf(-g)) * u) in fp32 from the two fp16 values, rounded once.
+    // (the stores below keep the one-token statements stream_decode_id_glu_kernel was built from
+    // beside the NT > 1 ones -- token t's entries stash_rows further -- so that its code stays)
     auto glu_out = [](bool up, uint16_t *slot, uint16_t *dst, float v) {
         const uint16_t hb = f2h_bits(v);
         if (!up) {
@@ -641,8 +647,10 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                     for (int t = 0; t < NT; ++t) {
                         const float v = wave_sum_dpp(a[t]);
                         a[t] = 0.f;
-                        if constexpr (GLU) {
+                        if constexpr (GLU && NT == 1) {
                             if (lane == 0 && t < ntok) glu_out(up, stash + r, C + (tok0 + t) * ldc + r0 + r, v);
+                        } else if constexpr (GLU) {
+                            if (lane == 0 && t < ntok) glu_out(up, stash + t * stash_rows + r, C + (tok0 + t) * ldc + r0 + r, v);
                         } else {
                             if (lane == 0 && t < ntok) C[(tok0 + t) * ldc + r0 + r] = f2h_bits(v);
                         }
@@ -653,8 +661,11 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                         float v = a[t];
                         for (int off = P >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
                         a[t] = 0.f;
-                        if constexpr (GLU) {
+                        if constexpr (GLU && NT == 1) {
                             if (lunit == 0 && r < nr && t < ntok) glu_out(up, stash + r, C + (tok0 + t) * ldc + r0 + r, v);
+                        } else if constexpr (GLU) {
+                            if (lunit == 0 && r < nr && t < ntok)
+                                glu_out(up, stash + t * stash_rows + r, C + (tok0 + t) * ldc + r0 + r, v);
                         } else {
                             if (lunit == 0 && r < nr && t < ntok) C[(tok0 + t) * ldc + r0 + r] = f2h_bits(v);
                         }
@@ -685,8 +696,10 @@ __device__ __forceinline__ void decode_body(const uint8_t *__restrict__ A, const
                 for (int t = 0; t < NT; ++t) {
                     const float v = wave_sum_dpp(acc[t]);
                     acc[t] = 0.f;
-                    if constexpr (GLU) {
+                    if constexpr (GLU && NT == 1) {
                         if (lane == 0 && t < ntok) glu_out(up, stash, C + (tok0 + t) * ldc + g, v);
+                    } else if constexpr (GLU) {
+                        if (lane == 0 && t < ntok) glu_out(up, stash + t * stash_rows, C + (tok0 + t) * ldc + g, v);
                     } else {
                         if (lane == 0 && t < ntok) C[(tok0 + t) * ldc + g] = f2h_bits(v);
                     }
@@ -1241,6 +1254,104 @@ bool plan_id_glu(int fmt, int64_t M, int64_t pairs, int64_t K, Pick &p, int &sta
     return lds <= (size_t)LDS_CAP && (int)(LDS_CAP / lds) == (int)(LDS_CAP / p.lds);
 }
 
+// ---- dense gate / up with SwiGLU (gq_mmq_glu) ----
+// stream_decode_kernel's grid, geometry and token tile -- pick(fmt, M, N, K), the plain call's -- on
+// two matrices of one type and shape: every workgroup runs decode_body's GLU form on A (gate) and A2
+// (up) and stores H = fp16(silu(g) * u) for its token group.  A row's arithmetic depends on F, NT
+// and K only, so g and u are the bits launch_decode_fused writes for A and for A2 at this N.
+// One kernel per (F, NT, ITC, IM), as the expert-indexed kernels.
+struct GluArgs {
+    const uint8_t *A, *A2;
+    const uint16_t *X;
+    uint16_t *H;
+    int64_t ldx, ldh, N;
+    int M, K;
+    int stash_off, stash_rows; // the waves' g stash: byte offset in LDS, uint16 entries per (wave, token)
+    DecodeGeom geo;
+};
+
+template <int F, int NT, int ITC, int IM>
+__global__ __launch_bounds__(DW * 64) void stream_decode_glu_kernel(const GluArgs a)
+{
+    extern __shared__ __attribute__((aligned(1024))) uint8_t smem[];
+    decode_body<F, NT, ITC, IM, 0, 2>(a.A, a.X, a.ldx, a.H, a.M, a.N, a.K, a.ldh, a.geo, (int)blockIdx.x, (int)gridDim.x,
+                                      (int)blockIdx.y, smem, a.A2, a.stash_off, a.stash_rows);
+}
+
+// The most cached chunks a dense GLU kernel exists for at one / two / four tokens: launch_f's caps
+// (itc_max) lowered where the GLU form -- the second matrix's partial sums and the stash address
+// beside the cached activations -- does not fit the register file (tools/spill_report.py; DESIGN.md,
+// "Dense GLU decode and shared experts").  A call whose pick() asks for more has no fused kernel:
+// decode_glu_ok refuses it.
+constexpr int kGluItc[kNumFmts][3] = {
+    {7, 4, 1}, // Q8_0
+    {7, 4, 1}, // Q4_K
+    {4, 1, 1}, // Q6_K
+    {6, 4, 1}, // Q5_K
+    {kQ3Itc1, kQ3Itc2, 1}, // Q3_K
+    {kQ2Itc1, kQ2Itc2, 1}, // Q2_K
+    {kQ40Itc1, kQ40Itc2, 1}, // Q4_0
+};
+constexpr int glu_itc_max(int fmt, int nt)
+{
+    const int i = nt == 1 ? 0 : (nt == 2 ? 1 : 2);
+    return known_fmt(fmt) ? (kGluItc[fmt][i] < itc_max(fmt, nt) ? kGluItc[fmt][i] : itc_max(fmt, nt)) : -1;
+}
+
+template <int F, int NT, int ITC, int IM = 0>
+hipError_t launch_glu_t(const GluArgs &a, const Pick &p, size_t lds, hipStream_t s)
+{
+    static bool attr = false; // raise the dynamic LDS limit once per instantiation
+    if (!attr) {
+        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_glu_kernel<F, NT, ITC, IM>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
+        if (e != hipSuccess) return e;
+        attr = true;
+    }
+    dim3 grid((unsigned)p.grid, (unsigned)((a.N + NT - 1) / NT)), block(DW * 64);
+    stream_decode_glu_kernel<F, NT, ITC, IM><<<grid, block, lds, s>>>(a);
+    return hipGetLastError();
+}
+
+// launch_f's q8_1 (NT, ITC, IM) set up to glu_itc_max
+template <int F>
+hipError_t launch_glu_f(const GluArgs &a, const Pick &p, size_t lds, hipStream_t s)
+{
+    auto tile = [&](auto nt, auto im) {
+        constexpr int NT = decltype(nt)::value, IM = decltype(im)::value;
+        return dispatch_upto<glu_itc_max(F, NT)>(p.itc, [&](auto itc) {
+            return launch_glu_t<F, NT, decltype(itc)::value, IM>(a, p, lds, s);
+        });
+    };
+    auto ring = [&](auto nt) {
+        if constexpr (F == Q6_K)
+            if (p.img) return tile(nt, ic<1>{});
+        return tile(nt, ic<0>{});
+    };
+    switch (p.nt) {
+    case 1: return ring(ic<1>{});
+    case 2: return ring(ic<2>{});
+    case 4: return ring(ic<4>{});
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// The dense GLU launch's plan: the plain call's pick and the LDS of plan_id_glu's rule -- the
+// launch's own image, then every wave's stash, one uint16 per (token of the tile, row of a task),
+// each token's rows rounded up to 16 bytes.  False: no such launch.
+bool plan_glu(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int &stash_off, int &stash_rows, size_t &lds)
+{
+    if (!known_fmt(fmt) || M < 1 || N < 1 || N > kGluMaxTokens) return false;
+    if (M * row_bytes(fmt, K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets: one launch per matrix
+    if (!decode_fused_ok(fmt, N, K) || !pick(fmt, M, N, K, p)) return false;
+    if (p.itc > glu_itc_max(fmt, p.nt)) return false; // (the instantiations that spill)
+    stash_rows = ((p.geo.nseg == 1 ? p.geo.G : 1) + 7) & ~7;
+    stash_off = (int)((p.lds + 15) & ~(size_t)15);
+    lds = (size_t)stash_off + (size_t)DW * p.nt * stash_rows * 2;
+    // (the workgroups per CU, hence the geometry, are the plain launch's: the stash may not cost one)
+    return lds <= (size_t)LDS_CAP && (int)(LDS_CAP / lds) == (int)(LDS_CAP / p.lds);
+}
+
 } // namespace
 
 bool decode_fused_ok(int fmt, int64_t N, int64_t K, bool fp8)
@@ -1487,6 +1598,34 @@ hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A
     a.gx = p.grid;
     a.geo = p.geo;
     return dispatch_fmt(fmt, [&](auto f) { return launch_id_glu_f<decltype(f)::value>(a, (int)pairs, p, lds, s); });
+}
+
+bool decode_glu_ok(int fmt, int64_t M, int64_t N, int64_t K)
+{
+    Pick p;
+    int off, rows;
+    size_t lds;
+    return plan_glu(fmt, M, N, K, p, off, rows, lds);
+}
+
+hipError_t launch_decode_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const uint16_t *X, int64_t ldx,
+                             uint16_t *H, int64_t M, int64_t N, int64_t K, int64_t ldh, hipStream_t s)
+{
+    Pick p;
+    GluArgs a{};
+    size_t lds;
+    if (!plan_glu(fmt, M, N, K, p, a.stash_off, a.stash_rows, lds)) return hipErrorInvalidValue;
+    a.A = A_gate;
+    a.A2 = A_up;
+    a.X = X;
+    a.H = H;
+    a.ldx = ldx;
+    a.ldh = ldh;
+    a.N = N;
+    a.M = (int)M;
+    a.K = (int)K;
+    a.geo = p.geo;
+    return dispatch_fmt(fmt, [&](auto f) { return launch_glu_f<decltype(f)::value>(a, p, lds, s); });
 }
 
 } // namespace gq

@@ -74,6 +74,8 @@ SIGNATURES = {
     "gq_mmq_id_sorted": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
     "gq_mmq_id_glu": ([_I, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_moe_combine": ([_P, _P, _I, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_mmq_glu": ([_I, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_moe_combine_shared": ([_P, _P, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_moe_topk": ([_P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _P], _I),
     "gq_moe_route": ([_P, _I, _P, _I64, _P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
@@ -515,6 +517,89 @@ def moe_combine(D: torch.Tensor, W: torch.Tensor, out: torch.Tensor | None = Non
         acc = torch.zeros((N, M), dtype=torch.float32, device=dev)
         for s in range(S):
             acc = acc + W[:, s, None].float() * D[:, s].float()
+        Y.copy_(acc.half())
+        return Y
+    _check(rc)
+    return Y
+
+
+def mmq_glu(gtype: int, A_gate: torch.Tensor, A_up: torch.Tensor, B: torch.Tensor, M: int, N: int, K: int,
+            out: torch.Tensor | None = None) -> torch.Tensor:
+    """Dense gate and up with SwiGLU (gq_mmq_glu): A_gate and A_up two packed (M, K) weights of one
+    type (mmq's A), B fp16 (N, K).  Returns (N, M) fp16 H = fp16(silu(g) * u), evaluated in fp32
+    from the fp16 g and u that mmq gives for A_gate and A_up at this N.  1..4 tokens where mmq's
+    route is the one-launch decode: one launch, the tokens quantized once for both weight streams.
+    Where the entry refuses the shape (GQ_EUNSUPPORTED: more than 4 tokens, a long K, a kernel that
+    is not built) the same definition is made from two mmq calls and torch ops."""
+    _check_weights(gtype, A_gate, M, K)
+    _check_weights(gtype, A_up, M, K)
+    _require_device(B, "B")
+    dev = A_gate.device
+    if A_up.device != dev or B.device != dev:
+        raise RuntimeError(f"A_gate on {dev} but A_up on {A_up.device} and B on {B.device}")
+    B = _check_acts(B, N, K)
+    C = _check_out(out, N, M, dev)
+    if M == 0 or N == 0:
+        return C
+    if N > 1 and B.stride(0) < K:
+        B = B.contiguous()
+    with torch.cuda.device(dev):
+        rc = lib().gq_mmq_glu(gtype, A_gate.data_ptr(), A_up.data_ptr(), B.data_ptr(), C.data_ptr(), M, N, K,
+                              max(B.stride(0), K), max(C.stride(0), M), _stream(dev))
+    if rc == GQ_EUNSUPPORTED:
+        C.copy_(glu_torch(mmq(gtype, A_gate, B, M, N, K), mmq(gtype, A_up, B, M, N, K)))
+        return C
+    _check(rc)
+    return C
+
+
+def moe_combine_shared(D: torch.Tensor, W: torch.Tensor, Dsh: torch.Tensor, gate: torch.Tensor | None = None,
+                       out: torch.Tensor | None = None) -> torch.Tensor:
+    """moe_combine plus a shared expert's term (gq_moe_combine_shared): D fp16 (N, S, M), W (N, S)
+    fp16 or fp32, Dsh fp16 (N, M) the shared expert's down output, gate None or N fp32 values (a
+    per-token gate of the shared term) -> fp16 (N, M),
+    Y[n] = fp16((sum_s W[n, s] * D[n, s]) + gate[n] * Dsh[n]) with every product and sum in fp32, the
+    slots in order and the shared term last, unfused -- one launch, deterministic.  More than 64
+    slots: the same definition with torch ops."""
+    _require_device(D, "D")
+    _require_device(W, "W")
+    _require_device(Dsh, "Dsh")
+    if D.dtype != torch.float16 or D.dim() != 3:
+        raise RuntimeError("D must be an fp16 (N, S, M) tensor")
+    N, S, M = D.shape
+    dev = D.device
+    if S < 1:
+        raise RuntimeError("moe_combine_shared needs at least one slot")
+    if tuple(W.shape) != (N, S) or W.device != dev:
+        raise RuntimeError(f"W is {tuple(W.shape)} on {W.device}, expected ({N}, {S}) on {dev}")
+    if Dsh.dtype != torch.float16 or tuple(Dsh.shape) != (N, M) or Dsh.device != dev:
+        raise RuntimeError(f"Dsh must be an fp16 ({N}, {M}) tensor on {dev}")
+    if gate is not None:
+        _require_device(gate, "gate")
+        if gate.numel() != N or gate.device != dev:
+            raise RuntimeError(f"gate has {gate.numel()} elements on {gate.device}, expected {N} on {dev}")
+        gate = gate.reshape(N).to(torch.float32).contiguous()
+    if W.dtype not in (torch.float16, torch.float32):
+        W = W.float()
+    W = W.contiguous()
+    Y = _check_out(out, N, M, dev)
+    if N * M == 0:
+        return Y
+    ldd = D.stride(1) if S > 1 else (D.stride(0) if N > 1 else M)
+    if (M > 1 and D.stride(2) != 1) or ldd < M or (S > 1 and N > 1 and D.stride(0) != S * ldd):
+        D = D.contiguous()
+        ldd = M
+    if (M > 1 and Dsh.stride(1) != 1) or (N > 1 and Dsh.stride(0) < M):
+        Dsh = Dsh.contiguous()
+    with torch.cuda.device(dev):
+        rc = lib().gq_moe_combine_shared(D.data_ptr(), W.data_ptr(), int(W.dtype == torch.float32), Dsh.data_ptr(),
+                                         max(Dsh.stride(0), M), gate.data_ptr() if gate is not None else None,
+                                         Y.data_ptr(), N, S, M, ldd, max(Y.stride(0), M), _stream(dev))
+    if rc == GQ_EUNSUPPORTED:
+        acc = torch.zeros((N, M), dtype=torch.float32, device=dev)
+        for s in range(S):
+            acc = acc + W[:, s, None].float() * D[:, s].float()
+        acc = acc + (Dsh.float() if gate is None else gate[:, None] * Dsh.float())
         Y.copy_(acc.half())
         return Y
     _check(rc)

@@ -20,6 +20,13 @@ MoERouter makes ids and weights on the device from the token's hidden state (gq_
 router product and the top-S selection, two launches), reading the gating function, the
 renormalisation, the scale and the selection bias from the file's metadata; MoEBlock is a router
 and its MoEFFN: MoEBlock.from_gguf(meta, tensors, layer).forward(x) is the FFN of a MoE layer.
+
+Shared experts (DeepSeek-V2/V3, Qwen-MoE, Llama-4: blk.<L>.ffn_{gate,up,down}_shexp.weight) are a
+dense SwiGLU FFN (kernels/ffn.py DenseFFN) whose output is added to the routed sum:
+MoEBlock(router, ffn, shared=..., shared_gate=...), or MoEBlock.from_gguf(..., shared_experts=True).
+With everything fused the decode block is seven launches: router 2, gq_mmq_id_glu, gq_mmq_id (down),
+gq_mmq_glu and gq_mmq (the shared expert), gq_moe_combine_shared; Qwen-MoE's per-token sigmoid gate
+of the shared term adds two.
 """
 from __future__ import annotations
 
@@ -27,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .ffn import DenseFFN
 
 
 class GGUFExperts:
@@ -74,21 +82,29 @@ class MoEFFN:
         one rounding fewer than the torch ops below), down, and the weighted sum over the slots in
         one launch (moe_combine: fp32 in slot order) -- three launches up to 64 pairs, fp16 out.
         A gate / up pair of different types has no fused kernel: the same h from two mmq_id calls."""
+        d = self.slots(x, ids)
+        if self.fused:
+            return _lib.moe_combine(d, weights)
+        return (weights[..., None] * d).sum(1)
+
+    def slots(self, x: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+        """The (N, S, hidden) down outputs of the chosen experts, before the weighted sum (forward's
+        own first part in either mode)."""
         if self.fused:
             if self.gate.gtype == self.up.gtype:
                 h = _lib.mmq_id_glu(self.gate.gtype, self.gate.A, self.up.A, ids, x, self.gate.E, self.gate.M, self.gate.K)
             else:
                 h = _lib.glu_torch(self.gate(x, ids), self.up(x, ids))
-            return _lib.moe_combine(self.down(h, ids), weights)
+            return self.down(h, ids)
         g, u = self.gate(x, ids), self.up(x, ids)
         h = torch.nn.functional.silu(g) * u
-        d = self.down(h, ids)
-        return (weights[..., None] * d).sum(1)
+        return self.down(h, ids)
 
     __call__ = forward
 
 
 SHARED_EXPERT_NAMES = ("ffn_gate_shexp", "ffn_up_shexp", "ffn_down_shexp")
+SHARED_GATE_NAME = "ffn_gate_inp_shexp"
 
 
 def _refuse_shared_experts(tensors: dict, layer: int):
@@ -124,7 +140,7 @@ class MoERouter:
         self.S, self.bias, self.func, self.norm, self.scale = int(S), bias, func, bool(norm), float(scale)
 
     @classmethod
-    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda"):
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", shared_experts: bool = False):
         """From read_gguf()'s metadata and tensors: blk.<layer>.ffn_gate_inp.weight (f32 or f16,
         GGUF dims (hidden, E)), the optional blk.<layer>.exp_probs_b.bias (f32, E) and, with arch =
         meta["general.architecture"],
@@ -137,8 +153,10 @@ class MoERouter:
         These key names, values and defaults are written from memory of llama.cpp; nothing here
         can check them against it.  In particular a Qwen-MoE file written without
         expert_weights_norm may want norm=False: build MoERouter(...) by hand when in doubt.
-        A layer that also holds shared-expert tensors raises NotImplementedError."""
-        _refuse_shared_experts(tensors, layer)
+        A layer that also holds shared-expert tensors raises NotImplementedError unless
+        shared_experts=True says that the caller computes their term (MoEBlock.from_gguf does)."""
+        if not shared_experts:
+            _refuse_shared_experts(tensors, layer)
         arch = meta.get("general.architecture")
         if not isinstance(arch, str):
             raise ValueError("the file's metadata has no general.architecture")
@@ -178,23 +196,76 @@ class MoERouter:
 class MoEBlock:
     """The whole FFN of a MoE layer: forward(x) = ffn(x, *router(x)), x (N, hidden) fp16 ->
     (N, hidden).  With MoEFFN(fused=True) five launches at decode (two for the router, three for
-    the experts), no host sync: graph-capturable, a replay routes the x it finds.  Shared experts
-    are not part of it."""
+    the experts), no host sync: graph-capturable, a replay routes the x it finds.
+    shared: a DenseFFN over the same hidden size, the layer's shared expert(s); its output is added
+    to the routed sum.  shared_gate: an (H,) or (1, H) vector v, Qwen-MoE's gate of the shared term:
+    token n's shared output is multiplied by sigmoid(x[n] . v), made in fp32 by the router entry
+    (kernels._lib.moe_route with one "expert", sigmoid gating, no renormalisation: its weights are
+    exactly that, and it falls back to torch by itself beyond 64 tokens or H % 32 != 0).
+    With a fused ffn the routed slots, the shared term and the gate meet in one launch
+    (moe_combine_shared: fp32, the slots in order, the shared term last, fp16 out); an unfused ffn
+    keeps torch lines: ffn(x, ids, w) + shared(x), the latter times the gate where there is one."""
 
-    def __init__(self, router: MoERouter, ffn: MoEFFN):
+    def __init__(self, router: MoERouter, ffn: MoEFFN, shared: DenseFFN | None = None,
+                 shared_gate: torch.Tensor | None = None):
         if router.E != ffn.gate.E or router.H != ffn.gate.K:
             raise ValueError(f"router is {router.E} x {router.H} but the experts are {ffn.gate.E} x (ffn, {ffn.gate.K})")
-        self.router, self.ffn = router, ffn
+        if shared is not None and (shared.gate.K != router.H or shared.down.M != router.H):
+            raise ValueError(f"the shared expert maps {shared.gate.K} -> {shared.down.M}, the block's hidden size is {router.H}")
+        if shared_gate is not None:
+            if shared is None:
+                raise ValueError("a shared_gate without a shared expert")
+            if shared_gate.numel() != router.H or shared_gate.dtype not in (torch.float32, torch.float16):
+                raise ValueError(f"shared_gate must hold hidden = {router.H} fp32 or fp16 values")
+            shared_gate = shared_gate.reshape(1, router.H).contiguous()
+        self.router, self.ffn, self.shared, self.shared_gate = router, ffn, shared, shared_gate
 
     @classmethod
-    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", fused: bool = True):
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", fused: bool = True,
+                  shared_experts: bool = False):
         """From read_gguf()'s metadata and tensors: MoERouter.from_gguf and MoEFFN.from_gguf of the
         layer.  A layer with shared-expert tensors (blk.<layer>.ffn_*_shexp.weight) raises
-        NotImplementedError: their output belongs in the sum and nothing here computes it."""
-        _refuse_shared_experts(tensors, layer)
-        return cls(MoERouter.from_gguf(meta, tensors, layer, device), MoEFFN.from_gguf(tensors, layer, device, fused=fused))
+        NotImplementedError: their output belongs in the sum and nothing here computes it --
+        unless shared_experts=True: then blk.<layer>.ffn_{gate,up,down}_shexp.weight (all three once
+        any is present; a layer without any has no shared expert) become the block's DenseFFN
+        (fused as the block), and the optional blk.<layer>.ffn_gate_inp_shexp.weight (f32 or f16,
+        hidden values) its shared_gate.  That last tensor name is written from memory of llama.cpp's
+        qwen2moe graph; nothing here can check it against it."""
+        if not shared_experts:
+            _refuse_shared_experts(tensors, layer)
+        router = MoERouter.from_gguf(meta, tensors, layer, device, shared_experts=shared_experts)
+        ffn = MoEFFN.from_gguf(tensors, layer, device, fused=fused)
+        shared = gate = None
+        if shared_experts and any(f"blk.{layer}.{n}.weight" in tensors for n in SHARED_EXPERT_NAMES):
+            for n in SHARED_EXPERT_NAMES:
+                if f"blk.{layer}.{n}.weight" not in tensors:
+                    raise ValueError(f"blk.{layer}.{n}.weight is missing: a shared expert needs its gate, up and down")
+            shared = DenseFFN.from_gguf(tensors, layer, SHARED_EXPERT_NAMES, device, fused=fused)
+            g = tensors.get(f"blk.{layer}.{SHARED_GATE_NAME}.weight")
+            if g is not None:
+                if g.type_name not in ("f32", "f16") or int(np.prod(g.dims)) != router.H:
+                    raise ValueError(f"{g.name}: expected {router.H} f32 or f16 values, got {g.type_name} dims {g.dims}")
+                np_dtype = np.float32 if g.type_name == "f32" else np.float16
+                gate = torch.from_numpy(np.array(g.data, dtype=np.uint8).view(np_dtype).reshape(1, router.H)).to(device)
+        return cls(router, ffn, shared, gate)
+
+    def token_gate(self, x: torch.Tensor) -> torch.Tensor | None:
+        """The (N,) fp32 gate of the shared term, sigmoid(x . shared_gate), or None without one."""
+        if self.shared_gate is None:
+            return None
+        _, g, _ = _lib.moe_route(self.shared_gate, x, 1, func="sigmoid", norm=False)
+        return g.reshape(-1)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.ffn(x, *self.router(x))
+        ids, w = self.router(x)
+        if self.shared is None:
+            return self.ffn(x, ids, w)
+        gate = self.token_gate(x)
+        if self.ffn.fused:
+            return _lib.moe_combine_shared(self.ffn.slots(x, ids), w, self.shared(x), gate)
+        sh = self.shared(x)
+        if gate is not None:
+            sh = gate[:, None] * sh
+        return self.ffn(x, ids, w) + sh
 
     __call__ = forward

@@ -23,6 +23,8 @@
  *   gq_mmq_id_sorted                    the same at any pair count: device-sorted expert GEMM (prefill)
  *   gq_mmq_id_glu                       gate and up of every pair with SwiGLU in one launch (decode)
  *   gq_moe_combine                      the router-weighted sum over a block's slots
+ *   gq_mmq_glu                          dense gate and up with SwiGLU in one launch (decode: a shared expert, a dense FFN)
+ *   gq_moe_combine_shared               that sum plus a shared expert's term
  *   gq_moe_topk                         a block's router selection: S expert ids and weights from fp32 logits
  *   gq_moe_route                        the router product and that selection, for decode
  */
@@ -399,6 +401,50 @@ int gq_mmq_id_glu(gq_type t, const void *A_gate, const void *A_up, const int32_t
  */
 int gq_moe_combine(const void *D, const void *W, int w_is_f32, void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd,
                    int64_t ldy, void *stream);
+
+/*
+ * Dense gate / up with SwiGLU at decode, ONE launch: the FFN of a dense model and the shared expert
+ * of a mixture-of-experts block.  The tokens are quantized once per workgroup and serve both
+ * weight streams.
+ *   A_gate, A_up : two packed M x K matrices of the same type `t`, each as gq_mmq's A.
+ *   B            : fp16 (N, K), row stride ldb >= K, no alignment beyond fp16's.
+ *   H            : fp16 (N, M), row stride ldh >= M.
+ * Defined result (gq_mmq_id_glu's definition): with g and u the fp16 values, bit for bit, that
+ * gq_mmq(t, A_gate | A_up, B, ..., M, N, K, ...) writes at this N under the default tuning,
+ *   H = fp16_rne( (float)g / (1 + expf(-(float)g)) * (float)u )
+ * evaluated in fp32 and rounded once.
+ * It takes 1 <= N <= 4 tokens (q8_1 activations) at the shapes where gq_mmq's own route for
+ * (t, M, N, K) is the one-launch decode, each matrix under 2 GiB.  GQ_EUNSUPPORTED launches
+ * nothing and leaves H untouched: N > 4; a K whose tokens do not fit the decode's LDS image (the
+ * GEMV shapes, e.g. 4 tokens at K >= 8960 for Q3_K); a matrix >= 2 GiB; a shape whose stash of g
+ * values would cost the launch a workgroup per CU; a shape whose kernel is not built because it
+ * would spill registers ("Dense GLU decode and shared experts").  The caller then
+ * makes the same result from two gq_mmq calls (kernels/_lib.py mmq_glu does).
+ * GQ_EINVAL: a null pointer, a negative size, ldb < K, ldh < M, K not a multiple of the block.
+ * M == 0 or N == 0: a no-op.  No workspace.  Asynchronous, no host sync, no allocation,
+ * graph-capturable.
+ * gq_version() did not change with it: a caller detects the entry by its symbol (dlsym).
+ */
+int gq_mmq_glu(gq_type t, const void *A_gate, const void *A_up, const void *B, void *H, int64_t M, int64_t N, int64_t K,
+               int64_t ldb, int64_t ldh, void *stream);
+
+/*
+ * gq_moe_combine with a shared expert's term, one launch:
+ *   D, W, w_is_f32, Y, ldd, ldy : exactly gq_moe_combine's.
+ *   Dsh  : fp16 (N, M), token n's M values at element n*ldsh (ldsh >= M) -- the shared expert's
+ *          down output.
+ *   gate : NULL, or N fp32 values in device memory (Qwen-MoE's per-token sigmoid gate).
+ * Y[n][m] = fp16_rne(acc): acc = 0.f; for s = 0..S-1 in that order acc = acc + w*d, the product and
+ * the sum each rounded to fp32 (gq_moe_combine's order); then acc = acc + dsh, or with a gate
+ * acc = acc + gate[n]*dsh, again a rounded product and a rounded sum (no fused multiply-add).
+ * Deterministic: one thread per output, no atomics.
+ * Any N, 1 <= S <= 64, M < 2^31.  N == 0 or M == 0: a no-op.  GQ_EINVAL: S == 0 (with a shared term
+ * an empty sum is not a no-op), a negative size, a null D, W, Dsh or Y, ldd, ldsh or ldy < M.
+ * GQ_EUNSUPPORTED (nothing launched): S > 64 or M >= 2^31.
+ * Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol.
+ */
+int gq_moe_combine_shared(const void *D, const void *W, int w_is_f32, const void *Dsh, int64_t ldsh, const float *gate,
+                          void *Y, int64_t N, int64_t S, int64_t M, int64_t ldd, int64_t ldy, void *stream);
 
 /*
  * The router's selection, one launch at any N: from each token's E fp32 logits to its S expert ids
