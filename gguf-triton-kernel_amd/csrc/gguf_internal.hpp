@@ -206,9 +206,10 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
 // kMaxIdPairs: every pair streams its expert's weights on its own share of the chip, so two pairs
 // that pick one expert read it twice; up to 8 tokens x top-8 that costs less than sorting the
 // pairs would, beyond it pairs sharing an expert should share one weight stream (a sorted GEMM,
-// not this kernel).  decode_id_ok: pairs <= kMaxIdPairs, the one-token fused decode fits
-// (decode_fused_ok(fmt, 1, K)) and one expert is < 2 GiB (32-bit buffer offsets; the whole tensor
-// may be larger) -- else the caller falls back.
+// not this kernel).  decode_id_ok: the launch's plan (mmq_decode.hip plan_id) succeeds -- pairs <=
+// kMaxIdPairs, the one-token fused decode fits (decode_fused_ok(fmt, 1, K)), one expert is < 2 GiB
+// (32-bit buffer offsets; the whole tensor may be larger) and the pairs' share of the chip picks the
+// one-token launch's kernel -- else the caller falls back.
 constexpr int kMaxIdPairs = 64;
 bool decode_id_ok(int fmt, int64_t M, int64_t pairs, int64_t K);
 hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const uint16_t *B, uint16_t *C, int64_t E,

@@ -771,11 +771,53 @@ size_t act_lds(int fmt, int nt, int64_t K, bool fp8 = false)
     return (size_t)nt * kp + (size_t)nt * nb * 4 * (has_sums(fmt) ? 3 : (has_mins(fmt) ? 2 : 1));
 }
 
-// the largest cached-chunk count ITC instantiated for (format, token tile) -- launch_f and
-// launch_id_f instantiate exactly 0..the cap; the fp8 form caches at one token only, at most two
-// units (64 VGPRs of x~ pairs)
+// the largest cached-chunk count ITC instantiated for (format, token tile); the fp8 form caches at
+// one token only, at most two units (64 VGPRs of x~ pairs)
 constexpr int fp8_itc_max(int fmt, int nt) { return nt == 1 ? fmt_info(fmt).fp8_itc : 0; }
 constexpr int itc_max(int fmt, int nt) { return fmt_info(fmt).itc[nt == 1 ? 0 : (nt == 2 ? 1 : 2)]; }
+// The most cached chunks a dense GLU kernel exists for at one / two / four tokens: the dense caps
+// (itc_max) lowered where the GLU form -- the second matrix's partial sums and the stash address
+// beside the cached activations -- does not fit the register file (tools/spill_report.py; DESIGN.md,
+// "Dense GLU decode and shared experts").  A call whose pick() asks for more has no fused kernel:
+// decode_glu_ok refuses it.
+constexpr int kGluItc[kNumFmts][3] = {
+    {7, 4, 1}, // Q8_0
+    {7, 4, 1}, // Q4_K
+    {4, 1, 1}, // Q6_K
+    {6, 4, 1}, // Q5_K
+    {kQ3Itc1, kQ3Itc2, 1}, // Q3_K
+    {kQ2Itc1, kQ2Itc2, 1}, // Q2_K
+    {kQ40Itc1, kQ40Itc2, 1}, // Q4_0
+};
+constexpr int glu_itc_max(int fmt, int nt)
+{
+    const int i = nt == 1 ? 0 : (nt == 2 ? 1 : 2);
+    return known_fmt(fmt) ? (kGluItc[fmt][i] < itc_max(fmt, nt) ? kGluItc[fmt][i] : itc_max(fmt, nt)) : -1;
+}
+
+// A decode family's kernels, said once: whether token tiles beyond one and the fp8 form exist, and
+// the most cached chunks at (type, token tile, form).  walk<Policy, F> instantiates exactly this set
+// -- both ring forms for Q6_K -- and instantiated<Policy> answers for a run-time Pick from the same
+// caps, so what a plan may ask for and what has a kernel cannot drift apart.
+struct DensePolicy {
+    static constexpr bool kTiles = true, kFp8 = true;
+    static constexpr int itc_cap(int fmt, int nt, bool fp8) { return fp8 ? fp8_itc_max(fmt, nt) : itc_max(fmt, nt); }
+};
+struct IdPolicy { // the expert-indexed kernels, plain and GLU: the dense one-token q8_1 set
+    static constexpr bool kTiles = false, kFp8 = false;
+    static constexpr int itc_cap(int fmt, int, bool) { return itc_max(fmt, 1); }
+};
+struct GluPolicy {
+    static constexpr bool kTiles = true, kFp8 = false;
+    static constexpr int itc_cap(int fmt, int nt, bool) { return glu_itc_max(fmt, nt); }
+};
+
+// workgroups of lds bytes one CU holds, and the chip: every decode plan's budget
+int wgs_per_cu(size_t lds) { return std::max(1, (int)(LDS_CAP / lds)); }
+int chip_wgs(size_t lds) { return num_cus() * wgs_per_cu(lds); }
+// the chip's workgroups shared evenly by the pairs of an expert-indexed launch (every pair streams
+// the same bytes), one workgroup each at least
+int pair_wgs(size_t lds, int64_t pairs) { return (int)std::max<int64_t>(1, chip_wgs(lds) / pairs); }
 
 // wgs: the workgroups the matrix gets (0: a launch of its own, the whole chip; a grouped launch
 // splits the chip's workgroups by weight bytes)
@@ -808,8 +850,7 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
     const int64_t upr = (K + 63) / 64;
     const int64_t cpr = upr / upc_of(fmt, p.nt); // lane chunks per row
     const int64_t cap = img ? NI * 1024 : NI * 1024 - 16;
-    const int per_cu = (int)(LDS_CAP / p.lds) > 0 ? (int)(LDS_CAP / p.lds) : 1;
-    int64_t W = (int64_t)num_cus() * per_cu * DW; // waves the chip holds (or the granted workgroups')
+    int64_t W = (int64_t)chip_wgs(p.lds) * DW; // waves the chip holds (or the granted workgroups')
     if (wgs > 0) W = (int64_t)wgs * DW;
     DecodeGeom &g = p.geo;
     if (RB <= cap) {
@@ -839,16 +880,16 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
     // units and 1 token (K <= 28672: the 70B ffn_down rows) -- no spills (kernel-resource-usage)
     const int64_t itc = (cpr + (1 << g.lp2) - 1) >> g.lp2, units = itc * (upr / cpr);
     p.itc = ((p.nt <= 2 && units <= (fmt == Q6_K ? 2 : 4)) || (p.nt == 1 && units <= 8)) ? (int)itc : 0;
-    // only the instantiated chunk counts (FmtInfo::itc: launch_f walks the same caps) -- e.g.
-    // K = 29568 at one token gives 8
-    if (p.itc > itc_max(fmt, p.nt)) p.itc = 0;
+    // only the instantiated chunk counts (FmtInfo::itc: DensePolicy's caps, which walk()
+    // instantiates) -- e.g. K = 29568 at one token gives 8
+    if (p.itc > DensePolicy::itc_cap(fmt, p.nt, false)) p.itc = 0;
     // four tokens, one unit per lane (K <= 4096): cached too (Q6_K 14336x4096 x4 27.7 -> 20.7 us,
     // profiles/r02/decode_nt4_cache_ab.txt)
     if (p.nt == 4 && units == 1)
         p.itc = 1;
     if (p.fp8) { // (cached x~ at one token: GQ_DECODE_F8_ITC=0 turns it off)
         const int64_t fitc = (cpr + (1 << g.lp2) - 1) >> g.lp2;
-        p.itc = p.nt == 1 && tuning().decode_f8_itc && fitc <= fp8_itc_max(fmt, 1) ? (int)fitc : 0;
+        p.itc = p.nt == 1 && tuning().decode_f8_itc && fitc <= DensePolicy::itc_cap(fmt, 1, true) ? (int)fitc : 0;
     }
     g.early = 0; // (1 / 2: the ring refilled under the quantization -- measured slower, profiles/r04/dec_early.txt)
     const int64_t waves = g.ngroups < W ? g.ngroups : W;
@@ -856,33 +897,38 @@ bool pick(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int wgs = 0)
     return true;
 }
 
-template <int F, int NT, int ITC, int IM = 0, int FP8 = 0>
-hipError_t launch_t(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, int64_t M, int64_t N, int64_t K,
-                    int64_t ldc, const Pick &p, hipStream_t s)
+// whether the family has a kernel for the pick: the run-time reading of what walk() instantiates
+template <class Policy> bool instantiated(int fmt, const Pick &p)
 {
-    static bool attr = false; // raise the dynamic LDS limit once per instantiation
+    if (p.nt != 1 && !(Policy::kTiles && (p.nt == 2 || p.nt == 4))) return false;
+    if (p.fp8 && !(Policy::kFp8 && !q8_1_only(fmt))) return false;
+    return p.itc >= 0 && p.itc <= Policy::itc_cap(fmt, p.nt, p.fp8);
+}
+
+// Every decode kernel's launch: DW waves per workgroup, the dynamic LDS limit raised once per kernel
+// instantiation.  The once-flag is per process, not per device -- a second device's first launch of
+// a kernel runs without the attribute set there; this is the one place to make it per device.
+template <auto Kernel, class... Args> hipError_t launch_kernel(dim3 grid, size_t lds, hipStream_t s, const Args &...args)
+{
+    static bool attr = false;
     if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_kernel<F, NT, ITC, IM, FP8>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
+        hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    dim3 grid((unsigned)p.grid, (unsigned)((N + NT - 1) / NT)), block(DW * 64);
-    stream_decode_kernel<F, NT, ITC, IM, FP8><<<grid, block, p.lds, s>>>(A, X, ldx, C, (int)M, N, (int)K, ldc, p.geo);
+    Kernel<<<grid, dim3(DW * 64), lds, s>>>(args...);
     return hipGetLastError();
 }
 
-// Every kernel pick() can ask for: itc 0..the cap pick() clamps by (itc_max / fp8_itc_max) at
-// each token tile, in both ring forms for Q6_K.  A chunk count beyond the cap has no kernel.
-template <int F>
-hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, int64_t M, int64_t N, int64_t K,
-                    int64_t ldc, const Pick &p, hipStream_t s)
+// The run-time pick as compile-time values: fn(ic<NT>, ic<ITC>, ic<IM>, ic<FP8>) for the family's
+// kernel of type F -- chunk counts 0..Policy::itc_cap at each token tile and form, in both ring forms
+// for Q6_K.  A pick outside the family's set (instantiated<Policy> is false) has no kernel:
+// hipErrorInvalidValue.
+template <class Policy, int F, class Fn> hipError_t walk(const Pick &p, Fn &&fn)
 {
     auto tile = [&](auto nt, auto im, auto fp8) {
-        constexpr int NT = decltype(nt)::value, IM = decltype(im)::value, FP8 = decltype(fp8)::value;
-        return dispatch_upto<FP8 ? fp8_itc_max(F, NT) : itc_max(F, NT)>(p.itc, [&](auto itc) {
-            return launch_t<F, NT, decltype(itc)::value, IM, FP8>(A, X, ldx, C, M, N, K, ldc, p, s);
-        });
+        constexpr int NT = decltype(nt)::value, FP8 = decltype(fp8)::value;
+        return dispatch_upto<Policy::itc_cap(F, NT, FP8 != 0)>(p.itc, [&](auto itc) { return fn(nt, itc, im, fp8); });
     };
     auto ring = [&](auto nt, auto fp8) {
         if constexpr (F == Q6_K)
@@ -890,16 +936,16 @@ hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *
         return tile(nt, ic<0>{}, fp8);
     };
     auto form = [&](auto nt) {
-        if constexpr (!q8_1_only(F))
+        if constexpr (Policy::kFp8 && !q8_1_only(F))
             if (p.fp8) return ring(nt, ic<1>{});
         return p.fp8 ? hipErrorInvalidValue : ring(nt, ic<0>{});
     };
-    switch (p.nt) {
-    case 1: return form(ic<1>{});
-    case 2: return form(ic<2>{});
-    case 4: return form(ic<4>{});
-    default: return hipErrorInvalidValue;
+    if (p.nt == 1) return form(ic<1>{});
+    if constexpr (Policy::kTiles) {
+        if (p.nt == 2) return form(ic<2>{});
+        if (p.nt == 4) return form(ic<4>{});
     }
+    return hipErrorInvalidValue;
 }
 
 // ---- grouped decode: several matrices (own type, activations, output) in one launch ----
@@ -1097,20 +1143,6 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_grouped_kernel(const Gr
 #undef GQ_GF
 }
 
-template <int NT, int FP8 = 0, int SET = 0>
-hipError_t launch_grouped_nt(GroupedArgs &a, int blocks, size_t lds, hipStream_t s)
-{
-    static bool attr = false;
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_grouped_kernel<NT, FP8, SET>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    stream_decode_grouped_kernel<NT, FP8, SET><<<dim3((unsigned)blocks), dim3(DW * 64), lds, s>>>(a);
-    return hipGetLastError();
-}
-
 // ---- expert-indexed decode (mul_mat_id): P = N*S (token, slot) pairs of one type, M and K ----
 // Pair p = n*S + s multiplies expert ids[p]'s matrix (E of them back to back at A, expert_bytes
 // apart) by its activation row B + n*ldb + s*ldb_slot into C + p*ldc.  Every pair gets gx
@@ -1144,34 +1176,6 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_id_kernel(const IdArgs 
     const int n = p / a.S, s = p - n * a.S;
     decode_body<F, 1, ITC, IM>(a.A + (int64_t)e * a.expert_bytes, a.B + (int64_t)n * a.ldb + (int64_t)s * a.ldb_slot,
                                a.ldb, Cp, a.M, 1, a.K, a.ldc, a.geo, bx, a.gx, 0, smem);
-}
-
-template <int F, int ITC, int IM = 0>
-hipError_t launch_id_t(const IdArgs &a, int pairs, size_t lds, hipStream_t s)
-{
-    static bool attr = false; // raise the dynamic LDS limit once per instantiation
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_id_kernel<F, ITC, IM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    stream_decode_id_kernel<F, ITC, IM><<<dim3((unsigned)(pairs * a.gx)), dim3(DW * 64), lds, s>>>(a);
-    return hipGetLastError();
-}
-
-// launch_f's one-token q8_1 kernels: itc 0..itc_max(F, 1), both ring forms for Q6_K
-template <int F>
-hipError_t launch_id_f(const IdArgs &a, int pairs, const Pick &p, hipStream_t s)
-{
-    auto ring = [&](auto im) {
-        return dispatch_upto<itc_max(F, 1)>(p.itc, [&](auto itc) {
-            return launch_id_t<F, decltype(itc)::value, decltype(im)::value>(a, pairs, p.lds, s);
-        });
-    };
-    if constexpr (F == Q6_K)
-        if (p.img) return ring(ic<1>{});
-    return ring(ic<0>{});
 }
 
 // ---- expert-indexed gate / up with SwiGLU (gq_mmq_id_glu) ----
@@ -1208,50 +1212,41 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_id_glu_kernel(const IdG
                                      a.stash_rows);
 }
 
-template <int F, int ITC, int IM = 0>
-hipError_t launch_id_glu_t(const IdGluArgs &a, int pairs, size_t lds, hipStream_t s)
+// The expert-indexed launches' plan: the one-token tile of a launch of its own (solo), then the same
+// tile on the pairs' share of the chip.  False: no such launch, the caller falls back.
+// The two picks cannot disagree today: pick()'s itc and img depend on (fmt, nt, K) only -- the lanes
+// per row and the image rule never read the workgroups granted -- and nt is 1 in both.  The check
+// stays: a pair's outputs are promised to be its one-token launch's bits, which needs the same kernel.
+bool plan_id(int fmt, int64_t M, int64_t pairs, int64_t K, Pick &p)
 {
-    static bool attr = false; // raise the dynamic LDS limit once per instantiation
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_id_glu_kernel<F, ITC, IM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    stream_decode_id_glu_kernel<F, ITC, IM><<<dim3((unsigned)(pairs * a.gx)), dim3(DW * 64), lds, s>>>(a);
-    return hipGetLastError();
-}
-
-// launch_id_f's (ITC, IM) set
-template <int F>
-hipError_t launch_id_glu_f(const IdGluArgs &a, int pairs, const Pick &p, size_t lds, hipStream_t s)
-{
-    auto ring = [&](auto im) {
-        return dispatch_upto<itc_max(F, 1)>(p.itc, [&](auto itc) {
-            return launch_id_glu_t<F, decltype(itc)::value, decltype(im)::value>(a, pairs, lds, s);
-        });
-    };
-    if constexpr (F == Q6_K)
-        if (p.img) return ring(ic<1>{});
-    return ring(ic<0>{});
-}
-
-// launch_decode_id's plan (the one-token pick on the pairs' share of the chip) and the GLU form's
-// LDS: the launch's own image, then every wave's stash -- one uint16 per row of a task (G rows;
-// a segmented row: one), rounded up to 16 bytes.  False: no such launch (the stash does not fit).
-bool plan_id_glu(int fmt, int64_t M, int64_t pairs, int64_t K, Pick &p, int &stash_off, int &stash_rows, size_t &lds)
-{
+    if (pairs < 1 || pairs > kMaxIdPairs || M < 1 || !known_fmt(fmt)) return false;
+    if (M * row_bytes(fmt, K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets within one expert
+    // (the solo pick succeeding is decode_fused_ok(fmt, 1, K): none of pick()'s refusals reads M, and
+    // one token is never split)
     Pick solo;
-    if (!decode_id_ok(fmt, M, pairs, K) || !pick(fmt, M, 1, K, solo)) return false;
-    const int per_cu = (int)(LDS_CAP / solo.lds) > 0 ? (int)(LDS_CAP / solo.lds) : 1;
-    const int64_t budget = (int64_t)num_cus() * per_cu;
-    const int wgs = (int)(budget / pairs > 1 ? budget / pairs : 1);
-    if (!pick(fmt, M, 1, K, p, wgs) || p.nt != 1 || p.itc != solo.itc || p.img != solo.img) return false;
-    stash_rows = ((p.geo.nseg == 1 ? p.geo.G : 1) + 7) & ~7;
-    stash_off = (int)((p.lds + 15) & ~(size_t)15);
-    lds = (size_t)stash_off + (size_t)DW * stash_rows * 2;
-    // (the workgroups per CU, hence the geometry, are the plain launch's: the stash may not cost one)
-    return lds <= (size_t)LDS_CAP && (int)(LDS_CAP / lds) == (int)(LDS_CAP / p.lds);
+    if (!pick(fmt, M, 1, K, solo) || !pick(fmt, M, 1, K, p, pair_wgs(solo.lds, pairs))) return false;
+    return p.itc == solo.itc && p.img == solo.img && instantiated<IdPolicy>(fmt, p);
+}
+
+// The GLU forms' LDS: the launch's own image, then every wave's stash -- one uint16 per (token of
+// the tile, row of a task: G rows; a segmented row: one), each token's rows rounded up to 16 bytes.
+// False: the stash does not fit, or costs a workgroup per CU (the workgroups per CU, hence the
+// geometry, are the plain launch's).
+struct Stash {
+    int off, rows; // byte offset in LDS, uint16 entries per (wave, token)
+    size_t lds;    // the launch's LDS with the stash
+};
+bool plan_stash(const Pick &p, int tokens, Stash &st)
+{
+    st.rows = ((p.geo.nseg == 1 ? p.geo.G : 1) + 7) & ~7;
+    st.off = (int)((p.lds + 15) & ~(size_t)15);
+    st.lds = (size_t)st.off + (size_t)DW * tokens * st.rows * 2;
+    return st.lds <= (size_t)LDS_CAP && wgs_per_cu(st.lds) == wgs_per_cu(p.lds);
+}
+
+bool plan_id_glu(int fmt, int64_t M, int64_t pairs, int64_t K, Pick &p, Stash &st)
+{
+    return plan_id(fmt, M, pairs, K, p) && plan_stash(p, 1, st);
 }
 
 // ---- dense gate / up with SwiGLU (gq_mmq_glu) ----
@@ -1278,78 +1273,14 @@ __global__ __launch_bounds__(DW * 64) void stream_decode_glu_kernel(const GluArg
                                       (int)blockIdx.y, smem, a.A2, a.stash_off, a.stash_rows);
 }
 
-// The most cached chunks a dense GLU kernel exists for at one / two / four tokens: launch_f's caps
-// (itc_max) lowered where the GLU form -- the second matrix's partial sums and the stash address
-// beside the cached activations -- does not fit the register file (tools/spill_report.py; DESIGN.md,
-// "Dense GLU decode and shared experts").  A call whose pick() asks for more has no fused kernel:
-// decode_glu_ok refuses it.
-constexpr int kGluItc[kNumFmts][3] = {
-    {7, 4, 1}, // Q8_0
-    {7, 4, 1}, // Q4_K
-    {4, 1, 1}, // Q6_K
-    {6, 4, 1}, // Q5_K
-    {kQ3Itc1, kQ3Itc2, 1}, // Q3_K
-    {kQ2Itc1, kQ2Itc2, 1}, // Q2_K
-    {kQ40Itc1, kQ40Itc2, 1}, // Q4_0
-};
-constexpr int glu_itc_max(int fmt, int nt)
-{
-    const int i = nt == 1 ? 0 : (nt == 2 ? 1 : 2);
-    return known_fmt(fmt) ? (kGluItc[fmt][i] < itc_max(fmt, nt) ? kGluItc[fmt][i] : itc_max(fmt, nt)) : -1;
-}
-
-template <int F, int NT, int ITC, int IM = 0>
-hipError_t launch_glu_t(const GluArgs &a, const Pick &p, size_t lds, hipStream_t s)
-{
-    static bool attr = false; // raise the dynamic LDS limit once per instantiation
-    if (!attr) {
-        hipError_t e = hipFuncSetAttribute((const void *)stream_decode_glu_kernel<F, NT, ITC, IM>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, LDS_CAP);
-        if (e != hipSuccess) return e;
-        attr = true;
-    }
-    dim3 grid((unsigned)p.grid, (unsigned)((a.N + NT - 1) / NT)), block(DW * 64);
-    stream_decode_glu_kernel<F, NT, ITC, IM><<<grid, block, lds, s>>>(a);
-    return hipGetLastError();
-}
-
-// launch_f's q8_1 (NT, ITC, IM) set up to glu_itc_max
-template <int F>
-hipError_t launch_glu_f(const GluArgs &a, const Pick &p, size_t lds, hipStream_t s)
-{
-    auto tile = [&](auto nt, auto im) {
-        constexpr int NT = decltype(nt)::value, IM = decltype(im)::value;
-        return dispatch_upto<glu_itc_max(F, NT)>(p.itc, [&](auto itc) {
-            return launch_glu_t<F, NT, decltype(itc)::value, IM>(a, p, lds, s);
-        });
-    };
-    auto ring = [&](auto nt) {
-        if constexpr (F == Q6_K)
-            if (p.img) return tile(nt, ic<1>{});
-        return tile(nt, ic<0>{});
-    };
-    switch (p.nt) {
-    case 1: return ring(ic<1>{});
-    case 2: return ring(ic<2>{});
-    case 4: return ring(ic<4>{});
-    default: return hipErrorInvalidValue;
-    }
-}
-
-// The dense GLU launch's plan: the plain call's pick and the LDS of plan_id_glu's rule -- the
-// launch's own image, then every wave's stash, one uint16 per (token of the tile, row of a task),
-// each token's rows rounded up to 16 bytes.  False: no such launch.
-bool plan_glu(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, int &stash_off, int &stash_rows, size_t &lds)
+// The dense GLU launch's plan: the plain call's pick, a kernel for it (GluPolicy: the instantiations
+// that spill are left out) and plan_stash's LDS.  False: no such launch.
+bool plan_glu(int fmt, int64_t M, int64_t N, int64_t K, Pick &p, Stash &st)
 {
     if (!known_fmt(fmt) || M < 1 || N < 1 || N > kGluMaxTokens) return false;
     if (M * row_bytes(fmt, K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets: one launch per matrix
     if (!decode_fused_ok(fmt, N, K) || !pick(fmt, M, N, K, p)) return false;
-    if (p.itc > glu_itc_max(fmt, p.nt)) return false; // (the instantiations that spill)
-    stash_rows = ((p.geo.nseg == 1 ? p.geo.G : 1) + 7) & ~7;
-    stash_off = (int)((p.lds + 15) & ~(size_t)15);
-    lds = (size_t)stash_off + (size_t)DW * p.nt * stash_rows * 2;
-    // (the workgroups per CU, hence the geometry, are the plain launch's: the stash may not cost one)
-    return lds <= (size_t)LDS_CAP && (int)(LDS_CAP / lds) == (int)(LDS_CAP / p.lds);
+    return instantiated<GluPolicy>(fmt, p) && plan_stash(p, p.nt, st);
 }
 
 } // namespace
@@ -1363,7 +1294,8 @@ bool decode_fused_ok(int fmt, int64_t N, int64_t K, bool fp8)
     // group streams the weights again), the GEMV path (activations quantized once to global,
     // weights streamed once) is taken instead: Q6_K 8192x28672 x4 140 -> 82 us, x2 74 -> 67,
     // Q4_K 4096x14336 x4 26.7 -> 22.6 (profiles/r02/decode_vs_gemv_long_k.txt)
-    return N <= 8 && pick(fmt, 1, N, K, p) && !p.lds_split;
+    // (pick()'s tile, form and chunk count depend on (fmt, N, K) only: the launch's kernel exists)
+    return N <= 8 && pick(fmt, 1, N, K, p) && !p.lds_split && instantiated<DensePolicy>(fmt, p);
 }
 
 hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, int64_t M,
@@ -1378,7 +1310,13 @@ hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int
         p.fp8 = fp8;
         if (!pick(fmt, m, N, K, p)) return hipErrorInvalidValue;
         hipError_t e = dispatch_fmt(fmt, [&](auto f) {
-            return launch_f<decltype(f)::value>(A + m0 * RB, X, ldx, C + m0, m, N, K, ldc, p, s);
+            constexpr int F = decltype(f)::value;
+            return walk<DensePolicy, F>(p, [&](auto nt, auto itc, auto im, auto f8) {
+                constexpr int NT = decltype(nt)::value;
+                return launch_kernel<stream_decode_kernel<F, NT, decltype(itc)::value, decltype(im)::value, decltype(f8)::value>>(
+                    dim3((unsigned)p.grid, (unsigned)((N + NT - 1) / NT)), p.lds, s, A + m0 * RB, X, ldx, C + m0, (int)m, N,
+                    (int)K, ldc, p.geo);
+            });
         });
         if (e != hipSuccess) return e;
     }
@@ -1451,8 +1389,7 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
         // once -- rounding every part up had put a few workgroups into a second round (a 7B layer:
         // 258 of 256), doubling the launch (44.5 -> 30.1 us at one token).  Weighting the bytes by
         // each format's large-matrix streaming rate measured 1-5% slower (grouped_alloc_ab.log).
-        const int per_cu = (int)(LDS_CAP / lds) > 0 ? (int)(LDS_CAP / lds) : 1;
-        const int budget = num_cus() * per_cu;
+        const int budget = chip_wgs(lds);
         int wg[kMaxGroup], used = 0;
         double frac[kMaxGroup];
         for (int j = 0; j < np; ++j) {
@@ -1495,8 +1432,7 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
             q.M = (int)items[i].M;
             q.K = (int)items[i].K;
             q.geo = p.geo;
-            if (p.itc > (fp8 ? fp8_itc_max(items[i].fmt, nt) : itc_max(items[i].fmt, nt)))
-                return hipErrorInvalidValue; // no kernel case
+            if (!instantiated<DensePolicy>(items[i].fmt, p)) return hipErrorInvalidValue; // no kernel case
             q.code = items[i].fmt * 16 + p.itc + (p.img ? 8 : 0);
             q.block0 = blocks;
             q.gx = p.grid;
@@ -1509,16 +1445,16 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
         if (set > 0 && nt == 1)
             for (int j = 0; j < np; ++j)
                 if (a.p[j].code % 8 > kGroupItc[set]) return hipErrorInvalidValue; // (decode_grouped_ok)
+        auto go = [&](auto tile, auto f8, auto st) {
+            return launch_kernel<stream_decode_grouped_kernel<decltype(tile)::value, decltype(f8)::value, decltype(st)::value>>(
+                dim3((unsigned)blocks), lds, s, a);
+        };
         hipError_t e;
         if (fp8) // (sets 1..: no fp8 form; decode_grouped_ok: at most two tokens)
-            e = set > 0 ? hipErrorInvalidValue
-                        : (nt == 1 ? launch_grouped_nt<1, 1>(a, blocks, lds, s) : launch_grouped_nt<2, 1>(a, blocks, lds, s));
+            e = set > 0 ? hipErrorInvalidValue : (nt == 1 ? go(ic<1>{}, ic<1>{}, ic<0>{}) : go(ic<2>{}, ic<1>{}, ic<0>{}));
         else
             e = dispatch_upto<kGroupSets - 1>(set, [&](auto st) {
-                constexpr int SET = decltype(st)::value;
-                return nt == 1   ? launch_grouped_nt<1, 0, SET>(a, blocks, lds, s)
-                       : nt == 2 ? launch_grouped_nt<2, 0, SET>(a, blocks, lds, s)
-                                 : launch_grouped_nt<4, 0, SET>(a, blocks, lds, s);
+                return nt == 1 ? go(ic<1>{}, ic<0>{}, st) : nt == 2 ? go(ic<2>{}, ic<0>{}, st) : go(ic<4>{}, ic<0>{}, st);
             });
         if (e != hipSuccess) return e;
     }
@@ -1527,9 +1463,8 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
 
 bool decode_id_ok(int fmt, int64_t M, int64_t pairs, int64_t K)
 {
-    if (pairs < 1 || pairs > kMaxIdPairs || M < 1 || !known_fmt(fmt)) return false;
-    if (M * row_bytes(fmt, K) >= ((int64_t)1 << 31)) return false; // 32-bit buffer offsets within one expert
-    return decode_fused_ok(fmt, 1, K);
+    Pick p;
+    return plan_id(fmt, M, pairs, K, p);
 }
 
 hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const uint16_t *B, uint16_t *C, int64_t E,
@@ -1537,15 +1472,8 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
                             hipStream_t s)
 {
     const int64_t pairs = N * S;
-    if (!decode_id_ok(fmt, M, pairs, K) || E < 1 || E > INT32_MAX) return hipErrorInvalidValue;
-    // the chip's workgroups shared evenly by the pairs (the grouped launcher's budget; every pair
-    // streams the same bytes), one workgroup each at least; the tile is the one-token launch's
-    Pick solo, p;
-    if (!pick(fmt, M, 1, K, solo)) return hipErrorInvalidValue;
-    const int per_cu = (int)(LDS_CAP / solo.lds) > 0 ? (int)(LDS_CAP / solo.lds) : 1;
-    const int64_t budget = (int64_t)num_cus() * per_cu;
-    const int wgs = (int)(budget / pairs > 1 ? budget / pairs : 1);
-    if (!pick(fmt, M, 1, K, p, wgs) || p.nt != 1 || p.itc != solo.itc || p.img != solo.img) return hipErrorInvalidValue;
+    Pick p;
+    if (E < 1 || E > INT32_MAX || !plan_id(fmt, M, pairs, K, p)) return hipErrorInvalidValue;
     IdArgs a{};
     a.A = A;
     a.ids = ids;
@@ -1561,15 +1489,19 @@ hipError_t launch_decode_id(int fmt, const uint8_t *A, const int32_t *ids, const
     a.S = (int)S;
     a.gx = p.grid;
     a.geo = p.geo;
-    return dispatch_fmt(fmt, [&](auto f) { return launch_id_f<decltype(f)::value>(a, (int)pairs, p, s); });
+    return dispatch_fmt(fmt, [&](auto f) {
+        return walk<IdPolicy, decltype(f)::value>(p, [&](auto, auto itc, auto im, auto) {
+            return launch_kernel<stream_decode_id_kernel<decltype(f)::value, decltype(itc)::value, decltype(im)::value>>(
+                dim3((unsigned)(pairs * a.gx)), p.lds, s, a);
+        });
+    });
 }
 
 bool decode_id_glu_ok(int fmt, int64_t M, int64_t pairs, int64_t K)
 {
     Pick p;
-    int off, rows;
-    size_t lds;
-    return plan_id_glu(fmt, M, pairs, K, p, off, rows, lds);
+    Stash st;
+    return plan_id_glu(fmt, M, pairs, K, p, st);
 }
 
 hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const int32_t *ids, const uint16_t *B,
@@ -1578,10 +1510,11 @@ hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A
 {
     const int64_t pairs = N * S;
     Pick p;
+    Stash st;
+    if (E < 1 || E > INT32_MAX || !plan_id_glu(fmt, M, pairs, K, p, st)) return hipErrorInvalidValue;
     IdGluArgs a{};
-    size_t lds;
-    if (E < 1 || E > INT32_MAX || !plan_id_glu(fmt, M, pairs, K, p, a.stash_off, a.stash_rows, lds))
-        return hipErrorInvalidValue;
+    a.stash_off = st.off;
+    a.stash_rows = st.rows;
     a.A = A_gate;
     a.A2 = A_up;
     a.ids = ids;
@@ -1597,24 +1530,30 @@ hipError_t launch_decode_id_glu(int fmt, const uint8_t *A_gate, const uint8_t *A
     a.S = (int)S;
     a.gx = p.grid;
     a.geo = p.geo;
-    return dispatch_fmt(fmt, [&](auto f) { return launch_id_glu_f<decltype(f)::value>(a, (int)pairs, p, lds, s); });
+    return dispatch_fmt(fmt, [&](auto f) {
+        return walk<IdPolicy, decltype(f)::value>(p, [&](auto, auto itc, auto im, auto) {
+            return launch_kernel<stream_decode_id_glu_kernel<decltype(f)::value, decltype(itc)::value, decltype(im)::value>>(
+                dim3((unsigned)(pairs * a.gx)), st.lds, s, a);
+        });
+    });
 }
 
 bool decode_glu_ok(int fmt, int64_t M, int64_t N, int64_t K)
 {
     Pick p;
-    int off, rows;
-    size_t lds;
-    return plan_glu(fmt, M, N, K, p, off, rows, lds);
+    Stash st;
+    return plan_glu(fmt, M, N, K, p, st);
 }
 
 hipError_t launch_decode_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const uint16_t *X, int64_t ldx,
                              uint16_t *H, int64_t M, int64_t N, int64_t K, int64_t ldh, hipStream_t s)
 {
     Pick p;
+    Stash st;
+    if (!plan_glu(fmt, M, N, K, p, st)) return hipErrorInvalidValue;
     GluArgs a{};
-    size_t lds;
-    if (!plan_glu(fmt, M, N, K, p, a.stash_off, a.stash_rows, lds)) return hipErrorInvalidValue;
+    a.stash_off = st.off;
+    a.stash_rows = st.rows;
     a.A = A_gate;
     a.A2 = A_up;
     a.X = X;
@@ -1625,7 +1564,13 @@ hipError_t launch_decode_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up
     a.M = (int)M;
     a.K = (int)K;
     a.geo = p.geo;
-    return dispatch_fmt(fmt, [&](auto f) { return launch_glu_f<decltype(f)::value>(a, p, lds, s); });
+    return dispatch_fmt(fmt, [&](auto f) {
+        return walk<GluPolicy, decltype(f)::value>(p, [&](auto nt, auto itc, auto im, auto) {
+            constexpr int NT = decltype(nt)::value;
+            return launch_kernel<stream_decode_glu_kernel<decltype(f)::value, NT, decltype(itc)::value, decltype(im)::value>>(
+                dim3((unsigned)p.grid, (unsigned)((N + NT - 1) / NT)), st.lds, s, a);
+        });
+    });
 }
 
 } // namespace gq
