@@ -239,6 +239,21 @@ bool decode_glu_ok(int fmt, int64_t M, int64_t N, int64_t K);
 hipError_t launch_decode_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up, const uint16_t *X, int64_t ldx,
                              uint16_t *H, int64_t M, int64_t N, int64_t K, int64_t ldh, hipStream_t s);
 
+// The decode plans as data (mmq_decode.hip; gq_debug_decode_plan, gq_debug_decode_cap): host only.
+// decode_plan_info: the launches the family's launcher would make, one entry per (launch part, token
+// group), from the launcher's own planning functions; returns their count (0: the family has no
+// one-launch decode for the call), filling at most max_out.  DF_DENSE launch_decode_fused, DF_ID /
+// DF_ID_GLU launch_decode_id[_glu] (N: the pairs), DF_GLU launch_decode_glu: items[0]'s fmt, M, K,
+// n == 1; DF_GROUPED launch_decode_grouped on the n items.  Pointers and strides are not read.
+// decode_itc_cap: the most cached chunks a kernel of the family exists for at (type, token tile,
+// form) -- set: the grouped kernel's case set -- or -1 when there is none at all.
+enum DecodeFamily : int { DF_DENSE = 0, DF_ID = 1, DF_ID_GLU = 2, DF_GLU = 3, DF_GROUPED = 4 };
+struct DecodePlanInfo { // (gq_decode_plan's fields, in its order)
+    int nt, itc, img, fp8, lds_split, nseg, G, lp2, grid, ngroups, stash_rows, tokens, set, item, lds;
+};
+int decode_plan_info(int family, const DecodeItem *items, int n, int64_t N, bool fp8, DecodePlanInfo *out, int max_out);
+int decode_itc_cap(int family, int set, int fmt, int nt, bool fp8);
+
 // Router-weighted sum over slots (moe_combine.hip; gq_moe_combine): Y[n][m] = fp16(sum_s W[n*S+s] *
 // D[(n*S+s)*ldd + m]), the products and sums in fp32 in slot order, uncontracted; no atomics.
 hipError_t launch_moe_combine(const uint16_t *D, const void *W, bool w_f32, uint16_t *Y, int64_t N, int64_t S, int64_t M,

@@ -1484,6 +1484,52 @@ int gq_mmq_sharded(gq_type t, const void *A_shard, const void *B, void *C, int64
 
 } // extern "C"
 
+// Each family's entry-point checks ahead of its launcher (gq_mmq_ex's route, gq_mmq_glu's, the id
+// entries' pair limits, gq_mmq_grouped_ex's token counts), then the launcher's own plan.
+int gq_debug_decode_plan(int family, gq_act act, const gq_group_item *items, int n, int64_t N, gq_decode_plan *out,
+                         int max_out)
+{
+    static_assert(sizeof(gq_decode_plan) == sizeof(gq::DecodePlanInfo), "gq_decode_plan is DecodePlanInfo");
+    g_err.clear();
+    if (n < 1 || n > 16 || !items || N < 1 || max_out < 0 || (max_out > 0 && !out)) return 0;
+    if (family != gq::DF_GROUPED && n != 1) return 0;
+    const bool fp8 = act == GQ_ACT_FP8_E4M3;
+    gq::DecodeItem di[16];
+    for (int i = 0; i < n; ++i) {
+        const gq_group_item &it = items[i];
+        // (the id families' N is the pair count: no part of the shape checks)
+        if (check_mmq_shape(it.type, act, it.M, family == gq::DF_GROUPED ? N : 1, it.K) != GQ_OK || it.M <= 0 || it.K <= 0) {
+            g_err.clear();
+            return 0;
+        }
+        di[i] = gq::DecodeItem{it.type, nullptr, nullptr, it.K, nullptr, it.M, it.M, it.K};
+    }
+    const gq::DecodeItem &d = di[0];
+    switch (family) {
+    case gq::DF_DENSE:
+    case gq::DF_GLU: {
+        const gq::Plan p = gq::plan_call(gq::shape_call(d.fmt, act, d.M, N, d.K, false), gq::tuning());
+        if (p.kernel != gq::K_DECODE || !p.raw) return 0;
+        if (family == gq::DF_GLU && (fp8 || N > gq::kGluMaxTokens)) return 0;
+        break;
+    }
+    case gq::DF_ID:
+    case gq::DF_ID_GLU:
+        if (fp8 || N > (int64_t)gq::kMaxIdPairs * gq::kMaxIdPairs) return 0;
+        break;
+    case gq::DF_GROUPED:
+        if (N >= (fp8 ? 3 : 5)) return 0; // (the K-chunked stream's token counts)
+        break;
+    default: return 0;
+    }
+    return gq::decode_plan_info(family, di, n, N, fp8, (gq::DecodePlanInfo *)out, max_out);
+}
+
+int gq_debug_decode_cap(int family, int set, gq_type t, int nt, int fp8)
+{
+    return gq::decode_itc_cap(family, set, t, nt, fp8 != 0);
+}
+
 const char *gq_debug_route(gq_type t, gq_act act, int64_t M, int64_t N, int64_t K, int prepared)
 {
     if (check_mmq_shape(t, act, M, N, K) != GQ_OK || M <= 0 || N <= 0 || K <= 0) return "none";

@@ -1347,6 +1347,116 @@ bool decode_grouped_ok(const DecodeItem *items, int n, int64_t N, bool fp8)
     return true;
 }
 
+namespace {
+
+// One launch of a grouped call: the items whose own token tile is nt, as the kernel's arguments.
+// (launch_decode_grouped launches it; decode_plan_info reports it.)
+struct GroupedLaunch {
+    GroupedArgs a;        // a.n == 0: no item takes this tile, nothing to launch
+    size_t lds;
+    int blocks, set;      // the grid; the kernel's case set
+    int item[kMaxGroup];  // part j's item
+};
+
+// solo: every item's pick as a launch of its own (its token tile)
+hipError_t plan_grouped(const DecodeItem *items, int n, int64_t N, bool fp8, const Pick *solo, int nt, GroupedLaunch &gl)
+{
+    gl = GroupedLaunch{};
+    // the launch's parts: (item, token group); its LDS is the largest part's
+    int *pi = gl.item, py[kMaxGroup], np = 0;
+    size_t lds = 0;
+    double bytes[kMaxGroup], total = 0;
+    for (int i = 0; i < n; ++i) {
+        if (solo[i].nt != nt) continue;
+        const int tg = (int)((N + nt - 1) / nt);
+        for (int y = 0; y < tg; ++y) {
+            if (np == kMaxGroup) return hipErrorInvalidValue;
+            pi[np] = i;
+            py[np] = y;
+            // Q6_K bytes weigh more at 1-2 tokens (their unpacking costs more per byte than
+            // Q4_K's): measured on the Q4_K_M 7B layer, profiles/r03/tails/grouped_q6k_weight_ab.log
+            // (re-swept after the Q6_K ring image: 0.9-1.75 at one and two tokens, none better,
+            // profiles/r03/s3/grouped_q6w_sweep.log)
+            // The fp8 form (v_dot2 on fp16 pairs, a different VALU mix): 1.30 / 1.00 at one / two
+            // tokens (fp8 layer x1 38.4 -> 37.2 us, x2 53.9 -> 51.2; profiles/r05/decode_q6w_fp8_ab.txt).
+            const double q6w = fp8 ? (nt == 1 ? 1.30 : 1.0) : (nt == 1 ? 1.15 : (nt == 2 ? 1.5 : 1.0));
+            bytes[np] = (double)items[i].M * (double)row_bytes(items[i].fmt, items[i].K) *
+                        (items[i].fmt == Q6_K ? q6w : 1.0);
+            total += bytes[np];
+            lds = solo[i].lds > lds ? solo[i].lds : lds;
+            ++np;
+        }
+    }
+    if (np == 0) return hipSuccess;
+    // The chip's workgroups split by (weighted) weight bytes (all parts finish together), whole
+    // workgroups by largest remainder, at least one each: never more than the chip holds at
+    // once -- rounding every part up had put a few workgroups into a second round (a 7B layer:
+    // 258 of 256), doubling the launch (44.5 -> 30.1 us at one token).  Weighting the bytes by
+    // each format's large-matrix streaming rate measured 1-5% slower (grouped_alloc_ab.log).
+    const int budget = chip_wgs(lds);
+    int wg[kMaxGroup], used = 0;
+    double frac[kMaxGroup];
+    for (int j = 0; j < np; ++j) {
+        const double ideal = budget * bytes[j] / total;
+        wg[j] = (int)ideal > 1 ? (int)ideal : 1;
+        frac[j] = ideal - wg[j];
+        used += wg[j];
+    }
+    while (used < budget) { // the largest remainders get the rest
+        int best = 0;
+        for (int j = 1; j < np; ++j)
+            if (frac[j] > frac[best]) best = j;
+        ++wg[best];
+        frac[best] -= 1.0;
+        ++used;
+    }
+    while (used > budget) { // (more parts than workgroups cannot happen: np <= 16)
+        int best = -1;
+        for (int j = 0; j < np; ++j)
+            if (wg[j] > 1 && (best < 0 || frac[j] < frac[best])) best = j;
+        if (best < 0) break;
+        --wg[best];
+        frac[best] += 1.0;
+        --used;
+    }
+    GroupedArgs &a = gl.a;
+    a.N = N;
+    int blocks = 0;
+    for (int j = 0; j < np; ++j) {
+        const int i = pi[j];
+        Pick p;
+        p.fp8 = fp8;
+        if (!pick(items[i].fmt, items[i].M, N, items[i].K, p, wg[j]) || p.nt != nt) return hipErrorInvalidValue;
+        GroupedProblem &q = a.p[j];
+        q.A = items[i].A;
+        q.X = items[i].X;
+        q.ldx = items[i].ldx;
+        q.C = items[i].C;
+        q.ldc = items[i].ldc;
+        q.M = (int)items[i].M;
+        q.K = (int)items[i].K;
+        q.geo = p.geo;
+        if (!instantiated<DensePolicy>(items[i].fmt, p)) return hipErrorInvalidValue; // no kernel case
+        q.code = items[i].fmt * 16 + p.itc + (p.img ? 8 : 0);
+        q.block0 = blocks;
+        q.gx = p.grid;
+        q.by = py[j];
+        blocks += p.grid;
+    }
+    a.n = np;
+    int set = 0; // the kernel's case set
+    for (int j = 0; j < np; ++j) set = std::max(set, fmt_info(items[pi[j]].fmt).group_set);
+    if (set > 0 && nt == 1)
+        for (int j = 0; j < np; ++j)
+            if (a.p[j].code % 8 > kGroupItc[set]) return hipErrorInvalidValue; // (decode_grouped_ok)
+    gl.lds = lds;
+    gl.blocks = blocks;
+    gl.set = set;
+    return hipSuccess;
+}
+
+} // namespace
+
 hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipStream_t s, bool fp8)
 {
     if (!decode_grouped_ok(items, n, N, fp8)) return hipErrorInvalidValue;
@@ -1358,98 +1468,15 @@ hipError_t launch_decode_grouped(const DecodeItem *items, int n, int64_t N, hipS
         if (!pick(items[i].fmt, items[i].M, N, items[i].K, solo[i])) return hipErrorInvalidValue;
     }
     for (int nt : {1, 2, 4}) {
-        // the launch's parts: (item, token group); its LDS is the largest part's
-        int pi[kMaxGroup], py[kMaxGroup], np = 0;
-        size_t lds = 0;
-        double bytes[kMaxGroup], total = 0;
-        for (int i = 0; i < n; ++i) {
-            if (solo[i].nt != nt) continue;
-            const int tg = (int)((N + nt - 1) / nt);
-            for (int y = 0; y < tg; ++y) {
-                if (np == kMaxGroup) return hipErrorInvalidValue;
-                pi[np] = i;
-                py[np] = y;
-                // Q6_K bytes weigh more at 1-2 tokens (their unpacking costs more per byte than
-                // Q4_K's): measured on the Q4_K_M 7B layer, profiles/r03/tails/grouped_q6k_weight_ab.log
-                // (re-swept after the Q6_K ring image: 0.9-1.75 at one and two tokens, none better,
-                // profiles/r03/s3/grouped_q6w_sweep.log)
-                // The fp8 form (v_dot2 on fp16 pairs, a different VALU mix): 1.30 / 1.00 at one / two
-                // tokens (fp8 layer x1 38.4 -> 37.2 us, x2 53.9 -> 51.2; profiles/r05/decode_q6w_fp8_ab.txt).
-                const double q6w = fp8 ? (nt == 1 ? 1.30 : 1.0) : (nt == 1 ? 1.15 : (nt == 2 ? 1.5 : 1.0));
-                bytes[np] = (double)items[i].M * (double)row_bytes(items[i].fmt, items[i].K) *
-                            (items[i].fmt == Q6_K ? q6w : 1.0);
-                total += bytes[np];
-                lds = solo[i].lds > lds ? solo[i].lds : lds;
-                ++np;
-            }
-        }
-        if (np == 0) continue;
-        // The chip's workgroups split by (weighted) weight bytes (all parts finish together), whole
-        // workgroups by largest remainder, at least one each: never more than the chip holds at
-        // once -- rounding every part up had put a few workgroups into a second round (a 7B layer:
-        // 258 of 256), doubling the launch (44.5 -> 30.1 us at one token).  Weighting the bytes by
-        // each format's large-matrix streaming rate measured 1-5% slower (grouped_alloc_ab.log).
-        const int budget = chip_wgs(lds);
-        int wg[kMaxGroup], used = 0;
-        double frac[kMaxGroup];
-        for (int j = 0; j < np; ++j) {
-            const double ideal = budget * bytes[j] / total;
-            wg[j] = (int)ideal > 1 ? (int)ideal : 1;
-            frac[j] = ideal - wg[j];
-            used += wg[j];
-        }
-        while (used < budget) { // the largest remainders get the rest
-            int best = 0;
-            for (int j = 1; j < np; ++j)
-                if (frac[j] > frac[best]) best = j;
-            ++wg[best];
-            frac[best] -= 1.0;
-            ++used;
-        }
-        while (used > budget) { // (more parts than workgroups cannot happen: np <= 16)
-            int best = -1;
-            for (int j = 0; j < np; ++j)
-                if (wg[j] > 1 && (best < 0 || frac[j] < frac[best])) best = j;
-            if (best < 0) break;
-            --wg[best];
-            frac[best] += 1.0;
-            --used;
-        }
-        GroupedArgs a{};
-        a.N = N;
-        int blocks = 0;
-        for (int j = 0; j < np; ++j) {
-            const int i = pi[j];
-            Pick p;
-            p.fp8 = fp8;
-            if (!pick(items[i].fmt, items[i].M, N, items[i].K, p, wg[j]) || p.nt != nt) return hipErrorInvalidValue;
-            GroupedProblem &q = a.p[j];
-            q.A = items[i].A;
-            q.X = items[i].X;
-            q.ldx = items[i].ldx;
-            q.C = items[i].C;
-            q.ldc = items[i].ldc;
-            q.M = (int)items[i].M;
-            q.K = (int)items[i].K;
-            q.geo = p.geo;
-            if (!instantiated<DensePolicy>(items[i].fmt, p)) return hipErrorInvalidValue; // no kernel case
-            q.code = items[i].fmt * 16 + p.itc + (p.img ? 8 : 0);
-            q.block0 = blocks;
-            q.gx = p.grid;
-            q.by = py[j];
-            blocks += p.grid;
-        }
-        a.n = np;
-        int set = 0; // the kernel's case set
-        for (int j = 0; j < np; ++j) set = std::max(set, fmt_info(items[pi[j]].fmt).group_set);
-        if (set > 0 && nt == 1)
-            for (int j = 0; j < np; ++j)
-                if (a.p[j].code % 8 > kGroupItc[set]) return hipErrorInvalidValue; // (decode_grouped_ok)
+        GroupedLaunch gl;
+        hipError_t e = plan_grouped(items, n, N, fp8, solo, nt, gl);
+        if (e != hipSuccess) return e;
+        if (gl.a.n == 0) continue;
+        const int set = gl.set;
         auto go = [&](auto tile, auto f8, auto st) {
             return launch_kernel<stream_decode_grouped_kernel<decltype(tile)::value, decltype(f8)::value, decltype(st)::value>>(
-                dim3((unsigned)blocks), lds, s, a);
+                dim3((unsigned)gl.blocks), gl.lds, s, gl.a);
         };
-        hipError_t e;
         if (fp8) // (sets 1..: no fp8 form; decode_grouped_ok: at most two tokens)
             e = set > 0 ? hipErrorInvalidValue : (nt == 1 ? go(ic<1>{}, ic<1>{}, ic<0>{}) : go(ic<2>{}, ic<1>{}, ic<0>{}));
         else
@@ -1571,6 +1598,130 @@ hipError_t launch_decode_glu(int fmt, const uint8_t *A_gate, const uint8_t *A_up
                 dim3((unsigned)p.grid, (unsigned)((N + NT - 1) / NT)), st.lds, s, a);
         });
     });
+}
+
+// ---- the plans above as data (gq_debug_decode_plan, gq_debug_decode_cap): host only, no device ----
+// Every answer comes from the planning function the family's launcher calls -- pick(), plan_id(),
+// plan_id_glu(), plan_glu(), decode_grouped_ok() + plan_grouped() -- never from a copy of it.
+namespace {
+
+DecodePlanInfo plan_info(const Pick &p, int tokens, int item)
+{
+    DecodePlanInfo d{};
+    d.nt = p.nt;
+    d.itc = p.itc;
+    d.img = p.img;
+    d.fp8 = p.fp8;
+    d.lds_split = p.lds_split;
+    d.nseg = p.geo.nseg;
+    d.G = p.geo.G;
+    d.lp2 = p.geo.lp2;
+    d.grid = p.grid;
+    d.ngroups = p.geo.ngroups;
+    d.tokens = tokens;
+    d.item = item;
+    d.lds = (int)p.lds;
+    return d;
+}
+
+// one entry per token group of the launch (the grid's y)
+int token_groups(const Pick &p, int64_t N, int stash_rows, size_t lds, DecodePlanInfo *out, int max_out)
+{
+    const int tg = (int)((N + p.nt - 1) / p.nt);
+    for (int y = 0; y < tg && y < max_out; ++y) {
+        out[y] = plan_info(p, (int)std::min<int64_t>(p.nt, N - (int64_t)y * p.nt), 0);
+        out[y].stash_rows = stash_rows;
+        out[y].lds = (int)lds;
+    }
+    return tg;
+}
+
+} // namespace
+
+int decode_plan_info(int family, const DecodeItem *items, int n, int64_t N, bool fp8, DecodePlanInfo *out, int max_out)
+{
+    if (n < 1 || !items || N < 1 || (max_out > 0 && !out)) return 0;
+    const DecodeItem &it = items[0];
+    if (family != DF_GROUPED && (n != 1 || !known_fmt(it.fmt) || it.M < 1)) return 0;
+    Pick p;
+    Stash st;
+    switch (family) {
+    case DF_DENSE: { // launch_decode_fused (a matrix of 2 GiB or more: its first launch's rows)
+        if (!decode_fused_ok(it.fmt, N, it.K, fp8)) return 0;
+        const int64_t max_rows = ((int64_t)1 << 31) / row_bytes(it.fmt, it.K) - 1;
+        p.fp8 = fp8;
+        if (!pick(it.fmt, std::min(it.M, max_rows), N, it.K, p)) return 0;
+        return token_groups(p, N, 0, p.lds, out, max_out);
+    }
+    case DF_ID: // N: the pairs
+        if (fp8 || !plan_id(it.fmt, it.M, N, it.K, p)) return 0;
+        if (max_out > 0) out[0] = plan_info(p, 1, 0);
+        return 1;
+    case DF_ID_GLU:
+        if (fp8 || !plan_id_glu(it.fmt, it.M, N, it.K, p, st)) return 0;
+        if (max_out > 0) {
+            out[0] = plan_info(p, 1, 0);
+            out[0].stash_rows = st.rows;
+            out[0].lds = (int)st.lds;
+        }
+        return 1;
+    case DF_GLU:
+        if (fp8 || !plan_glu(it.fmt, it.M, N, it.K, p, st)) return 0;
+        return token_groups(p, N, st.rows, st.lds, out, max_out);
+    case DF_GROUPED: { // launch_decode_grouped: the parts of every token tile's launch
+        if (!decode_grouped_ok(items, n, N, fp8)) return 0;
+        Pick solo[kMaxGroup];
+        for (int i = 0; i < n; ++i) {
+            solo[i].fp8 = fp8;
+            if (!pick(items[i].fmt, items[i].M, N, items[i].K, solo[i])) return 0;
+        }
+        int m = 0;
+        for (int nt : {1, 2, 4}) {
+            GroupedLaunch gl;
+            if (plan_grouped(items, n, N, fp8, solo, nt, gl) != hipSuccess) return 0;
+            for (int j = 0; j < gl.a.n; ++j, ++m) {
+                if (m >= max_out) continue;
+                const GroupedProblem &q = gl.a.p[j];
+                Pick part = solo[gl.item[j]]; // nt, fp8; then what the kernel is handed
+                part.itc = q.code % 8;
+                part.img = (q.code & 8) != 0;
+                part.geo = q.geo;
+                part.grid = q.gx;
+                part.lds = gl.lds;
+                out[m] = plan_info(part, (int)std::min<int64_t>(nt, N - (int64_t)q.by * nt), gl.item[j]);
+                out[m].set = gl.set;
+            }
+        }
+        return m;
+    }
+    default: return 0;
+    }
+}
+
+int decode_itc_cap(int family, int set, int fmt, int nt, bool fp8)
+{
+    if (!known_fmt(fmt) || (nt != 1 && nt != 2 && nt != 4)) return -1;
+    Pick p{};
+    p.nt = nt;
+    p.itc = 0;
+    p.fp8 = fp8;
+    switch (family) {
+    case DF_DENSE: return instantiated<DensePolicy>(fmt, p) ? DensePolicy::itc_cap(fmt, nt, fp8) : -1;
+    case DF_ID:
+    case DF_ID_GLU: return instantiated<IdPolicy>(fmt, p) ? IdPolicy::itc_cap(fmt, nt, fp8) : -1;
+    case DF_GLU: return instantiated<GluPolicy>(fmt, p) ? GluPolicy::itc_cap(fmt, nt, fp8) : -1;
+    case DF_GROUPED: {
+        // stream_decode_grouped_kernel<NT, FP8, SET>'s hand lists: the set's types (kGroupHas) at the dense
+        // caps, at one token in sets 1.. no further than kGroupItc[set]; the fp8 form in set 0 at one
+        // and two tokens
+        if (set < 0 || set >= kGroupSets || !(kGroupHas[set] >> fmt_info(fmt).group_set & 1u)) return -1;
+        if (fp8 && (set != 0 || nt == 4)) return -1;
+        if (!instantiated<DensePolicy>(fmt, p)) return -1;
+        const int cap = DensePolicy::itc_cap(fmt, nt, fp8);
+        return nt == 1 && set > 0 ? std::min(cap, kGroupItc[set]) : cap;
+    }
+    default: return -1;
+    }
 }
 
 } // namespace gq

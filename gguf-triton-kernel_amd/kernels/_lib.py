@@ -46,6 +46,14 @@ class GemmItem(ctypes.Structure):
     _fields_ = [("type", ctypes.c_int), ("A", _P), ("ws", _P), ("C", _P), ("ldc", _I64), ("M", _I64), ("K", _I64)]
 
 
+class DecodePlan(ctypes.Structure):
+    """gq_decode_plan (include/gguf_mmq.h)."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("nt", "itc", "img", "fp8", "lds_split", "nseg", "G", "lp2", "grid",
+                                              "ngroups", "stash_rows", "tokens", "set", "item", "lds")]
+
+
+DECODE_FAMILIES = {"dense": 0, "id": 1, "id_glu": 2, "glu": 3, "grouped": 4}
+
 SIGNATURES = {
     "gq_block_elems": ([_I], _I),
     "gq_block_bytes": ([_I], _I),
@@ -80,6 +88,8 @@ SIGNATURES = {
     "gq_moe_route": ([_P, _I, _P, _I64, _P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
+    "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
+    "gq_debug_decode_cap": ([_I, _I, _I, _I, _I], _I),
     "gq_mmq_grouped_prepared_workspace_size": ([_I, ctypes.POINTER(GemmItem), _I, _I64], _SZ),
     "gq_mmq_grouped_prepared": ([_I, ctypes.POINTER(GemmItem), _I, _I64, _P, _SZ, _P], _I),
     "gq_last_error": ([], ctypes.c_char_p),
@@ -144,6 +154,22 @@ def set_tuning(key: str, value: int):
 def route_name(gtype: int, M: int, N: int, K: int, act: str = "q8_1", prepared: bool = False) -> str:
     """The kernel(s) the library would launch for this call (gq_debug_route)."""
     return lib().gq_debug_route(gtype, ACTS[act], M, N, K, int(prepared)).decode()
+
+
+def decode_plan(family: str, items, N: int, act: str = "q8_1") -> list:
+    """The one-launch decode's plan for a call (gq_debug_decode_plan; host only once GQ_CUS is set):
+    a list of DecodePlan, one per (item, token group), empty when the family's entry point would not
+    take its one-launch decode.  items: (gtype, M, K) -- one for "dense", "id", "id_glu" (N: the
+    pairs) and "glu", the launch's list for "grouped"."""
+    arr = (GroupItem * len(items))(*[GroupItem(t, None, None, K, None, M, M, K) for t, M, K in items])
+    out = (DecodePlan * 32)()
+    n = lib().gq_debug_decode_plan(DECODE_FAMILIES[family], ACTS[act], arr, len(items), N, out, 32)
+    return [out[i] for i in range(n)]
+
+
+def decode_cap(family: str, gtype: int, nt: int, fp8: bool = False, group_set: int = 0) -> int:
+    """The most cached chunks a decode kernel of the family exists for (gq_debug_decode_cap), -1: none."""
+    return int(lib().gq_debug_decode_cap(DECODE_FAMILIES[family], group_set, gtype, nt, int(fp8)))
 
 
 def reset_tuning():

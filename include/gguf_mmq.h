@@ -547,6 +547,31 @@ void gq_debug_reset_tuning(void);
  * names as its roofline kernel.  Split-K reduce kernels are listed whether or not the plan
  * splits. */
 const char *gq_debug_route(gq_type t, gq_act act, int64_t M, int64_t N, int64_t K, int prepared);
+/* The one-launch decode's plan for a call, host only (no device is touched once GQ_CUS is set): what
+ * tests/decode_cases.py builds its case table from.  family: 0 gq_mmq_ex's decode, 1 gq_mmq_id,
+ * 2 gq_mmq_id_glu, 3 gq_mmq_glu -- items[0]'s type, M and K with n = 1, N the tokens (families 1, 2:
+ * the N*S pairs) -- or 4 gq_mmq_grouped_ex on the n items.  Pointers and strides in the items are not
+ * read.  Returns how many entries the call's launches have -- one per (item, token group), at most
+ * max_out of them written to out -- or 0 when that entry point would not take its one-launch decode
+ * for the call under the current tuning.
+ *   nt, itc, img, fp8 : the kernel: token tile, cached activation chunks, Q6_K's aligned ring, fp8 form
+ *   lds_split         : the tile was cut to fit LDS (never set in an accepted plan)
+ *   nseg, G, lp2      : segments per row, rows per task, log2 of the lanes per row
+ *   grid, ngroups     : workgroups (families 1, 2: per pair; 4: the item's share) and the row groups
+ *                       (rows when nseg > 1) they share, 8 waves each
+ *   stash_rows        : families 2, 3: uint16 entries of a wave's g stash per token
+ *   tokens            : tokens in this entry's token group
+ *   set, item         : family 4: the launch's case set and the entry's item
+ *   lds               : the launch's dynamic LDS bytes
+ * Debug entry points: they do not move gq_version. */
+typedef struct gq_decode_plan {
+    int32_t nt, itc, img, fp8, lds_split, nseg, G, lp2, grid, ngroups, stash_rows, tokens, set, item, lds;
+} gq_decode_plan;
+int gq_debug_decode_plan(int family, gq_act act, const gq_group_item *items, int n, int64_t N, gq_decode_plan *out,
+                         int max_out);
+/* The most cached chunks (itc) a decode kernel of the family exists for at (type, token tile nt in
+ * 1, 2, 4, fp8 form), or -1 when it has none; family as above, set: family 4's case set (0..4). */
+int gq_debug_decode_cap(int family, int set, gq_type t, int nt, int fp8);
 /* How many synchronisation waits inside a kernel gave up since the library was loaded: the
  * resident GEMM's in-launch split-K combine (only possible when another kernel holds CUs its grid
  * needed) and the K-chunked stream's cross-wave hand-off.  A wait gives up after a bounded spin
