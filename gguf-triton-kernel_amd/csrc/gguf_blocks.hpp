@@ -125,10 +125,23 @@ template <int MAX, int I = 0, class Fn> hipError_t dispatch_upto(int i, Fn &&fn)
 }
 // fn(ic<F>{}) for the table's type fmt; hipErrorInvalidValue for an unknown one
 template <class Fn> hipError_t dispatch_fmt(int fmt, Fn &&fn) { return dispatch_upto<kNumFmts - 1>(fmt, fn); }
+// fn(ic<NB>{}) for a token-tile count nb in {1, 2, 4, 8} (pick_nb's values: tiles of 16*nb tokens);
+// hipErrorInvalidValue for any other
+template <class Fn> hipError_t dispatch_nb(int nb, Fn &&fn)
+{
+    switch (nb) {
+    case 1: return fn(ic<1>{});
+    case 2: return fn(ic<2>{});
+    case 4: return fn(ic<4>{});
+    case 8: return fn(ic<8>{});
+    default: return hipErrorInvalidValue;
+    }
+}
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ u32x4 ld16(const void *p)
 {
@@ -172,6 +185,21 @@ __device__ __forceinline__ float h2f(uint32_t bits16)
 __device__ __forceinline__ uint16_t f2h_bits(float f)
 {
     return __builtin_bit_cast(uint16_t, (_Float16)f);
+}
+
+// v = four consecutive output rows (row..row + 3 of M) of one token, dst = the first one's fp16:
+// one packed 8-byte store (2-byte aligned when ldc or M is odd: an unaligned store), or the rows
+// below M one by one in the last, partial group.  Four epilogues keep this text in place (gemm_kernel,
+// store_c_tiles, ilc_sum, reduce_grouped_kernel): called through the function they compile to other
+// machine code -- the tail's compares hoisted or rescheduled ("The 256-row tile family")
+template <class R, class L> __device__ __forceinline__ void store_h4(uint16_t *dst, const f32x4 v, R row, L M)
+{
+    if (row + 4 <= M) {
+        *(u32x2 *)dst = (u32x2){(uint32_t)f2h_bits(v[0]) | ((uint32_t)f2h_bits(v[1]) << 16),
+                                (uint32_t)f2h_bits(v[2]) | ((uint32_t)f2h_bits(v[3]) << 16)};
+    } else {
+        for (int i = 0; i < 4 && row + i < M; ++i) dst[i] = f2h_bits(v[i]);
+    }
 }
 
 // v_dot4_i32_i8: c + sum_k a.i8[k] * b.i8[k]

@@ -87,6 +87,10 @@ bool decode_fused_ok(int fmt, int64_t N, int64_t K, bool fp8 = false);
 hipError_t launch_decode_fused(int fmt, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, int64_t M,
                                int64_t N, int64_t K, int64_t ldc, hipStream_t s, bool fp8 = false);
 
+// 16-token groups per workgroup tile for N tokens (a sorted expert GEMM: the mean per expert):
+// every MFMA GEMM plan's nb -- 16-, 32-, 64- or 128-token tiles
+constexpr int pick_nb(int64_t N) { return N > 64 ? 8 : (N > 32 ? 4 : (N > 16 ? 2 : 1)); }
+
 // Batched GEMM on fp16 MFMA (mmq_gemm.hip): C[t][m] from the dequantized activation x~.
 struct GemmPlan {
     int nb = 8;                // 16-token groups per workgroup (tile = 16*nb tokens)
@@ -118,8 +122,9 @@ GemmPlan plan_gemm(int fmt, int64_t M, int64_t N, int64_t K, int act = AF_F16);
 hipError_t launch_gemm(int fmt, const uint8_t *A, const GemmAct &x, uint16_t *C, float *partials,
                        const GemmPlan &plan, int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s);
 
-// The split-K sum of the fp16 partials gemm_kernel (and rgemm_kernel) write: tiles of 16*8*rg
-// rows x 16*nb tokens, S splits (mmq_gemm.hip gemm_reduce_f16_kernel).
+// The split-K sum of the fp16 partials gemm_kernel (and rgemm_kernel, sgemm_kernel) write: tiles of
+// 16*8*rg rows x 16*nb tokens, S splits (mmq_gemm.hip gemm_reduce_f16_kernel; the partial's layout:
+// gguf_partial.hpp).
 hipError_t launch_gemm_reduce_f16(int nb, int rg, const uint16_t *P, uint16_t *C, int64_t M, int64_t N, int64_t ldc,
                                   int S, int tiles_x, int tiles_y, hipStream_t s);
 
@@ -142,7 +147,8 @@ bool rgemm_estore(int nb);
 unsigned int ilc_timeouts();
 // the K-chunked stream's cross-wave hand-off waits that gave up (0 unless broken)
 unsigned int kstream_timeouts();
-// resident workgroups one CU holds at once (LDS-bound: Q4_K at 16 tokens 3, at 32 two, else one)
+// resident workgroups one CU holds at once (LDS-bound: Q4_K at 16 tokens 3, at 32 two, else one);
+// 0 for a type without a resident form or an nb that is not pick_nb's
 int rgemm_per_cu(int fmt, int nb);
 hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *partials,
                         const RGemmPlan &p, int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s);

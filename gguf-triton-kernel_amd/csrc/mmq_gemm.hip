@@ -51,6 +51,7 @@
 #include "gguf_internal.hpp"
 #include "gguf_q8_1.hpp"
 #include "gguf_mfma.hpp"
+#include "gguf_partial.hpp"
 
 namespace gq {
 
@@ -569,8 +570,9 @@ __global__ __launch_bounds__(64 * (NWAVE + NL)) void gemm_kernel(const uint8_t *
         // wave and block, read by the reduce as a scalar) follow the blocks.
         const int64_t tile = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
         if (pf16) {
+            constexpr PartLayout L = {G::BM, NWAVE, G::BN}; // gguf_partial.hpp
             const int64_t bidx = tile * gridDim.z + blockIdx.z;
-            uint16_t *hb = (uint16_t *)P + bidx * (int64_t)(G::BM * G::BN);
+            uint16_t *hb = (uint16_t *)P + bidx * (int64_t)L.halves();
             float mx = 0.f;
 #pragma unroll
             for (int rg = 0; rg < RG; ++rg)
@@ -592,7 +594,7 @@ __global__ __launch_bounds__(64 * (NWAVE + NL)) void gemm_kernel(const uint8_t *
             const int e = E - 14 > 0 ? (E - 14 < 127 ? E - 14 : 126) : 0;
             const float down = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);
             const int64_t nblk = (int64_t)gridDim.x * gridDim.y * gridDim.z;
-            int *es = (int *)((uint16_t *)P + nblk * (G::BM * G::BN));
+            int *es = (int *)((uint16_t *)P + nblk * L.halves());
             auto pk = [down](const f32x4 &v) {
                 return (u32x2){(uint32_t)f2h_bits(v[0] * down) | ((uint32_t)f2h_bits(v[1] * down) << 16),
                                (uint32_t)f2h_bits(v[2] * down) | ((uint32_t)f2h_bits(v[3] * down) << 16)};
@@ -634,7 +636,7 @@ __global__ __launch_bounds__(64 * (NWAVE + NL)) void gemm_kernel(const uint8_t *
             const int64_t tok = n0 + 16 * t + l16;
             if (tok >= N) continue;
             const f32x4 v = acc[rg][t];
-            uint16_t *dst = C + tok * ldc + row;
+            uint16_t *dst = C + tok * ldc + row; // (store_h4's text in place: see gguf_blocks.hpp)
             if (row + 4 <= M) {
                 const u32x2 o = {(uint32_t)f2h_bits(v[0]) | ((uint32_t)f2h_bits(v[1]) << 16),
                                  (uint32_t)f2h_bits(v[2]) | ((uint32_t)f2h_bits(v[3]) << 16)};
@@ -682,8 +684,9 @@ __global__ __launch_bounds__(256) void gemm_reduce_f16_kernel(const uint16_t *__
     const int q = TPU == 2 ? it >> 1 : it, j = TPU == 2 ? it & 1 : 0; // unit, tile within the unit
     const int lane = q & 63, u = (q >> 6) % (NB / TPU), wr = (q >> 6) / (NB / TPU);
     const int64_t m0 = (tile % tiles_x) * (16 * NWAVE * RG), n0 = (tile / tiles_x) * (16 * NB);
-    const int64_t blk = (int64_t)QPT * 4; // halves per (tile, split) block
-    const int *es = (const int *)(P + ntiles * S * blk);
+    constexpr PartLayout L = {16 * NWAVE * RG, NWAVE, 16 * NB};
+    const int64_t blk = L.halves(); // per (tile, split) block
+    const int *es = (const int *)((const uint8_t *)P + L.exp_off(ntiles * S));
     const int wv = __builtin_amdgcn_readfirstlane(wr / RG); // uniform: a reduce wave is one GEMM wave's rows
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     for (int s0 = 0; s0 < S; s0 += 8) {
@@ -715,14 +718,7 @@ __global__ __launch_bounds__(256) void gemm_reduce_f16_kernel(const uint16_t *__
     const int64_t row = m0 + 16 * wr + 4 * (lane >> 4);
     const int64_t tok = n0 + 16 * (TPU * u + j) + (lane & 15);
     if (row >= M || tok >= N) return;
-    uint16_t *dst = C + tok * ldc + row;
-    if (row + 4 <= M) {
-        const u32x2 o = {(uint32_t)f2h_bits(acc[0]) | ((uint32_t)f2h_bits(acc[1]) << 16),
-                         (uint32_t)f2h_bits(acc[2]) | ((uint32_t)f2h_bits(acc[3]) << 16)};
-        *(u32x2 *)dst = o;
-    } else {
-        for (int i = 0; i < 4 && row + i < M; ++i) dst[i] = f2h_bits(acc[i]);
-    }
+    store_h4(C + tok * ldc + row, acc, row, M);
 }
 
 template <int NB, int RG>
@@ -766,14 +762,7 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(const float *__restric
     }
     const int64_t row = m0 + 16 * wave + 4 * (lane >> 4), tok = n0 + 16 * t + (lane & 15);
     if (tok >= N || row >= M) return;
-    uint16_t *dst = C + tok * ldc + row;
-    if (row + 4 <= M) {
-        const u32x2 o = {(uint32_t)f2h_bits(acc[0]) | ((uint32_t)f2h_bits(acc[1]) << 16),
-                         (uint32_t)f2h_bits(acc[2]) | ((uint32_t)f2h_bits(acc[3]) << 16)};
-        *(u32x2 *)dst = o;
-    } else {
-        for (int i = 0; i < 4 && row + i < M; ++i) dst[i] = f2h_bits(acc[i]);
-    }
+    store_h4(C + tok * ldc + row, acc, row, M);
 }
 
 template <int F, int NB, int RG, int AM = AF_F16, int NL = 0, int AQ = 0>
@@ -848,8 +837,6 @@ hipError_t launch_fmt(const uint8_t *A, const GemmAct &x, uint16_t *C, float *P,
     }
 }
 
-int pick_nb(int64_t N) { return N > 64 ? 8 : (N > 32 ? 4 : (N > 16 ? 2 : 1)); }
-
 } // namespace
 
 hipError_t launch_gemm_reduce_f16(int nb, int rg, const uint16_t *P, uint16_t *C, int64_t M, int64_t N, int64_t ldc,
@@ -919,8 +906,8 @@ GemmPlan plan_gemm(int fmt, int64_t M, int64_t N, int64_t K, int act)
     p.pf16 = 1;
     if (tuning().gemm_partial_f32) p.pf16 = 0;
     // blocked partials: S x (tiles) x 128 rows x 16*nb tokens (padded tiles)
-    p.partial_bytes = S > 1 ? (size_t)S * tiles * bm * 16 * p.nb * (p.pf16 ? 2 : sizeof(float)) : 0;
-    if (S > 1 && p.pf16) p.partial_bytes += (size_t)S * tiles * NWAVE * sizeof(int); // the per-wave e's
+    p.partial_bytes = S <= 1 ? 0 : (p.pf16 ? PartLayout{(int)bm, NWAVE, 16 * p.nb}.bytes(S * tiles)
+                                           : (size_t)S * tiles * bm * 16 * p.nb * sizeof(float));
     return p;
 }
 

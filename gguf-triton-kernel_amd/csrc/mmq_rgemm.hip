@@ -28,6 +28,7 @@
 #include "gguf_blocks.hpp"
 #include "gguf_internal.hpp"
 #include "gguf_mfma.hpp"
+#include "gguf_partial.hpp"
 #include "gguf_q8_1.hpp"
 
 namespace gq {
@@ -281,7 +282,8 @@ struct IlcSync {
     uint32_t *nonce;  // [tiles]
 };
 // the sync words after the partial blocks and their exponents
-__host__ __device__ inline size_t ilc_flags_off(int64_t nblk, int BN) { return ((size_t)nblk * (RBM * BN * 2 + RW * 4) + 7) & ~(size_t)7; }
+constexpr PartLayout part_layout(int BN) { return PartLayout{RBM, RW, BN}; } // gguf_partial.hpp
+__host__ __device__ inline size_t ilc_flags_off(int64_t nblk, int BN) { return part_layout(BN).bytes(nblk, 8); }
 __host__ __device__ inline size_t ilc_sync_bytes(int64_t nblk, int64_t ntiles) { return (size_t)nblk * 8 + (size_t)ntiles * 4; }
 __device__ __forceinline__ IlcSync ilc_sync(uint16_t *P, const TileId &id, int BN)
 {
@@ -331,11 +333,10 @@ __device__ __forceinline__ void ilc_sum(uint16_t *__restrict__ C, const uint16_t
                                         int64_t ldc, int64_t m0, int64_t n0, int64_t tile, int slots, int64_t nblk, int S,
                                         int k, int nsh)
 {
-    constexpr int BN = 16 * NB;
+    constexpr PartLayout L = part_layout(16 * NB);
     constexpr int TPU = NB == 1 ? 1 : 2, UB = 8 * TPU, UPT = RW * RRG * (NB / TPU) * 64;
     const int tid = threadIdx.x;
-    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)P, 0, (int)(uint32_t)(nblk * (RBM * BN * 2 + RW * 4)), 0x00020000);
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void *)P, 0, (int)(uint32_t)L.bytes(nblk), 0x00020000);
     const int u0 = (int)((int64_t)k * UPT / nsh), u1 = (int)((int64_t)(k + 1) * UPT / nsh);
     for (int it = u0 + tid; it < u1; it += (int)blockDim.x) {
         const int q = it >> 6, ln = it & 63, u = q % (NB / TPU), wr = q / (NB / TPU), wv = wr / RRG;
@@ -349,9 +350,11 @@ __device__ __forceinline__ void ilc_sum(uint16_t *__restrict__ C, const uint16_t
 #pragma unroll
             for (int g = 0; g < G; ++g) { // unconditional (clamped) loads, the surplus zeroed after
                 const uint32_t b = (uint32_t)(tile * slots + (s0 + g < S ? s0 + g : S - 1));
-                const uint32_t eo = (uint32_t)(nblk * (RBM * BN * 2)) + (b * RW + (uint32_t)wv) * 4u;
+                // (32-bit on purpose: PartLayout's exponent base and block size, this kernel's own integer
+                // widths -- the int64 exp_off(nblk, blk, wave) compiles to other code here)
+                const uint32_t eo = (uint32_t)L.exp_off(nblk) + (b * RW + (uint32_t)wv) * 4u;
                 up[g] = __builtin_bit_cast(float, (127u + __builtin_amdgcn_raw_buffer_load_b32(prs, eo, 0, 16)) << 23);
-                const uint32_t vo = b * (uint32_t)(RBM * BN * 2) + (uint32_t)it * UB;
+                const uint32_t vo = b * (uint32_t)L.block_bytes() + (uint32_t)it * UB;
                 if constexpr (TPU == 2) {
                     v[g] = __builtin_amdgcn_raw_buffer_load_b128(prs, vo, 0, 16);
                 } else {
@@ -441,9 +444,7 @@ template <int NB> __device__ __forceinline__ float tile_absmax(const f32x4 (&acc
             for (int i = 0; i < 4; ++i) mx = fmaxf(mx, fabsf(acc[rg][t][i]));
     return mx;
 }
-// A workgroup's block of the split-K partial (gemm_kernel's fp16 form, summed by its reduce
-// kernel): per (tile, split) 256 x BN halves in accumulator order -- a 16-byte unit holds one
-// lane's values of two token tiles -- each wave's values scaled by 2^-e, the e's after all blocks.
+// A workgroup's block of the split-K partial (gguf_partial.hpp), block (tile, split id.z).
 // SP: the store cache policy where the caller knows it at compile time (then no branch between the
 // stores), or -1: the constructor's.
 template <int NB, int SP = -1> struct PartBlock {
@@ -452,13 +453,13 @@ template <int NB, int SP = -1> struct PartBlock {
     int spol;
     __device__ __forceinline__ PartBlock(uint16_t *P, const TileId &id, int spol_) : spol(SP < 0 ? spol_ : SP)
     {
-        constexpr int BN = 16 * NB;
+        constexpr PartLayout L = part_layout(16 * NB);
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         const int64_t bidx = ((int64_t)id.y * id.gx + id.x) * id.gz + id.z;
         const int64_t nblk = (int64_t)id.gx * id.gy * id.gz;
-        prs = __builtin_amdgcn_make_buffer_rsrc((void *)P, 0, (int)(uint32_t)(nblk * (RBM * BN * 2 + RW * 4)), 0x00020000);
-        bo = (uint32_t)(bidx * (RBM * BN * 2));
-        eo = (uint32_t)(nblk * (RBM * BN * 2) + (bidx * RW + wave) * 4);
+        prs = __builtin_amdgcn_make_buffer_rsrc((void *)P, 0, (int)(uint32_t)L.bytes(nblk), 0x00020000);
+        bo = (uint32_t)L.block_off(bidx);
+        eo = (uint32_t)L.exp_off(nblk, bidx, wave);
     }
     __device__ __forceinline__ void exponent(int e) const
     {
@@ -513,7 +514,7 @@ __device__ __forceinline__ void store_c_tiles(const f32x4 (&acc)[RRG][NB], int t
             const int64_t tok = n0 + 16 * t + l16;
             if (tok >= N) continue;
             const f32x4 v = acc[rg][t];
-            uint16_t *dst = C + tok * ldc + row;
+            uint16_t *dst = C + tok * ldc + row; // (store_h4's text in place: see gguf_blocks.hpp)
             if (row + 4 <= M) {
                 *(u32x2 *)dst = (u32x2){(uint32_t)f2h_bits(v[0]) | ((uint32_t)f2h_bits(v[1]) << 16),
                                         (uint32_t)f2h_bits(v[2]) | ((uint32_t)f2h_bits(v[3]) << 16)};
@@ -643,14 +644,7 @@ __device__ __forceinline__ void store_tile_rows(const f32x4 (&acc)[RRG][NB], uin
         for (int rg = 0; rg < RRG; ++rg) {
             const int64_t row = m0 + 16 * (RRG * wave + rg) + 4 * g;
             if (row >= M) continue;
-            const f32x4 v = acc[rg][t];
-            uint16_t *dst = out + row;
-            if (row + 4 <= M) {
-                *(u32x2 *)dst = (u32x2){(uint32_t)f2h_bits(v[0]) | ((uint32_t)f2h_bits(v[1]) << 16),
-                                        (uint32_t)f2h_bits(v[2]) | ((uint32_t)f2h_bits(v[3]) << 16)};
-            } else {
-                for (int i = 0; i < 4 && row + i < M; ++i) dst[i] = f2h_bits(v[i]);
-            }
+            store_h4(out + row, acc[rg][t], row, M);
         }
     }
 }
@@ -1198,13 +1192,6 @@ template <int NB> constexpr int max_slds()
 // Q3_K's nor Q2_K's (plan_sgemm_grouped refuses such a mix: the caller runs the items alone).
 constexpr int kSgemmSets = 4;
 template <int NB, int SET = 0>
-__global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a);
-template <int NB, int SET = 0> int grouped_occ()
-{
-    int n = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sgemm_grouped_kernel<NB, SET>, 64 * RW, 0) == hipSuccess ? n : 0;
-}
-template <int NB, int SET>
 __global__ __launch_bounds__(64 * RW) void sgemm_grouped_kernel(const SParts a)
 {
     __shared__ __attribute__((aligned(1024))) uint8_t lds[max_slds<NB>()];
@@ -1351,8 +1338,9 @@ __global__ __launch_bounds__(256) void reduce_grouped_kernel(const RParts a)
     const int lane = it & 63, u = (it >> 6) % (NB / TPU), wr = (it >> 6) / (NB / TPU);
     const int wv = __builtin_amdgcn_readfirstlane(wr / RRG);
     const int64_t m0 = (int64_t)(tile % q.tiles_m) * RBM, n0 = (int64_t)(tile / q.tiles_m) * (16 * NB);
-    const int64_t blk = (int64_t)RBM * 16 * NB; // halves per (tile, split) block
-    const int *es = (const int *)(q.P + (int64_t)ntiles * ss * blk);
+    constexpr PartLayout L = part_layout(16 * NB);
+    const int64_t blk = L.halves(); // per (tile, split) block
+    const int *es = (const int *)((const uint8_t *)q.P + L.exp_off((int64_t)ntiles * ss));
     f32x4 acc[TPU];
 #pragma unroll
     for (int j = 0; j < TPU; ++j) acc[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -1399,16 +1387,23 @@ __global__ __launch_bounds__(256) void reduce_grouped_kernel(const RParts a)
     }
 }
 
+// workgroups of a GEMM kernel of this file (64 * RW threads, static LDS only) a CU admits at once:
+// the runtime's answer -- registers as well as LDS --, asked once per kernel; 0 when it fails
+template <auto Kernel> int occupancy()
+{
+    static const int occ = [] {
+        int n = 0;
+        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, Kernel, 64 * RW, 0) == hipSuccess ? n : 0;
+    }();
+    return occ;
+}
+
 template <int F, int NB>
 hipError_t launch_snb(const uint8_t *A, const uint16_t *X, uint16_t *C, void *P, const RGemmPlan &p, int64_t M,
                       int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    static const int occ = [] {
-        int n = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sgemm_kernel<F, NB>, 64 * RW, 0) == hipSuccess ? n : 0;
-    }();
     const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n * p.splits;
-    if (sgemm_ilc(p) && blocks <= (int64_t)num_cus() * occ) { // one kernel
+    if (sgemm_ilc(p) && blocks <= (int64_t)num_cus() * occupancy<sgemm_kernel<F, NB>>()) { // one kernel
         sgemm_kernel<F, NB><<<dim3((unsigned)blocks), dim3(64 * RW), 0, s>>>(A, X, C, (uint16_t *)P, M, N, K, ldc, 16,
                                                                              tuning().sgemm_full != 0, p.tiles_m, p.tiles_n, 1);
         return hipGetLastError();
@@ -1438,13 +1433,9 @@ template <int F, int NB, int AQ, int ES>
 hipError_t launch_es(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *P, const RGemmPlan &p,
                      int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    // workgroups a CU admits at once (the runtime's answer: registers as well as LDS)
-    static const int occ = [] {
-        int n = 0;
-        return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, rgemm_kernel<F, NB, AQ, ES>, 64 * RW, 0) == hipSuccess ? n : 0;
-    }();
     const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n * p.splits;
-    if (rgemm_ilc(F, p) && blocks <= (int64_t)num_cus() * occ) { // the split-K sum inside the launch: one kernel
+    // the split-K sum inside the launch: one kernel
+    if (rgemm_ilc(F, p) && blocks <= (int64_t)num_cus() * occupancy<rgemm_kernel<F, NB, AQ, ES>>()) {
         rgemm_kernel<F, NB, AQ, ES><<<dim3((unsigned)blocks), dim3(64 * RW), 0, s>>>(A, X, ldx, C, (uint16_t *)P, M, N, K,
                                                                                      ldc, 16, p.tiles_m, p.tiles_n);
         return hipGetLastError();
@@ -1466,52 +1457,54 @@ hipError_t launch_nb(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t 
     return launch_es<F, NB, AQ, 0>(A, X, ldx, C, P, p, M, N, K, ldc, s);
 }
 
-template <int F, int AQ>
-hipError_t launch_f(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *P, const RGemmPlan &p,
-                    int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
+// fn(ic<F>{}) for a type that has a resident form (not Q5_K, Q3_K, Q2_K, Q4_0), as dispatch_fmt:
+// hipErrorInvalidValue for any other
+template <class Fn> hipError_t dispatch_resident(int fmt, Fn &&fn)
 {
-    switch (p.nb) {
-    case 1: return launch_nb<F, 1, AQ>(A, X, ldx, C, P, p, M, N, K, ldc, s);
-    case 2: return launch_nb<F, 2, AQ>(A, X, ldx, C, P, p, M, N, K, ldc, s);
-    case 4: return launch_nb<F, 4, AQ>(A, X, ldx, C, P, p, M, N, K, ldc, s);
-    case 8: return launch_nb<F, 8, AQ>(A, X, ldx, C, P, p, M, N, K, ldc, s);
+    switch (fmt) {
+    case Q8_0: return fn(ic<Q8_0>{});
+    case Q4_K: return fn(ic<Q4_K>{});
+    case Q6_K: return fn(ic<Q6_K>{});
     default: return hipErrorInvalidValue;
     }
+}
+
+// A 256-row tile plan of one matrix: nb, the tile grid, the splits as splits(tiles, super-blocks)
+// chooses them, and their workspace -- the partial blocks and their exponents, then the in-launch
+// combine's flags and nonces
+template <class Splits> RGemmPlan plan_tiles(int64_t M, int64_t N, int64_t K, Splits splits)
+{
+    RGemmPlan p;
+    if (M < 1 || N < 1 || K < 256 || K % 256 != 0) return p;
+    p.nb = pick_nb(N);
+    p.tiles_m = (int)((M + RBM - 1) / RBM);
+    p.tiles_n = (int)((N + 16 * p.nb - 1) / (16 * p.nb));
+    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n;
+    p.splits = splits(tiles, K / 256);
+    const int64_t nblk = tiles * p.splits;
+    p.partial_bytes = p.splits > 1 ? ilc_flags_off(nblk, 16 * p.nb) + ilc_sync_bytes(nblk, tiles) : 0;
+    p.ok = true;
+    return p;
 }
 
 } // namespace
 
 int rgemm_per_cu(int fmt, int nb)
 {
-#define GQ_RPC(F)                                                                                                      \
-    switch (nb) {                                                                                                      \
-    case 1: return LDS_CAP / RCfg<F, 1>::LDS;                                                                          \
-    case 2: return LDS_CAP / RCfg<F, 2>::LDS;                                                                          \
-    case 4: return LDS_CAP / RCfg<F, 4>::LDS;                                                                          \
-    default: return LDS_CAP / RCfg<F, 8>::LDS;                                                                         \
-    }
-    switch (fmt) {
-    case Q8_0: GQ_RPC(Q8_0)
-    case Q4_K: GQ_RPC(Q4_K)
-    case Q6_K: GQ_RPC(Q6_K)
-    default: return 0; // (no resident form: Q5_K, Q3_K, Q2_K)
-    }
-#undef GQ_RPC
+    int n = 0; // (no resident form: Q5_K, Q3_K, Q2_K, Q4_0)
+    dispatch_resident(fmt, [&](auto f) {
+        return dispatch_nb(nb, [&](auto b) {
+            n = LDS_CAP / RCfg<decltype(f)::value, decltype(b)::value>::LDS;
+            return hipSuccess;
+        });
+    });
+    return n;
 }
 
+// one split per super-block
 RGemmPlan plan_rgemm(int64_t M, int64_t N, int64_t K)
 {
-    RGemmPlan p;
-    if (M < 1 || N < 1 || K < 256 || K % 256 != 0) return p;
-    p.nb = N > 64 ? 8 : (N > 32 ? 4 : (N > 16 ? 2 : 1));
-    p.tiles_m = (int)((M + RBM - 1) / RBM);
-    p.tiles_n = (int)((N + 16 * p.nb - 1) / (16 * p.nb));
-    p.splits = (int)(K / 256);
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n, nblk = tiles * p.splits;
-    // the partial blocks and their exponents, then the in-launch combine's flags and nonces
-    p.partial_bytes = p.splits > 1 ? ilc_flags_off(nblk, 16 * p.nb) + ilc_sync_bytes(nblk, tiles) : 0;
-    p.ok = true;
-    return p;
+    return plan_tiles(M, N, K, [](int64_t, int64_t nsb) { return (int)nsb; });
 }
 
 // The in-launch combine (ilc_combine) instead of the reduce launch: split-K plans whose grid the
@@ -1546,20 +1539,13 @@ unsigned int ilc_timeouts()
 
 RGemmPlan plan_sgemm(int64_t M, int64_t N, int64_t K, int splits)
 {
-    RGemmPlan p;
-    if (M < 1 || N < 1 || K < 256 || K % 256 != 0) return p;
-    p.nb = N > 64 ? 8 : (N > 32 ? 4 : (N > 16 ? 2 : 1));
-    p.tiles_m = (int)((M + RBM - 1) / RBM);
-    p.tiles_n = (int)((N + 16 * p.nb - 1) / (16 * p.nb));
-    const int64_t tiles = (int64_t)p.tiles_m * p.tiles_n, nsb = K / 256, cus = num_cus();
     // as many splits as keep the grid within one round of the chip (each at least one super-block)
-    int64_t S = splits > 0 ? splits : (tiles >= cus ? 1 : cus / tiles);
-    if (S > nsb) S = nsb;
-    p.splits = (int)(S < 1 ? 1 : S);
-    const int64_t nblk = tiles * p.splits;
-    p.partial_bytes = p.splits > 1 ? ilc_flags_off(nblk, 16 * p.nb) + ilc_sync_bytes(nblk, tiles) : 0;
-    p.ok = true;
-    return p;
+    return plan_tiles(M, N, K, [splits](int64_t tiles, int64_t nsb) {
+        const int64_t cus = num_cus();
+        int64_t S = splits > 0 ? splits : (tiles >= cus ? 1 : cus / tiles);
+        if (S > nsb) S = nsb;
+        return (int)(S < 1 ? 1 : S);
+    });
 }
 
 hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *C, void *partials, const RGemmPlan &p,
@@ -1567,14 +1553,9 @@ hipError_t launch_sgemm(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *
 {
     if (!p.ok) return hipErrorInvalidValue;
     return dispatch_fmt(fmt, [&](auto f) {
-        constexpr int F = decltype(f)::value;
-        switch (p.nb) {
-        case 1: return launch_snb<F, 1>(A, X, C, partials, p, M, N, K, ldc, s);
-        case 2: return launch_snb<F, 2>(A, X, C, partials, p, M, N, K, ldc, s);
-        case 4: return launch_snb<F, 4>(A, X, C, partials, p, M, N, K, ldc, s);
-        case 8: return launch_snb<F, 8>(A, X, C, partials, p, M, N, K, ldc, s);
-        default: return hipErrorInvalidValue;
-        }
+        return dispatch_nb(p.nb, [&](auto nb) {
+            return launch_snb<decltype(f)::value, decltype(nb)::value>(A, X, C, partials, p, M, N, K, ldc, s);
+        });
     });
 }
 
@@ -1585,7 +1566,7 @@ SortedPlan plan_sgemm_id(int64_t E, int64_t M, int64_t P, int64_t K)
     SortedPlan p;
     if (E < 1 || E > kMaxSortExperts || M < 1 || P < 1 || P > kMaxSortPairs || K < 256 || K % 256 != 0) return p;
     const int64_t ne = E < P ? E : P, avg = (P + ne - 1) / ne;
-    p.nb = avg > 64 ? 8 : (avg > 32 ? 4 : (avg > 16 ? 2 : 1));
+    p.nb = pick_nb(avg);
     p.tiles_m = (int)((M + RBM - 1) / RBM);
     p.t_max = (int)(ne + P / (16 * p.nb));
     if ((int64_t)p.tiles_m * p.t_max > INT32_MAX) return p;
@@ -1603,14 +1584,9 @@ hipError_t launch_sgemm_id(int fmt, const uint8_t *A, const uint16_t *X, uint16_
 {
     if (!p.ok) return hipErrorInvalidValue;
     return dispatch_fmt(fmt, [&](auto f) {
-        constexpr int F = decltype(f)::value;
-        switch (p.nb) {
-        case 1: return launch_sid<F, 1>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
-        case 2: return launch_sid<F, 2>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
-        case 4: return launch_sid<F, 4>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
-        case 8: return launch_sid<F, 8>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
-        default: return hipErrorInvalidValue;
-        }
+        return dispatch_nb(p.nb, [&](auto nb) {
+            return launch_sid<decltype(f)::value, decltype(nb)::value>(A, X, C, perm, hdr, table, p, M, K, ldc, s);
+        });
     });
 }
 
@@ -1618,8 +1594,9 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
 {
     SGroupPlan g;
     if (n < 1 || n > kMaxSParts || N < 1) return g;
-    g.nb = N > 64 ? 8 : (N > 32 ? 4 : (N > 16 ? 2 : 1));
+    g.nb = pick_nb(N);
     const int tn = (int)((N + 16 * g.nb - 1) / (16 * g.nb));
+    const PartLayout part = part_layout(16 * g.nb);
     int64_t units = 0, Lmax = 1;
     int set_lo = kSgemmSets, set_hi = 0; // the smallest and the largest case set over the parts that name one
     for (int i = 0; i < n; ++i) {
@@ -1688,7 +1665,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
             g.scap[i] = cap;
             g.splits[i] = cap;
             g.poff[i] = pb;
-            if (cap > 1) pb += ((size_t)cap * nt * (RBM * 16 * g.nb * 2 + RW * 4) + 255) & ~(size_t)255;
+            if (cap > 1) pb += part.bytes(cap * nt, 256);
             ust += nt * nsb;
         }
         // the in-launch combine's flags [tile * scap + slot] and nonces [tile] of the split parts
@@ -1724,7 +1701,7 @@ SGroupPlan plan_sgemm_grouped(const SGroupItem *items, int n, int64_t N, int spl
         g.wg0[i] = (int)wg0;
         wg0 += (int64_t)g.tiles_m[i] * tn * S;
         g.poff[i] = pb;
-        if (S > 1) pb += ((size_t)S * g.tiles_m[i] * tn * (RBM * 16 * g.nb * 2 + RW * 4) + 255) & ~(size_t)255;
+        if (S > 1) pb += part.bytes(S * g.tiles_m[i] * tn, 256);
     }
     g.tiles_n = tn;
     g.blocks = (int)wg0;
@@ -1746,12 +1723,16 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     a.streamk = r.streamk = g.streamk ? 1 : 0;
     int set = 0; // the kernel's case set
     for (int i = 0; i < n; ++i) set = std::max(set, fmt_info(items[i].fmt).sgemm_set);
-    const int nbi = g.nb == 1 ? 0 : (g.nb == 2 ? 1 : (g.nb == 4 ? 2 : 3));
-    static const int occ[kSgemmSets][4] = {{grouped_occ<1>(), grouped_occ<2>(), grouped_occ<4>(), grouped_occ<8>()},
-                                           {grouped_occ<1, 1>(), grouped_occ<2, 1>(), grouped_occ<4, 1>(), grouped_occ<8, 1>()},
-                                           {grouped_occ<1, 2>(), grouped_occ<2, 2>(), grouped_occ<4, 2>(), grouped_occ<8, 2>()},
-                                           {grouped_occ<1, 3>(), grouped_occ<2, 3>(), grouped_occ<4, 3>(), grouped_occ<8, 3>()}};
-    const int oc = occ[set][nbi];
+    // fn(ic<NB>, ic<SET>) for the launch's kernel
+    auto kernel = [&](auto fn) {
+        return dispatch_upto<kSgemmSets - 1>(set, [&](auto st) { return dispatch_nb(g.nb, [&](auto nb) { return fn(nb, st); }); });
+    };
+    int oc = 0;
+    hipError_t e = kernel([&](auto nb, auto st) {
+        oc = occupancy<sgemm_grouped_kernel<decltype(nb)::value, decltype(st)::value>>();
+        return hipSuccess;
+    });
+    if (e != hipSuccess) return e;
     a.ilc = g.streamk && tuning().rgemm_ilc != 0 && g.blocks <= num_cus() * oc ? 1 : 0;
     a.U = r.U = g.U;
     a.W = r.W = g.blocks;
@@ -1770,21 +1751,12 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
             rb += g.tiles_m[i] * g.tiles_n * bpt;
         }
     }
-    auto launch = [&](auto nb, auto st) {
+    return kernel([&](auto nb, auto st) {
         constexpr int NB = decltype(nb)::value;
         sgemm_grouped_kernel<NB, decltype(st)::value><<<dim3((unsigned)g.blocks), dim3(64 * RW), 0, s>>>(a);
         if (hipGetLastError() != hipSuccess) return hipErrorLaunchFailure;
         if (r.n > 0) reduce_grouped_kernel<NB><<<dim3((unsigned)rb), dim3(UPB), 0, s>>>(r);
         return hipGetLastError();
-    };
-    return dispatch_upto<kSgemmSets - 1>(set, [&](auto st) {
-        switch (g.nb) {
-        case 1: return launch(ic<1>{}, st);
-        case 2: return launch(ic<2>{}, st);
-        case 4: return launch(ic<4>{}, st);
-        case 8: return launch(ic<8>{}, st);
-        default: return hipErrorInvalidValue;
-        }
     });
 }
 
@@ -1793,19 +1765,14 @@ hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, in
 {
     if (!p.ok) return hipErrorInvalidValue;
     if (aq != 0 && ldx % 8 != 0) return hipErrorInvalidValue; // 16-byte activation loads
-#define GQ_RG_AQ(F)                                                                                                   \
-    switch (aq) {                                                                                                     \
-    case 0: return launch_f<F, 0>(A, X, ldx, C, partials, p, M, N, K, ldc, s);                                        \
-    case 1: return launch_f<F, 1>(A, X, ldx, C, partials, p, M, N, K, ldc, s);                                        \
-    default: return launch_f<F, 2>(A, X, ldx, C, partials, p, M, N, K, ldc, s);                                       \
-    }
-    switch (fmt) {
-    case Q8_0: GQ_RG_AQ(Q8_0)
-    case Q4_K: GQ_RG_AQ(Q4_K)
-    case Q6_K: GQ_RG_AQ(Q6_K)
-    default: return hipErrorInvalidValue; // (no resident form: Q5_K, Q3_K, Q2_K)
-    }
-#undef GQ_RG_AQ
+    return dispatch_resident(fmt, [&](auto f) {
+        return dispatch_upto<2>(aq, [&](auto q) { // (rgemm_kernel's AQ: 0, 1, 2)
+            return dispatch_nb(p.nb, [&](auto nb) {
+                return launch_nb<decltype(f)::value, decltype(nb)::value, decltype(q)::value>(A, X, ldx, C, partials, p, M, N,
+                                                                                             K, ldc, s);
+            });
+        });
+    });
 }
 
 } // namespace gq

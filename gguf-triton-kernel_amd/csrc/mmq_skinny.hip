@@ -105,13 +105,7 @@ __global__ __launch_bounds__(64 * SW) void skinny_kernel(const uint8_t *__restri
             for (int k = 1; k < KR; ++k) v += *(const f32x4 *)(red + (k * NT * RG + rt) * 256 + 4 * l);
             const int row = m0 + 16 * rf + 4 * (l >> 4), tok = 16 * t + (l & 15);
             if (row >= M || tok >= N) continue;
-            uint16_t *dst = C + (size_t)tok * ldc + row;
-            if (row + 4 <= M) {
-                *(u32x2 *)dst = (u32x2){(uint32_t)f2h_bits(v[0]) | ((uint32_t)f2h_bits(v[1]) << 16),
-                                        (uint32_t)f2h_bits(v[2]) | ((uint32_t)f2h_bits(v[3]) << 16)};
-            } else {
-                for (int i = 0; i < 4 && row + i < M; ++i) dst[i] = f2h_bits(v[i]);
-            }
+            store_h4(C + (size_t)tok * ldc + row, v, row, M);
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // red may be rewritten
     };
