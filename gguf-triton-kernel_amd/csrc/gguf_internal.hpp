@@ -75,6 +75,24 @@ struct DeqSeg {
 };
 hipError_t launch_act_quant_deq_grouped(const DeqSeg *segs, int n, hipStream_t s, int mode = ACT_DEQ); // or ACT_F8DEQ
 
+// Residual add + RMSNorm (rmsnorm.hip), one workgroup per row: h = R ? fp16(x + r) : x,
+// y = fp16((h * 1/sqrtf(mean(h^2) + eps)) * w).  Every output is optional: H and Y (fp16, rows ldh /
+// ldy apart) and act_quant's q8_1 forms of y, rows K apart -- xq + xd + xs (SOA; xraw: the fp16 copy
+// beside it) or xdeq (DEQ), never both.  N < 2^31, K % 32 == 0.
+constexpr int kNormChunk = 2048;   // elements a workgroup covers per step (256 lanes x 8)
+constexpr int kNormRegChunks = 8;  // rows up to this many chunks stay in registers; longer: read twice
+struct NormArgs {
+    const uint16_t *X, *R;
+    uint16_t *H, *Y;
+    const float *w;
+    float eps;
+    int64_t K, ldx, ldr, ldh, ldy;
+    int8_t *xq;
+    float *xd, *xs;
+    uint16_t *xdeq, *xraw;
+};
+hipError_t launch_rmsnorm(const NormArgs &a, int64_t N, hipStream_t s);
+
 // Decode-shaped GEMV (mmq_gemv.hip): C[t][m] for t < N_tok <= 8 from SOA activations.
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,
                        int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s);

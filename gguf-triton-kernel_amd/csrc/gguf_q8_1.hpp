@@ -163,6 +163,23 @@ __device__ __forceinline__ Q81Quad q8_1_quad(u32x4 w)
     return r;
 }
 
+// The DEQ form of a lane's 8 elements: x~ = fp16(d*q); each 4-element group in the order
+// (0,2,1,3): the order mmq_gemm.hip's packed dequantization produces weight pairs in (its
+// k-permutation; the MFMA k-sum is unchanged)
+__device__ __forceinline__ u32x4 deq_words(const Q81Quad &q)
+{
+    uint32_t o[4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float v4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v4[i] = q.d * (float)(int8_t)((q.codes[h] >> (8 * i)) & 0xff);
+        o[2 * h] = (uint32_t)f2h_bits(v4[0]) | ((uint32_t)f2h_bits(v4[2]) << 16);
+        o[2 * h + 1] = (uint32_t)f2h_bits(v4[1]) | ((uint32_t)f2h_bits(v4[3]) << 16);
+    }
+    return (u32x4){o[0], o[1], o[2], o[3]};
+}
+
 // The DEQ form's x~ = fp16(d * q) of one 32-element block held by an aligned group of 4 lanes
 // (8 elements each), bit-identical to q8_1_quad + the fp32 product act_quant.hip rounds (the
 // same amax, d, fp16-exact quotient and clamp), with the per-element tail on packed fp16: the

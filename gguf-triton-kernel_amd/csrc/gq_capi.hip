@@ -1316,6 +1316,96 @@ int gq_moe_route(const void *Wr, int wr_is_f16, const void *X, int64_t ldx, floa
                   "moe topk");
 }
 
+// The byte range [lo, hi) of an fp16 (N, K) tensor with rows ld elements apart (N, K >= 1)
+struct ByteRange {
+    uintptr_t lo, hi;
+};
+static ByteRange rows_range(const void *p, int64_t N, int64_t K, int64_t ld)
+{
+    return {(uintptr_t)p, (uintptr_t)p + (size_t)((N - 1) * ld + K) * 2};
+}
+static bool overlaps(ByteRange a, ByteRange b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// gq_rmsnorm's and gq_rmsnorm_prepare's checks, in this order (prep: with the workspace, which
+// needs `need` bytes).  empty: nothing to write.
+static int check_norm_args(bool prep, const void *X, const void *R, const void *H, const float *w, float eps, const void *Y,
+                           int64_t N, int64_t K, int64_t ldx, int64_t ldr, int64_t ldh, int64_t ldy, const void *workspace,
+                           size_t workspace_bytes, bool &empty)
+{
+    empty = false;
+    if (N < 0 || K < 0) return fail(GQ_EINVAL, "negative size N=%lld K=%lld", (long long)N, (long long)K);
+    if (K % 32 != 0) return fail(GQ_EINVAL, "K=%lld is not a multiple of 32", (long long)K);
+    if (!(eps >= 0.f) || eps == INFINITY) return fail(GQ_EINVAL, "eps=%g is not a finite value >= 0", (double)eps);
+    empty = N == 0 || K == 0;
+    if (empty) return GQ_OK;
+    if (!X || !w) return fail(GQ_EINVAL, "null pointer (X=%p w=%p)", X, (const void *)w);
+    if (!prep && !Y) return fail(GQ_EINVAL, "null pointer (Y=%p)", Y);
+    if (ldx < K) return fail(GQ_EINVAL, "ldx=%lld < K=%lld", (long long)ldx, (long long)K);
+    if (R && ldr < K) return fail(GQ_EINVAL, "ldr=%lld < K=%lld", (long long)ldr, (long long)K);
+    if (H && ldh < K) return fail(GQ_EINVAL, "ldh=%lld < K=%lld", (long long)ldh, (long long)K);
+    if (Y && ldy < K) return fail(GQ_EINVAL, "ldy=%lld < K=%lld", (long long)ldy, (long long)K);
+    const size_t need = prep ? gq::act_bytes(GQ_ACT_Q8_1, N, K) : 0;
+    if (prep && (!workspace || workspace_bytes < need)) return fail_workspace(workspace, workspace_bytes, need);
+    // H may BE X or R (the in-place residual update); any other overlap of an output with an input
+    // or with another output would have one row's stores race another row's loads
+    const ByteRange rx = rows_range(X, N, K, ldx), rr = R ? rows_range(R, N, K, ldr) : ByteRange{0, 0},
+                    rh = H ? rows_range(H, N, K, ldh) : ByteRange{0, 0}, ry = Y ? rows_range(Y, N, K, ldy) : ByteRange{0, 0},
+                    rw = prep ? ByteRange{(uintptr_t)workspace, (uintptr_t)workspace + need} : ByteRange{0, 0},
+                    rg = {(uintptr_t)w, (uintptr_t)w + (size_t)K * 4};
+    if (H && !(H == X && ldh == ldx) && overlaps(rh, rx)) return fail(GQ_EINVAL, "H overlaps X without being X (same base and stride)");
+    if (H && R && !(H == R && ldh == ldr) && overlaps(rh, rr)) return fail(GQ_EINVAL, "H overlaps R without being R (same base and stride)");
+    if (H && overlaps(rh, rg)) return fail(GQ_EINVAL, "H overlaps w");
+    if (Y && (overlaps(ry, rx) || (R && overlaps(ry, rr)) || (H && overlaps(ry, rh)) || overlaps(ry, rg)))
+        return fail(GQ_EINVAL, "Y overlaps X, R, H or w");
+    if (prep && (overlaps(rw, rx) || (R && overlaps(rw, rr)) || (H && overlaps(rw, rh)) || (Y && overlaps(rw, ry)) || overlaps(rw, rg)))
+        return fail(GQ_EINVAL, "the workspace overlaps X, R, H, Y or w");
+    if (N > INT32_MAX) return fail(GQ_EUNSUPPORTED, "N=%lld: one workgroup per row, N < 2^31", (long long)N);
+    return GQ_OK;
+}
+
+static gq::NormArgs norm_args(const void *X, const void *R, void *H, const float *w, float eps, void *Y, int64_t K, int64_t ldx,
+                              int64_t ldr, int64_t ldh, int64_t ldy)
+{
+    gq::NormArgs a{};
+    a.X = (const uint16_t *)X, a.R = (const uint16_t *)R, a.H = (uint16_t *)H, a.Y = (uint16_t *)Y;
+    a.w = w, a.eps = eps, a.K = K, a.ldx = ldx, a.ldr = ldr, a.ldh = ldh, a.ldy = ldy;
+    return a;
+}
+
+int gq_rmsnorm(const void *X, const void *R, void *H, const float *w, float eps, void *Y, int64_t N, int64_t K, int64_t ldx,
+               int64_t ldr, int64_t ldh, int64_t ldy, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    const int rc = check_norm_args(false, X, R, H, w, eps, Y, N, K, ldx, ldr, ldh, ldy, nullptr, 0, empty);
+    if (rc != GQ_OK || empty) return rc;
+    return hip_rc(gq::launch_rmsnorm(norm_args(X, R, H, w, eps, Y, K, ldx, ldr, ldh, ldy), N, (hipStream_t)stream), "rmsnorm");
+}
+
+int gq_rmsnorm_prepare(const void *X, const void *R, void *H, const float *w, float eps, void *Y, int64_t N, int64_t K,
+                       int64_t ldx, int64_t ldr, int64_t ldh, int64_t ldy, void *workspace, size_t workspace_bytes,
+                       void *stream)
+{
+    g_err.clear();
+    bool empty;
+    const int rc = check_norm_args(true, X, R, H, w, eps, Y, N, K, ldx, ldr, ldh, ldy, workspace, workspace_bytes, empty);
+    if (rc != GQ_OK || empty) return rc;
+    gq::NormArgs a = norm_args(X, R, H, w, eps, Y, K, ldx, ldr, ldh, ldy);
+    if (gq::use_i8(GQ_Q8_0, N, K, gq::tuning())) {
+        // gq_act_prepare writes the int8 form too: the norm into Y, then its launches on Y
+        if (!Y)
+            return fail(GQ_EUNSUPPORTED, "the int8 GEMM form (GQ_GEMM_I8) is written by gq_act_prepare: pass Y, or call "
+                                         "gq_rmsnorm and gq_act_prepare");
+        const hipError_t e = gq::launch_rmsnorm(a, N, (hipStream_t)stream);
+        if (e != hipSuccess) return hip_rc(e, "rmsnorm");
+        return prepare(GQ_ACT_Q8_1, Y, N, K, ldy, workspace, (hipStream_t)stream, 3);
+    }
+    const Carved c = carve(GQ_ACT_Q8_1, workspace, N, K);
+    if (gq::use_gemv(N, K)) a.xq = c.xq, a.xd = c.xd, a.xs = c.xs, a.xraw = c.xraw;
+    else a.xdeq = c.xdeq;
+    return hip_rc(gq::launch_rmsnorm(a, N, (hipStream_t)stream), "rmsnorm");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

@@ -140,7 +140,7 @@ def _w_val(f, v):
 def write_gguf(path, tensors, metadata=None, alignment=32):
     """Write a GGUF v3 file.  tensors: {name: (type_name, (M, K), raw bytes ndarray)}; a shape
     (E, M, K) writes the 3-D tensor of E expert matrices back to back (GGUF dims (K, M, E), as
-    blk.L.ffn_*_exps.weight of a mixture-of-experts model)."""
+    blk.L.ffn_*_exps.weight of a mixture-of-experts model), a shape (K,) a 1-D tensor (a norm weight)."""
     metadata = dict(metadata or {})
     metadata.setdefault("general.alignment", alignment)
     with open(path, "wb") as f:
@@ -152,9 +152,9 @@ def write_gguf(path, tensors, metadata=None, alignment=32):
         off = 0
         blobs = []
         for name, (tname, shape, raw) in tensors.items():
-            if len(shape) not in (2, 3):
-                raise ValueError(f"{name}: shape {tuple(shape)} is neither (M, K) nor (E, M, K)")
-            M, K = shape[-2:]
+            if len(shape) not in (1, 2, 3):
+                raise ValueError(f"{name}: shape {tuple(shape)} is neither (K,), (M, K) nor (E, M, K)")
+            M, K = shape[-2:] if len(shape) > 1 else (1, shape[0])
             E = shape[0] if len(shape) == 3 else 1
             _, qk, bb = GGML_TYPES[TYPE_IDS[tname]]
             raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)

@@ -86,6 +86,8 @@ SIGNATURES = {
     "gq_moe_combine_shared": ([_P, _P, _I, _P, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_moe_topk": ([_P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _P], _I),
     "gq_moe_route": ([_P, _I, _P, _I64, _P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_rmsnorm": ([_P, _P, _P, _P, ctypes.c_float, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_rmsnorm_prepare": ([_P, _P, _P, _P, ctypes.c_float, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
@@ -857,6 +859,86 @@ def act_prepare_grouped(items, act: str = "q8_1"):
         arr[i] = PrepItem(B.data_ptr(), N, K, B.stride(0), ws.data_ptr(), ws.numel())
     with torch.cuda.device(dev):
         _check(lib().gq_act_prepare_grouped(ACTS[act], arr, len(items), torch.cuda.current_stream(dev).cuda_stream))
+
+
+def _norm_rows(t: torch.Tensor | None, name: str, N: int, K: int, dev, out: bool = False):
+    """An fp16 (N, K) tensor of the norm entries with unit column stride and rows >= K apart:
+    (tensor, ld); an input of another layout is copied, an output must have it."""
+    if t is None:
+        return None, K
+    _require_device(t, name)
+    if t.device != dev:
+        raise RuntimeError(f"{name} on {t.device}, expected {dev}")
+    ok = t.dtype == torch.float16 and t.dim() == 2 and tuple(t.shape) == (N, K) and (K <= 1 or t.stride(1) == 1) and \
+        (N <= 1 or t.stride(0) >= K)
+    if not ok:
+        if out:
+            raise RuntimeError(f"{name} must be an fp16 ({N}, {K}) tensor with unit column stride and rows at least K apart")
+        if t.dim() != 2 or tuple(t.shape) != (N, K):
+            raise RuntimeError(f"{name} is {tuple(t.shape)}, expected ({N}, {K})")
+        t = t.to(torch.float16).contiguous()
+    return t, (t.stride(0) if N > 1 else max(t.stride(0), K))
+
+
+def _norm_args(x, w, eps, residual, y, h_out, need_y: bool):
+    _require_device(x, "x")
+    if x.dim() != 2:
+        raise RuntimeError("x must be an (N, K) tensor")
+    N, K = x.shape
+    dev = x.device
+    if K % 32 != 0:
+        raise RuntimeError(f"K={K} is not a multiple of 32")
+    _require_device(w, "w")
+    if w.device != dev or w.dtype != torch.float32 or w.numel() != K or not w.is_contiguous():
+        raise RuntimeError(f"w must hold K = {K} contiguous fp32 values on {dev}")
+    x, ldx = _norm_rows(x, "x", N, K, dev)
+    r, ldr = _norm_rows(residual, "residual", N, K, dev)
+    if y is None and need_y:
+        y = torch.empty((N, K), dtype=torch.float16, device=dev)
+    y, ldy = _norm_rows(y, "out", N, K, dev, out=True)
+    h, ldh = _norm_rows(h_out, "h_out", N, K, dev, out=True)
+    return x, ldx, r, ldr, y, ldy, h, ldh, N, K, dev
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, residual: torch.Tensor | None = None,
+            out: torch.Tensor | None = None, h_out: torch.Tensor | None = None) -> torch.Tensor:
+    """Residual add + RMSNorm in one launch (gq_rmsnorm): x fp16 (N, K), w K fp32 values ->
+    y = fp16((h / sqrt(mean(h^2) + eps)) * w) with h = fp16(x + residual) (h = x without a residual).
+    h_out: an fp16 (N, K) tensor that receives h, the new residual stream; it may be x or residual
+    themselves (the in-place update).  Returns y (out, when given).  No host sync, no fallback."""
+    x, ldx, r, ldr, y, ldy, h, ldh, N, K, dev = _norm_args(x, w, eps, residual, out, h_out, True)
+    if N * K == 0:
+        return y
+    with torch.cuda.device(dev):
+        _check(lib().gq_rmsnorm(x.data_ptr(), _ptr(r), _ptr(h), w.data_ptr(), float(eps), y.data_ptr(), N, K, ldx, ldr,
+                                ldh, ldy, _stream(dev)))
+    return y
+
+
+def rmsnorm_prepare(x: torch.Tensor, w: torch.Tensor, eps: float, workspace: torch.Tensor,
+                    residual: torch.Tensor | None = None, y_out: torch.Tensor | None = None,
+                    h_out: torch.Tensor | None = None):
+    """rmsnorm whose y is left in `workspace` as act_prepare(y, N, K, workspace) would leave it
+    (gq_rmsnorm_prepare, q8_1 activations): one launch, then any number of mmq_prepared calls with
+    this (N, K).  y_out: an fp16 (N, K) tensor that also receives y; h_out as rmsnorm's.  Where the
+    library writes the int8 GEMM form too (the GQ_GEMM_I8 tuning) and no y_out was given, the two
+    steps run here: rmsnorm into a temporary, then act_prepare -- the same bytes.  Returns y_out."""
+    x, ldx, r, ldr, y, ldy, h, ldh, N, K, dev = _norm_args(x, w, eps, residual, y_out, h_out, False)
+    _check_workspace(workspace, 0, dev)
+    if N * K == 0:
+        return y
+    with torch.cuda.device(dev):
+        rc = lib().gq_rmsnorm_prepare(x.data_ptr(), _ptr(r), _ptr(h), w.data_ptr(), float(eps), _ptr(y), N, K, ldx, ldr,
+                                      ldh, ldy, workspace.data_ptr(), workspace.numel(), _stream(dev))
+    if rc == GQ_EUNSUPPORTED and y is None:
+        act_prepare(rmsnorm(x, w, eps, r, None, h), N, K, workspace)
+        return None
+    _check(rc)
+    return y
 
 
 def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N: int, K: int,

@@ -35,6 +35,7 @@ import torch
 
 from . import _lib
 from .ffn import DenseFFN
+from .norm import RMSNorm
 
 
 class GGUFExperts:
@@ -207,7 +208,10 @@ class MoEBlock:
     keeps torch lines: ffn(x, ids, w) + shared(x), the latter times the gate where there is one."""
 
     def __init__(self, router: MoERouter, ffn: MoEFFN, shared: DenseFFN | None = None,
-                 shared_gate: torch.Tensor | None = None):
+                 shared_gate: torch.Tensor | None = None, norm: RMSNorm | None = None):
+        if norm is not None and norm.K != router.H:
+            raise ValueError(f"the norm has {norm.K} weights, the block's hidden size is {router.H}")
+        self.norm = norm
         if router.E != ffn.gate.E or router.H != ffn.gate.K:
             raise ValueError(f"router is {router.E} x {router.H} but the experts are {ffn.gate.E} x (ffn, {ffn.gate.K})")
         if shared is not None and (shared.gate.K != router.H or shared.down.M != router.H):
@@ -222,7 +226,7 @@ class MoEBlock:
 
     @classmethod
     def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", fused: bool = True,
-                  shared_experts: bool = False):
+                  shared_experts: bool = False, norm: bool = False):
         """From read_gguf()'s metadata and tensors: MoERouter.from_gguf and MoEFFN.from_gguf of the
         layer.  A layer with shared-expert tensors (blk.<layer>.ffn_*_shexp.weight) raises
         NotImplementedError: their output belongs in the sum and nothing here computes it --
@@ -230,7 +234,8 @@ class MoEBlock:
         any is present; a layer without any has no shared expert) become the block's DenseFFN
         (fused as the block), and the optional blk.<layer>.ffn_gate_inp_shexp.weight (f32 or f16,
         hidden values) its shared_gate.  That last tensor name is written from memory of llama.cpp's
-        qwen2moe graph; nothing here can check it against it."""
+        qwen2moe graph; nothing here can check it against it.
+        norm=True: blk.<layer>.ffn_norm.weight becomes the block's RMSNorm (RMSNorm.from_gguf)."""
         if not shared_experts:
             _refuse_shared_experts(tensors, layer)
         router = MoERouter.from_gguf(meta, tensors, layer, device, shared_experts=shared_experts)
@@ -247,7 +252,8 @@ class MoEBlock:
                     raise ValueError(f"{g.name}: expected {router.H} f32 or f16 values, got {g.type_name} dims {g.dims}")
                 np_dtype = np.float32 if g.type_name == "f32" else np.float16
                 gate = torch.from_numpy(np.array(g.data, dtype=np.uint8).view(np_dtype).reshape(1, router.H)).to(device)
-        return cls(router, ffn, shared, gate)
+        rms = RMSNorm.from_gguf(meta, tensors, f"blk.{layer}.ffn_norm", device) if norm else None
+        return cls(router, ffn, shared, gate, norm=rms)
 
     def token_gate(self, x: torch.Tensor) -> torch.Tensor | None:
         """The (N,) fp32 gate of the shared term, sigmoid(x . shared_gate), or None without one."""
@@ -255,6 +261,17 @@ class MoEBlock:
             return None
         _, g, _ = _lib.moe_route(self.shared_gate, x, 1, func="sigmoid", norm=False)
         return g.reshape(-1)
+
+    def forward_normed(self, x: torch.Tensor, residual: torch.Tensor | None = None):
+        """(out, h): h = fp16(x + residual) (x itself without a residual), out = forward(norm(h)) --
+        rmsnorm, one launch, then forward on y at every token count: the router and the expert
+        kernels read fp16."""
+        if self.norm is None:
+            raise RuntimeError("forward_normed needs MoEBlock(..., norm=RMSNorm(...))")
+        if residual is None:
+            return self.forward(self.norm(x)), x
+        y, h = self.norm(x, residual)
+        return self.forward(y), h
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         ids, w = self.router(x)

@@ -27,6 +27,8 @@
  *   gq_moe_combine_shared               that sum plus a shared expert's term
  *   gq_moe_topk                         a block's router selection: S expert ids and weights from fp32 logits
  *   gq_moe_route                        the router product and that selection, for decode
+ *   gq_rmsnorm                          residual add + RMSNorm of the hidden state, one launch
+ *   gq_rmsnorm_prepare                  the same, written as gq_act_prepare's q8_1 activations
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -125,9 +127,11 @@ size_t gq_mmq_call_workspace_size(gq_type t, gq_act act, int64_t M, int64_t N, i
  * Returns GQ_OK or an error code (gq_last_error() has the text; nothing was launched).
  *
  * Pointers and strides (gq_mmq[_ex], gq_act_prepare[_ex], gq_mmq_prepared[_ex], gq_dequantize,
- * gq_quantize_q8_1, gq_quantize_fp8; tests/test_gpu_strides.py holds every dense route to this):
- *   - B, C, W and X need fp16's 2-byte alignment and nothing more, and any row stride >= the row
- *     length (ldb >= K, ldc >= M, ldw >= K, ldx >= K; shorter: GQ_EINVAL).  Only the row's own K
+ * gq_quantize_q8_1, gq_quantize_fp8, gq_rmsnorm, gq_rmsnorm_prepare; tests/test_gpu_strides.py holds
+ * every dense route to this, tests/test_gpu_rmsnorm.py the two norm entries):
+ *   - B, C, W and X (the norm entries' X, R, H and Y) need fp16's 2-byte alignment and nothing more,
+ *     and any row stride >= the row length (ldb >= K, ldc >= M, ldw >= K, ldx >= K, and ldr, ldh,
+ *     ldy >= K; shorter: GQ_EINVAL).  Only the row's own K
  *     (M) elements are read (written): the ld - K pad columns, rows >= N and whatever lies in front
  *     of the base are never read into a result, and the ld - M pad columns of C are never written.
  *     A needs no alignment beyond its blocks' (a 16-byte load may read up to 15 bytes past its end).
@@ -491,6 +495,49 @@ int gq_moe_topk(const float *logits, int64_t ldl, const float *bias, int func, i
 int gq_moe_route(const void *Wr, int wr_is_f16, const void *X, int64_t ldx, float *logits, int64_t ldl, const float *bias,
                  int func, int norm, float scale, int32_t *ids, void *W, int w_is_f32, int64_t N, int64_t E, int64_t H,
                  int64_t S, void *stream);
+
+/*
+ * Residual add + RMSNorm of the hidden state, one launch, one workgroup per token:
+ *   X : fp16 (N, K), row n at element n*ldx.       R : NULL, or the residual, fp16 (N, K), rows ldr apart.
+ *   H : NULL, or fp16 (N, K), rows ldh apart: the new residual stream h.
+ *   w : K fp32 values (GGUF stores *_norm.weight as F32), 4-byte aligned.
+ *   Y : fp16 (N, K), rows ldy apart: the normed activations (required).
+ *   h[k]  = R ? fp16_rne(float(x[k]) + float(r[k])) : x[k]
+ *   ss    = sum_k float(h[k])^2 in fp32 (every square is exact; the additions in an order that is a
+ *           function of K alone: 256 lanes each sum their own elements in k order, then a tree)
+ *   scale = 1 / sqrtf(ss / K + eps), IEEE fp32 division and square root
+ *   y[k]  = fp16_rne((float(h[k]) * scale) * w[k]), two rounded fp32 products
+ * A token's h and y are the bits of its own one-token call, at every N, stride and base.
+ * H may be X or R themselves (the same base and the same stride: the in-place update of the
+ * residual stream).  Any other overlap of H with X or R, and Y (or w) overlapping X, R or H, is
+ * GQ_EINVAL: the byte ranges are compared on the host.  Only a row's K elements are read or written.
+ * K % 32 == 0, every ld >= K, eps finite and >= 0 (GQ_EINVAL otherwise, as a null X, w or Y or a
+ * negative size); N == 0 or K == 0: a no-op.  N >= 2^31: GQ_EUNSUPPORTED.  Every check precedes the
+ * launch.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol;
+ * gq_version() did not change with it.
+ */
+int gq_rmsnorm(const void *X, const void *R, void *H, const float *w, float eps, void *Y, int64_t N, int64_t K, int64_t ldx,
+               int64_t ldr, int64_t ldh, int64_t ldy, void *stream);
+
+/*
+ * gq_rmsnorm whose y goes straight into a workspace as gq_act_prepare(y, N, K, ...) would leave it
+ * (GQ_ACT_Q8_1): byte for byte that call's activation part -- the decode token counts' SOA codes,
+ * d and s with, where gq_act_prepare keeps one, the fp16 copy (y itself); from 5 tokens the fp16 x~
+ * -- so that any number of gq_mmq_prepared calls with this (N, K) follow.  One launch: y makes no
+ * round trip through memory and is quantized where it is made.
+ *   Y : may be NULL (y is then not stored); otherwise gq_rmsnorm's Y, the same bits.
+ *   workspace : >= gq_mmq_workspace_size(t, M, N, K) bytes for the products that follow; this call
+ *               needs and writes the activation part only.  It must not overlap X, R, H, Y or w.
+ * Checks: gq_rmsnorm's, then the workspace (null or short: GQ_EINVAL), then the overlaps.
+ * Where gq_act_prepare also writes the int8 GEMM form (the GQ_GEMM_I8=1 tuning, from 5 tokens at
+ * K % 256 == 0) this entry is gq_rmsnorm into Y followed by gq_act_prepare's launches on Y -- the
+ * same bytes -- and with Y == NULL it answers GQ_EUNSUPPORTED and launches nothing: call the two
+ * entries.  The fp8 activation variant is not part of this entry (gq_rmsnorm + gq_act_prepare_ex).
+ * Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol.
+ */
+int gq_rmsnorm_prepare(const void *X, const void *R, void *H, const float *w, float eps, void *Y, int64_t N, int64_t K,
+                       int64_t ldx, int64_t ldr, int64_t ldh, int64_t ldy, void *workspace, size_t workspace_bytes,
+                       void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE
