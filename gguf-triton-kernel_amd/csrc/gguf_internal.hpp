@@ -143,6 +143,7 @@ hipError_t launch_gemm(int fmt, const uint8_t *A, const GemmAct &x, uint16_t *C,
 // The split-K sum of the fp16 partials gemm_kernel (and rgemm_kernel, sgemm_kernel) write: tiles of
 // 16*8*rg rows x 16*nb tokens, S splits (mmq_gemm.hip gemm_reduce_f16_kernel; the partial's layout:
 // gguf_partial.hpp).
+int gemm_reduce_blocks(int tiles_x, int tiles_y, int rg, int nb); // its workgroups
 hipError_t launch_gemm_reduce_f16(int nb, int rg, const uint16_t *P, uint16_t *C, int64_t M, int64_t N, int64_t ldc,
                                   int S, int tiles_x, int tiles_y, hipStream_t s);
 
@@ -168,6 +169,8 @@ unsigned int kstream_timeouts();
 // resident workgroups one CU holds at once (LDS-bound: Q4_K at 16 tokens 3, at 32 two, else one);
 // 0 for a type without a resident form or an nb that is not pick_nb's
 int rgemm_per_cu(int fmt, int nb);
+// launch_rgemm takes the call: a plan, and 16-byte activation rows where the kernel quantizes them
+bool rgemm_call_ok(int aq, int64_t ldx, const RGemmPlan &p);
 hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *partials,
                         const RGemmPlan &p, int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s);
 // Streaming form (mmq_rgemm.hip sgemm_kernel): the same tile over K splits of several
@@ -366,8 +369,36 @@ struct SkinnyPlan {
     int rg = 1, nb = 1, d = 3;
 };
 SkinnyPlan plan_skinny(int fmt, int64_t M, int64_t N, int64_t K, int rg, int d);
+bool skinny_call_ok(int fmt, const SkinnyPlan &plan, int64_t M, int64_t N, int64_t K); // launch_skinny takes the call
 hipError_t launch_skinny(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *C, const SkinnyPlan &plan, int64_t M,
                          int64_t N, int64_t K, int64_t ldc, hipStream_t s);
+
+// The GEMM plans as data (gq_debug_gemm_plan): host only, one entry per kernel a launcher would
+// launch, written by the launcher's own deciding functions (each *_plan_info below sits beside its
+// launcher and calls what the launcher calls).  Fields that do not apply to a kernel stay 0.  ilc is
+// the plan's answer: the launchers also ask the runtime's occupancy for the kernel (a device query)
+// and take the two-launch form when the grid would not be resident; that check is not in here.
+enum GemmKernelId : int {
+    GK_NONE = 0, GK_RGEMM, GK_SGEMM, GK_SGEMM_ID, GK_SGEMM_GROUPED, GK_REDUCE_GROUPED, GK_GEMM, GK_GEMM_REDUCE_F16,
+    GK_GEMM_REDUCE, GK_SKINNY, GK_KSTREAM, GK_KSTREAM_REDUCE
+};
+struct GemmPlanInfo { // (gq_gemm_plan's fields, in its order)
+    int kernel, fmt, nb, rg, am, nl, aq, es, set, cwm;                    // the kernel and its template parameters
+    int splits, chunks_per_split, pf16, ilc, order, full, streamk;        // its run-time form
+    int tiles_m, tiles_n, blocks, item;                                   // its geometry; item: the list entry (-1: several)
+    int64_t rows, toks;                                                   // rows and tokens of this launch
+    uint64_t partial_bytes;                                               // partials the launch's plan needs
+};
+// appends to out[at..max_out) and returns the new count (entries past max_out are counted, not written)
+int rgemm_plan_info(int fmt, int aq, int64_t ldx, const RGemmPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out);
+int sgemm_plan_info(int fmt, const RGemmPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out);
+int sgemm_id_plan_info(int fmt, const SortedPlan &p, int64_t M, int64_t K, GemmPlanInfo *out, int at, int max_out);
+int sgemm_grouped_plan_info(const SGroupItem *items, int n, int64_t N, const SGroupPlan &g, const int *item_ids,
+                            GemmPlanInfo *out, int at, int max_out);
+int gemm_plan_info(int fmt, const GemmPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out);
+int skinny_plan_info(int fmt, const SkinnyPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out);
+int kstream_plan_info(const KItem *items, int n, int64_t N, int aq, const int *item_ids, GemmPlanInfo *out, int at,
+                      int max_out);
 
 // Dequantization and the library GEMM (mmq_dequant.hip).  perm: store 4-groups as (0,2,1,3),
 // matching act_quant's DEQ form.  blas_gemm returns 0 or a negative code.

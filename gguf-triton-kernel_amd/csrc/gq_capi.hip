@@ -694,6 +694,27 @@ bool sizable(int t, int act, int64_t M, int64_t N, int64_t K)
     return M >= 0 && N > 0 && K > 0 && K % gq::fmt_info(t).qk == 0;
 }
 
+// The launches of the chunked kernels (launch_plan, plan_entries): fn(m0, mc, n0, nc) per launch
+// until it fails; K_SGEMM cuts rows alone.  Chunks of < 2 GiB of weights and of activations per launch
+// (32-bit buffer offsets).
+template <class Fn> static hipError_t for_chunks(int64_t M, int64_t N, int64_t rows, int64_t toks, Fn &&fn)
+{
+    hipError_t e = hipSuccess;
+    for (int64_t n0 = 0; n0 < N && e == hipSuccess; n0 += toks)
+        for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += rows)
+            e = fn(m0, M - m0 < rows ? M - m0 : rows, n0, N - n0 < toks ? N - n0 : toks);
+    return e;
+}
+// a row chunk of the streaming GEMM plans its own splits
+static gq::RGemmPlan sgemm_chunk_plan(const gq::Plan &p, int64_t mc, int64_t M, int64_t N, int64_t K)
+{
+    return mc == M ? p.rg : gq::plan_sgemm(mc, N, K, gq::tuning().sgemm_splits);
+}
+static gq::KItem kstream_item(const gq::Call &c, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C)
+{
+    return gq::KItem{c.t, A, X, ldx, C, c.ldc, c.M, c.K};
+}
+
 } // namespace
 
 extern "C" {
@@ -841,7 +862,7 @@ static int launch_plan(const gq::Call &c, const gq::Plan &p, const void *A_, con
     }
     case gq::K_GEMV: return hip_rc(gq::launch_gemv(t, A, w.xq, w.xd, w.xs, C, M, N, K, ldc, s), "mmq");
     case gq::K_KSTREAM: {
-        const gq::KItem it{t, A, X, ldx, C, ldc, M, K};
+        const gq::KItem it = kstream_item(c, A, X, ldx, C);
         return hip_rc(gq::launch_kstream(&it, 1, N, p.aq, w.partials, s), "kstream");
     }
     case gq::K_RGEMM: // (+ the split-K reduce)
@@ -855,11 +876,10 @@ static int launch_plan(const gq::Call &c, const gq::Plan &p, const void *A_, con
         return hip_rc(gq::launch_sgemm_grouped(&it, 1, N, p.sg, w.partials, s), "sgemm");
     }
     case gq::K_SGEMM: // row chunks under the per-launch byte limit (Q5_K / Q3_K / Q2_K; the others are never cut)
-        for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += p.rows) {
-            const int64_t mc = M - m0 < p.rows ? M - m0 : p.rows;
-            e = gq::launch_sgemm(t, A + m0 * gq::row_bytes(t, K), w.xdeq, C + m0, w.partials,
-                                 mc == M ? p.rg : gq::plan_sgemm(mc, N, K, gq::tuning().sgemm_splits), mc, N, K, ldc, s);
-        }
+        e = for_chunks(M, N, p.rows, N, [&](int64_t m0, int64_t mc, int64_t, int64_t) {
+            return gq::launch_sgemm(t, A + m0 * gq::row_bytes(t, K), w.xdeq, C + m0, w.partials,
+                                    sgemm_chunk_plan(p, mc, M, N, K), mc, N, K, ldc, s);
+        });
         return hip_rc(e, "sgemm");
     case gq::K_SKINNY:
     case gq::K_GEMM:
@@ -871,26 +891,62 @@ static int launch_plan(const gq::Call &c, const gq::Plan &p, const void *A_, con
         x.ldx = ldx;
         return hip_rc(gq::launch_gemm(t, A, x, C, w.partials, p.gemm, M, N, K, ldc, s), "mmq");
     }
-    // chunks of < 2 GiB of weights and of activations per launch (32-bit buffer offsets)
-    for (int64_t n0 = 0; n0 < N && e == hipSuccess; n0 += p.toks)
-        for (int64_t m0 = 0; m0 < M && e == hipSuccess; m0 += p.rows) {
-            const int64_t mc = M - m0 < p.rows ? M - m0 : p.rows, nc = N - n0 < p.toks ? N - n0 : p.toks;
-            const uint8_t *Ac = A + m0 * gq::row_bytes(t, K);
-            uint16_t *Cc = C + n0 * ldc + m0;
-            if (p.kernel == gq::K_SKINNY) {
-                e = gq::launch_skinny(t, Ac, w.xdeq + n0 * K, Cc, gq::plan_skinny(t, mc, nc, K, gq::tuning().skinny_rg, 0),
-                                      mc, nc, K, ldc, s);
-                continue;
-            }
-            gq::GemmAct x;
-            x.xdeq = w.xdeq ? w.xdeq + n0 * K : nullptr;
-            x.xq = w.xq ? w.xq + n0 * K : nullptr;
-            x.xd = w.xd ? w.xd + n0 : nullptr;
-            x.ldd = gq::scale_ld(N);
-            e = gq::launch_gemm(t, Ac, x, Cc, w.partials, gq::plan_gemm(t, mc, nc, K, p.form), mc, nc, K, ldc, s);
-        }
+    e = for_chunks(M, N, p.rows, p.toks, [&](int64_t m0, int64_t mc, int64_t n0, int64_t nc) {
+        const uint8_t *Ac = A + m0 * gq::row_bytes(t, K);
+        uint16_t *Cc = C + n0 * ldc + m0;
+        if (p.kernel == gq::K_SKINNY)
+            return gq::launch_skinny(t, Ac, w.xdeq + n0 * K, Cc, gq::plan_skinny(t, mc, nc, K, gq::tuning().skinny_rg, 0), mc,
+                                     nc, K, ldc, s);
+        gq::GemmAct x;
+        x.xdeq = w.xdeq ? w.xdeq + n0 * K : nullptr;
+        x.xq = w.xq ? w.xq + n0 * K : nullptr;
+        x.xd = w.xd ? w.xd + n0 : nullptr;
+        x.ldd = gq::scale_ld(N);
+        return gq::launch_gemm(t, Ac, x, Cc, w.partials, gq::plan_gemm(t, mc, nc, K, p.form), mc, nc, K, ldc, s);
+    });
     return hip_rc(e, "mmq");
 }
+
+// launch_plan's launches as data (gq_debug_gemm_plan): the same switch, each case the kernel file's
+// *_plan_info beside the launcher launch_plan calls.  Returns the new entry count.
+static int plan_entries(const gq::Call &c, const gq::Plan &p, gq::GemmPlanInfo *out, int at, int max_out)
+{
+    const int t = c.t;
+    const int64_t M = c.M, N = c.N, K = c.K;
+    switch (p.kernel) {
+    case gq::K_NONE:
+    case gq::K_DECODE:
+    case gq::K_BLAS:
+    case gq::K_GEMV: return at; // (no GEMM kernel of the four files)
+    case gq::K_KSTREAM: {
+        const gq::KItem it = kstream_item(c, nullptr, nullptr, p.raw ? c.ldb : K, nullptr);
+        return gq::kstream_plan_info(&it, 1, N, p.aq, nullptr, out, at, max_out);
+    }
+    case gq::K_RGEMM:
+        return gq::rgemm_plan_info(t, p.aq, p.raw ? c.ldb : K, p.rg, M, N, K, out, at, max_out);
+    case gq::K_SGEMM_STREAMK: return gq::sgemm_grouped_plan_info(&p.item, 1, N, p.sg, nullptr, out, at, max_out);
+    case gq::K_SGEMM:
+        (void)for_chunks(M, N, p.rows, N, [&](int64_t, int64_t mc, int64_t, int64_t) {
+            at = gq::sgemm_plan_info(t, sgemm_chunk_plan(p, mc, M, N, K), mc, N, K, out, at, max_out);
+            return hipSuccess;
+        });
+        return at;
+    case gq::K_SKINNY:
+    case gq::K_GEMM: break;
+    }
+    if (p.raw) return gq::gemm_plan_info(t, p.gemm, M, N, K, out, at, max_out);
+    (void)for_chunks(M, N, p.rows, p.toks, [&](int64_t, int64_t mc, int64_t, int64_t nc) {
+        at = p.kernel == gq::K_SKINNY
+                 ? gq::skinny_plan_info(t, gq::plan_skinny(t, mc, nc, K, gq::tuning().skinny_rg, 0), mc, nc, K, out, at, max_out)
+                 : gq::gemm_plan_info(t, gq::plan_gemm(t, mc, nc, K, p.form), mc, nc, K, out, at, max_out);
+        return hipSuccess;
+    });
+    return at;
+}
+
+// gq_mmq_ex runs a raw call's own plan when it is one launch on the caller's activations (or refused);
+// every other raw call is act_quant + the prepared call's plan (Plan::raw)
+static bool runs_own_plan(const gq::Plan &p) { return p.raw || p.kernel == gq::K_NONE; }
 
 // gq_mmq_prepared_ex after the shape checks
 static int run_prepared(gq_type t, int act, const void *A, void *workspace, size_t workspace_bytes, void *C, int64_t M,
@@ -919,7 +975,7 @@ int gq_mmq_ex(gq_type t, gq_act act, const void *A, const void *B, void *C, int6
     const gq::Plan p = gq::plan_call(c, gq::tuning());
     const size_t need = p.ws_bytes();
     if (need && (!workspace || workspace_bytes < need)) return fail_workspace(workspace, workspace_bytes, need);
-    if (p.raw || p.kernel == gq::K_NONE) return launch_plan(c, p, A, B, workspace, C, (hipStream_t)stream); // (or refused)
+    if (runs_own_plan(p)) return launch_plan(c, p, A, B, workspace, C, (hipStream_t)stream); // (or refused)
     // act_quant, then the prepared call (its own plan: see Plan::raw)
     rc = prepare(act, B, N, K, ldb, workspace, (hipStream_t)stream, p.forms);
     if (rc != GQ_OK) return rc;
@@ -1094,6 +1150,16 @@ int gq_mmq_grouped(const gq_group_item *items, int n, int64_t N, void *stream)
     return gq_mmq_grouped_ex(GQ_ACT_Q8_1, items, n, N, stream);
 }
 
+// gq_mmq_grouped_ex at 5..32 tokens (fp8: 3..32): an item of the K-chunked stream's one launch (the
+// grouped launch's own route: the stream wherever it applies, GQ_KSTREAM=0 refuses; no K ranges; rows
+// the in-kernel quantizer can load)
+static bool grouped_ex_kstream_item(const gq::DecodeItem &d, gq_act act, int64_t N)
+{
+    return gq::grouped_kstream_item(d.fmt, act, d.M, N, d.K, d.ldx, d.ldc, d.C, false, gq::tuning()) &&
+           gq::kstream_splits(d.K) <= 1 && d.ldx % 8 == 0 && ((uintptr_t)d.X & 15) == 0;
+}
+static bool grouped_ex_is_kstream(gq_act act, int64_t N) { return N >= (act == GQ_ACT_FP8_E4M3 ? 3 : 5); }
+
 int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, void *stream)
 {
     g_err.clear();
@@ -1118,14 +1184,12 @@ int gq_mmq_grouped_ex(gq_act act, const gq_group_item *items, int n, int64_t N, 
     if (m == 0) return GQ_OK;
     // (3..4 q8_1 tokens stay on the grouped decode: the stream for the K <= 4096 items with the
     // long-K item on its own measured 13% slower on the 7B layer, profiles/r06/kstream_rawg3_ab.txt)
-    if (N >= (fp8 ? 3 : 5)) {
+    if (grouped_ex_is_kstream(act, N)) {
         // 5..32 tokens (fp8: 3..32): the K-chunked streaming MMQ, every item in one launch
         gq::KItem ki[16];
         for (int i = 0; i < m; ++i) {
             const gq::DecodeItem &d = di[i];
-            // (the grouped launch's own route: the stream wherever it applies, GQ_KSTREAM=0 refuses)
-            if (!gq::grouped_kstream_item(d.fmt, act, d.M, N, d.K, d.ldx, d.ldc, d.C, false, gq::tuning()) ||
-                gq::kstream_splits(d.K) > 1 || d.ldx % 8 != 0 || ((uintptr_t)d.X & 15) != 0)
+            if (!grouped_ex_kstream_item(d, act, N))
                 return fail(GQ_EUNSUPPORTED, "item %d (%s): not a grouped K-chunked-stream shape (N=%lld, M=%lld, K=%lld)", i,
                             gq::type_info(d.fmt).name, (long long)N, (long long)d.M, (long long)d.K);
             ki[i] = gq::KItem{d.fmt, d.A, d.X, d.ldx, d.C, d.ldc, d.M, d.K};
@@ -1455,7 +1519,9 @@ int gq_mmq_id_sorted(gq_type t, const void *A, const int32_t *ids, const void *B
 }
 
 // gq_mmq_grouped_prepared: the items as the grouped streaming GEMM takes them, or a GQ_* error
-static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int64_t N, gq::SGroupItem *out)
+// (shape_only: the plan query's items, whose pointers are null and not read)
+static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int64_t N, gq::SGroupItem *out,
+                              bool shape_only = false)
 {
     if (n < 0 || (n > 0 && !items)) return fail(GQ_EINVAL, "bad item list (n=%d, items=%p)", n, (const void *)items);
     if (n > 16) return fail(GQ_EUNSUPPORTED, "more than 16 items");
@@ -1465,12 +1531,12 @@ static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int6
         const int rc = check_mmq_shape(it.type, act, it.M, N, it.K);
         if (rc != GQ_OK) return rc;
         if (it.K % 256 != 0 || it.K == 0) return fail(GQ_EUNSUPPORTED, "item %d: K=%lld is not a multiple of 256", i, (long long)it.K);
-        if (it.M > 0 && (!it.A || !it.ws || !it.C)) return fail(GQ_EINVAL, "item %d: null pointer", i);
+        if (!shape_only && it.M > 0 && (!it.A || !it.ws || !it.C)) return fail(GQ_EINVAL, "item %d: null pointer", i);
         if (it.ldc < it.M) return fail(GQ_EINVAL, "item %d: ldc=%lld < M=%lld", i, (long long)it.ldc, (long long)it.M);
         if (gq::gemm_rows_per_launch(it.type, it.M, it.K, gq::tuning()) < it.M ||
             gq::gemm_toks_per_launch(N, it.K, gq::tuning()) < N)
             return fail(GQ_EUNSUPPORTED, "item %d: 2 GiB or more in one operand", i);
-        out[i] = gq::SGroupItem{it.type, (const uint8_t *)it.A, carve(act, const_cast<void *>(it.ws), N, it.K).xdeq,
+        out[i] = gq::SGroupItem{it.type, (const uint8_t *)it.A, shape_only ? nullptr : carve(act, const_cast<void *>(it.ws), N, it.K).xdeq,
                                 (uint16_t *)it.C, it.ldc, it.M, it.K};
     }
     return GQ_OK;
@@ -1481,8 +1547,9 @@ static int grouped_gemm_items(gq_act act, const gq_gemm_item *items, int n, int6
 // The stream's launch holds at most kKMaxParts (item, K range) parts: an item whose ranges would
 // pass that goes to the streaming GEMM (e.g. 16 items at K = 8192 are 32 parts: the first 12 take
 // the stream, the other 4 the GEMM).
+// kid, rid (the plan query): each launch's items as indices of the call's list.
 static void grouped_split(gq_act act, gq::SGroupItem *g, int n, int64_t N, gq::KItem *ks, int &nk, gq::SGroupItem *rest,
-                          int &nr)
+                          int &nr, int *kid = nullptr, int *rid = nullptr)
 {
     nk = nr = 0;
     int parts = 0;
@@ -1490,10 +1557,13 @@ static void grouped_split(gq_act act, gq::SGroupItem *g, int n, int64_t N, gq::K
         if (g[i].M <= 0) continue;
         const int np = gq::kstream_splits(g[i].K);
         if (gq::grouped_kstream_item(g[i].fmt, act, g[i].M, N, g[i].K, g[i].K, g[i].ldc, g[i].C, true, gq::tuning()) &&
-            parts + np <= gq::kKMaxParts && (parts += np, true))
+            parts + np <= gq::kKMaxParts && (parts += np, true)) {
+            if (kid) kid[nk] = i;
             ks[nk++] = gq::KItem{g[i].fmt, g[i].A, g[i].X, g[i].K, g[i].C, g[i].ldc, g[i].M, g[i].K};
-        else
+        } else {
+            if (rid) rid[nr] = i;
             rest[nr++] = g[i];
+        }
     }
 }
 
@@ -1613,6 +1683,78 @@ int gq_debug_decode_plan(int family, gq_act act, const gq_group_item *items, int
     default: return 0;
     }
     return gq::decode_plan_info(family, di, n, N, fp8, (gq::DecodePlanInfo *)out, max_out);
+}
+
+// Each entry point's checks and plan ahead of its launches, then the launches as data (plan_entries and
+// the kernel files' *_plan_info).
+int gq_debug_gemm_plan(int entry, gq_act act, const gq_group_item *items, int n, int64_t N, int64_t E, int64_t S,
+                       gq_gemm_plan *out_, int max_out)
+{
+    static_assert(sizeof(gq_gemm_plan) == sizeof(gq::GemmPlanInfo), "gq_gemm_plan is GemmPlanInfo");
+    static_assert((int)GQ_GK_NONE == gq::GK_NONE && (int)GQ_GK_RGEMM == gq::GK_RGEMM && (int)GQ_GK_SGEMM == gq::GK_SGEMM &&
+                      (int)GQ_GK_SGEMM_ID == gq::GK_SGEMM_ID && (int)GQ_GK_SGEMM_GROUPED == gq::GK_SGEMM_GROUPED &&
+                      (int)GQ_GK_REDUCE_GROUPED == gq::GK_REDUCE_GROUPED && (int)GQ_GK_GEMM == gq::GK_GEMM &&
+                      (int)GQ_GK_GEMM_REDUCE_F16 == gq::GK_GEMM_REDUCE_F16 && (int)GQ_GK_GEMM_REDUCE == gq::GK_GEMM_REDUCE &&
+                      (int)GQ_GK_SKINNY == gq::GK_SKINNY && (int)GQ_GK_KSTREAM == gq::GK_KSTREAM &&
+                      (int)GQ_GK_KSTREAM_REDUCE == gq::GK_KSTREAM_REDUCE,
+                  "GQ_GK_* is GemmKernelId");
+    g_err.clear();
+    gq::GemmPlanInfo *out = (gq::GemmPlanInfo *)out_;
+    if (n < 1 || n > 16 || !items || N < 1 || max_out < 0 || (max_out > 0 && !out)) return 0;
+    if (entry >= 0 && entry <= 2 && n != 1) return 0;
+    const gq_group_item &d = items[0];
+    int cnt = 0;
+    switch (entry) {
+    case 0:   // gq_mmq_ex
+    case 1: { // gq_mmq_prepared_ex
+        if (check_mmq_shape(d.type, act, d.M, N, d.K) != GQ_OK || d.M <= 0 || d.K <= 0) break;
+        gq::Call c = gq::shape_call(d.type, act, d.M, N, d.K, entry == 1);
+        gq::Plan p = gq::plan_call(c, gq::tuning());
+        if (entry == 0 && !runs_own_plan(p)) { // (act_quant, then run_prepared)
+            c = gq::shape_call(d.type, act, d.M, N, d.K, true);
+            p = gq::plan_call(c, gq::tuning());
+        }
+        cnt = plan_entries(c, p, out, 0, max_out);
+        break;
+    }
+    case 2: { // gq_mmq_id_sorted: N tokens x S slots on E experts
+        if (!gq::known_type(d.type) || d.M <= 0 || d.K <= 0) break;
+        cnt = gq::sgemm_id_plan_info(d.type, sorted_plan(d.type, E, d.M, N, S, d.K), d.M, d.K, out, 0, max_out);
+        break;
+    }
+    case 3: { // gq_mmq_grouped_prepared
+        gq_gemm_item gi[16];
+        gq::SGroupItem g[16], rest[16];
+        gq::KItem ks[16];
+        int nk, nr, kid[16], rid[16];
+        for (int i = 0; i < n; ++i) gi[i] = gq_gemm_item{items[i].type, nullptr, nullptr, nullptr, items[i].M, items[i].M, items[i].K};
+        if (grouped_gemm_items(act, gi, n, N, g, true) != GQ_OK) break;
+        grouped_split(act, g, n, N, ks, nk, rest, nr, kid, rid);
+        gq::SGroupPlan p;
+        if (nr > 0 && !(p = gq::plan_sgemm_grouped(rest, nr, N, gq::tuning().sgemm_splits)).ok) break; // (refused)
+        if (nk > 0) cnt = gq::kstream_plan_info(ks, nk, N, 0, kid, out, cnt, max_out);
+        if (nr > 0) cnt = gq::sgemm_grouped_plan_info(rest, nr, N, p, rid, out, cnt, max_out);
+        break;
+    }
+    case 4: { // gq_mmq_grouped_ex on the K-chunked stream
+        if (!grouped_ex_is_kstream(act, N)) break;
+        gq::KItem ki[16];
+        int m = 0;
+        for (int i = 0; i < n; ++i) {
+            const gq_group_item &it = items[i];
+            if (check_mmq_shape(it.type, act, it.M, N, it.K) != GQ_OK || it.K <= 0) return g_err.clear(), 0;
+            if (it.M == 0) continue;
+            const gq::DecodeItem di{it.type, nullptr, nullptr, it.K, nullptr, it.M, it.M, it.K};
+            if (!grouped_ex_kstream_item(di, act, N)) return 0;
+            ki[m++] = gq::KItem{di.fmt, di.A, di.X, di.ldx, di.C, di.ldc, di.M, di.K};
+        }
+        if (m > 0) cnt = gq::kstream_plan_info(ki, m, N, act == GQ_ACT_FP8_E4M3 ? 2 : 1, nullptr, out, 0, max_out);
+        break;
+    }
+    default: break;
+    }
+    g_err.clear();
+    return cnt;
 }
 
 int gq_debug_decode_cap(int family, int set, gq_type t, int nt, int fp8)

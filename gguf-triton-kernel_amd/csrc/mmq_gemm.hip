@@ -765,12 +765,19 @@ __global__ __launch_bounds__(256) void gemm_reduce_kernel(const float *__restric
     store_h4(C + tok * ldc + row, acc, row, M);
 }
 
+// the tile grid of a (rg, nb) kernel and the workgroups of its split-K sum (launch_cfg,
+// launch_gemm_reduce_f16, the plan query)
+int gemm_tiles_m(int64_t M, int rg) { return (int)((M + 16 * NWAVE * rg - 1) / (16 * NWAVE * rg)); }
+int gemm_tiles_n(int64_t N, int nb) { return (int)((N + 16 * nb - 1) / (16 * nb)); }
+int64_t gemm_reduce_units(int tiles_x, int tiles_y, int rg, int nb) { return (int64_t)tiles_x * tiles_y * (NWAVE * rg * nb * 64); }
+
 template <int F, int NB, int RG, int AM = AF_F16, int NL = 0, int AQ = 0>
 hipError_t launch_cfg(const uint8_t *A, const GemmAct &x, uint16_t *C, float *P, const GemmPlan &pl, int64_t M,
                       int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
     using G = Cfg<F, NB, RG, AM, NL, AQ>;
-    dim3 grid((unsigned)((M + G::BM - 1) / G::BM), (unsigned)((N + G::BN - 1) / G::BN), (unsigned)pl.splits);
+    static_assert(G::BM == 16 * NWAVE * RG && G::BN == 16 * NB, "gemm_tiles_m / gemm_tiles_n");
+    dim3 grid((unsigned)gemm_tiles_m(M, RG), (unsigned)gemm_tiles_n(N, NB), (unsigned)pl.splits);
     float *PP = pl.splits > 1 ? P : nullptr;
     const int cps = pl.chunks_per_split;
     const void *X = AQ ? (const void *)x.xraw : (G::CODES ? (const void *)x.xq : (const void *)x.xdeq);
@@ -791,50 +798,57 @@ hipError_t launch_cfg(const uint8_t *A, const GemmAct &x, uint16_t *C, float *P,
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || pl.splits == 1) return e;
     if (pl.pf16) {
-        const int64_t nq = (int64_t)grid.x * grid.y * (NWAVE * RG * NB * 64);
+        const int64_t nq = gemm_reduce_units((int)grid.x, (int)grid.y, RG, NB);
         gemm_reduce_f16_kernel<NB, RG><<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(
             (const uint16_t *)P, C, M, N, ldc, pl.splits, (int)grid.x, nq);
         return hipGetLastError();
     }
-    const int64_t nq = (int64_t)grid.x * grid.y * (NWAVE * RG * NB * 64);
+    const int64_t nq = gemm_reduce_units((int)grid.x, (int)grid.y, RG, NB);
     gemm_reduce_kernel<NB, RG><<<dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, s>>>(P, C, M, N, ldc, pl.splits,
                                                                                          (int)grid.x, nq);
     return hipGetLastError();
+}
+
+// The gemm_kernel<F, NB, RG, 0, AM, NL, AQ> a plan runs: launch_fmt's choice, and gemm_plan_info's.
+// nb = 0: no kernel (in-kernel quantization is built for 16-, 32- and 64-token tiles only).
+struct GemmInst {
+    int nb, rg, am, nl, aq;
+    bool is(int nb_, int rg_, int am_, int nl_, int aq_) const { return nb == nb_ && rg == rg_ && am == am_ && nl == nl_ && aq == aq_; }
+};
+GemmInst gemm_instance(int fmt, const GemmPlan &pl)
+{
+    const int nb = pl.nb == 1 || pl.nb == 2 || pl.nb == 4 ? pl.nb : 8;
+    if ((fmt == Q4_K || fmt == Q6_K) && pl.rg == 2 * R1 && pl.nb == 8) return {8, 2 * R1, AF_F16, pl.loaders == 4 ? 4 : 0, 0};
+    if (fmt == Q8_0 && pl.act == AF_I8) return {nb, 1, AF_I8, 0, 0};
+    if (pl.aq && pl.loaders == 4 && pl.rg == R1 && pl.act == AF_F16) return {nb == 8 ? 0 : nb, R1, AF_F16, 4, 1};
+    return {nb, R1, AF_F16, pl.loaders == 4 ? 4 : 0, 0};
 }
 
 template <int F>
 hipError_t launch_fmt(const uint8_t *A, const GemmAct &x, uint16_t *C, float *P, const GemmPlan &pl, int64_t M,
                       int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    if constexpr (F == Q4_K || F == Q6_K)
-        if (pl.rg == 2 * R1 && pl.nb == 8)
-            return pl.loaders == 4 ? launch_cfg<F, 8, 2 * R1, AF_F16, 4>(A, x, C, P, pl, M, N, K, ldc, s)
-                                   : launch_cfg<F, 8, 2 * R1>(A, x, C, P, pl, M, N, K, ldc, s);
-    if constexpr (F == Q8_0)
-        if (pl.act == AF_I8) switch (pl.nb) {
-            case 1: return launch_cfg<F, 1, 1, AF_I8>(A, x, C, P, pl, M, N, K, ldc, s);
-            case 2: return launch_cfg<F, 2, 1, AF_I8>(A, x, C, P, pl, M, N, K, ldc, s);
-            case 4: return launch_cfg<F, 4, 1, AF_I8>(A, x, C, P, pl, M, N, K, ldc, s);
-            default: return launch_cfg<F, 8, 1, AF_I8>(A, x, C, P, pl, M, N, K, ldc, s);
-            }
-    if (pl.aq && pl.loaders == 4 && pl.rg == R1 && pl.act == AF_F16) switch (pl.nb) {
-        case 1: return launch_cfg<F, 1, R1, AF_F16, 4, 1>(A, x, C, P, pl, M, N, K, ldc, s);
-        case 2: return launch_cfg<F, 2, R1, AF_F16, 4, 1>(A, x, C, P, pl, M, N, K, ldc, s);
-        case 4: return launch_cfg<F, 4, R1, AF_F16, 4, 1>(A, x, C, P, pl, M, N, K, ldc, s);
-        default: return hipErrorInvalidValue;
-        }
-    if (pl.loaders == 4) switch (pl.nb) {
-        case 1: return launch_cfg<F, 1, R1, AF_F16, 4>(A, x, C, P, pl, M, N, K, ldc, s);
-        case 2: return launch_cfg<F, 2, R1, AF_F16, 4>(A, x, C, P, pl, M, N, K, ldc, s);
-        case 4: return launch_cfg<F, 4, R1, AF_F16, 4>(A, x, C, P, pl, M, N, K, ldc, s);
-        default: return launch_cfg<F, 8, R1, AF_F16, 4>(A, x, C, P, pl, M, N, K, ldc, s);
-        }
-    switch (pl.nb) {
-    case 1: return launch_cfg<F, 1, R1>(A, x, C, P, pl, M, N, K, ldc, s);
-    case 2: return launch_cfg<F, 2, R1>(A, x, C, P, pl, M, N, K, ldc, s);
-    case 4: return launch_cfg<F, 4, R1>(A, x, C, P, pl, M, N, K, ldc, s);
-    default: return launch_cfg<F, 8, R1>(A, x, C, P, pl, M, N, K, ldc, s);
+    const GemmInst k = gemm_instance(F, pl);
+    // (the instantiations: every kernel this file builds for F)
+#define GQ_INST(NB_, RG_, AM_, NL_, AQ_) \
+    if (k.is(NB_, RG_, AM_, NL_, AQ_)) return launch_cfg<F, NB_, RG_, AM_, NL_, AQ_>(A, x, C, P, pl, M, N, K, ldc, s);
+#define GQ_INST_NB(RG_, AM_, NL_, AQ_) GQ_INST(1, RG_, AM_, NL_, AQ_) GQ_INST(2, RG_, AM_, NL_, AQ_) GQ_INST(4, RG_, AM_, NL_, AQ_)
+    if constexpr (F == Q4_K || F == Q6_K) {
+        GQ_INST(8, 2 * R1, AF_F16, 4, 0)
+        GQ_INST(8, 2 * R1, AF_F16, 0, 0)
     }
+    if constexpr (F == Q8_0) {
+        GQ_INST_NB(1, AF_I8, 0, 0)
+        GQ_INST(8, 1, AF_I8, 0, 0)
+    }
+    GQ_INST_NB(R1, AF_F16, 4, 1)
+    GQ_INST_NB(R1, AF_F16, 4, 0)
+    GQ_INST(8, R1, AF_F16, 4, 0)
+    GQ_INST_NB(R1, AF_F16, 0, 0)
+    GQ_INST(8, R1, AF_F16, 0, 0)
+#undef GQ_INST_NB
+#undef GQ_INST
+    return hipErrorInvalidValue;
 }
 
 } // namespace
@@ -842,13 +856,20 @@ hipError_t launch_fmt(const uint8_t *A, const GemmAct &x, uint16_t *C, float *P,
 hipError_t launch_gemm_reduce_f16(int nb, int rg, const uint16_t *P, uint16_t *C, int64_t M, int64_t N, int64_t ldc,
                                   int S, int tiles_x, int tiles_y, hipStream_t s)
 {
-    const int64_t nq = (int64_t)tiles_x * tiles_y * (NWAVE * rg * nb * 64);
-    const dim3 grid((unsigned)((nq + 255) / 256)), block(256);
+    const int64_t nq = gemm_reduce_units(tiles_x, tiles_y, rg, nb);
+    const dim3 grid((unsigned)gemm_reduce_blocks(tiles_x, tiles_y, rg, nb)), block(256);
 #define GQ_RED(NB_, RG_)                                                                                                   if (nb == NB_ && rg == RG_) {                                                                                              gemm_reduce_f16_kernel<NB_, RG_><<<grid, block, 0, s>>>(P, C, M, N, ldc, S, tiles_x, nq);                              return hipGetLastError();                                                                                          }
     GQ_RED(1, 2) GQ_RED(2, 2) GQ_RED(4, 2) GQ_RED(8, 2)
 #undef GQ_RED
     return hipErrorInvalidValue;
 }
+
+int gemm_reduce_blocks(int tiles_x, int tiles_y, int rg, int nb)
+{
+    return (int)((gemm_reduce_units(tiles_x, tiles_y, rg, nb) + 255) / 256);
+}
+// the types launch_gemm has kernels for (Q5_K, Q3_K, Q2_K, Q4_0 have no LDS-DMA GEMM form: the streaming GEMM takes them)
+bool gemm_has_fmt(int fmt) { return fmt == Q8_0 || fmt == Q4_K || fmt == Q6_K; }
 
 bool gemm_supported(int /*fmt*/, int64_t K) { return K > 0 && K % 256 == 0; }
 
@@ -914,12 +935,37 @@ GemmPlan plan_gemm(int fmt, int64_t M, int64_t N, int64_t K, int act)
 hipError_t launch_gemm(int fmt, const uint8_t *A, const GemmAct &x, uint16_t *C, float *P, const GemmPlan &plan,
                        int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
+    if (!gemm_has_fmt(fmt)) return hipErrorInvalidValue;
     switch (fmt) {
     case Q8_0: return launch_fmt<Q8_0>(A, x, C, P, plan, M, N, K, ldc, s);
     case Q4_K: return launch_fmt<Q4_K>(A, x, C, P, plan, M, N, K, ldc, s);
-    case Q6_K: return launch_fmt<Q6_K>(A, x, C, P, plan, M, N, K, ldc, s);
-    default: return hipErrorInvalidValue; // (Q5_K has no LDS-DMA GEMM form: the streaming GEMM takes it)
+    default: return launch_fmt<Q6_K>(A, x, C, P, plan, M, N, K, ldc, s);
     }
+}
+
+// gemm_kernel and its split-K sum as launch_fmt / launch_cfg launch them
+int gemm_plan_info(int fmt, const GemmPlan &pl, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out)
+{
+    (void)K;
+    if (!gemm_has_fmt(fmt)) return at;
+    const GemmInst k = gemm_instance(fmt, pl);
+    if (k.nb == 0) return at;
+    GemmPlanInfo e{};
+    e.kernel = GK_GEMM, e.fmt = fmt, e.nb = k.nb, e.rg = k.rg, e.am = k.am, e.nl = k.nl, e.aq = k.aq;
+    e.splits = pl.splits, e.chunks_per_split = pl.chunks_per_split, e.pf16 = pl.splits > 1 ? pl.pf16 : 0;
+    e.tiles_m = gemm_tiles_m(M, k.rg), e.tiles_n = gemm_tiles_n(N, k.nb);
+    e.blocks = e.tiles_m * e.tiles_n * pl.splits;
+    e.rows = M, e.toks = N, e.partial_bytes = pl.partial_bytes;
+    if (at < max_out) out[at] = e;
+    ++at;
+    if (pl.splits == 1) return at;
+    GemmPlanInfo r{};
+    r.kernel = pl.pf16 ? GK_GEMM_REDUCE_F16 : GK_GEMM_REDUCE, r.fmt = fmt, r.nb = k.nb, r.rg = k.rg;
+    r.splits = pl.splits, r.pf16 = pl.pf16, r.tiles_m = e.tiles_m, r.tiles_n = e.tiles_n;
+    r.blocks = gemm_reduce_blocks(e.tiles_m, e.tiles_n, k.rg, k.nb);
+    r.rows = M, r.toks = N;
+    if (at < max_out) out[at] = r;
+    return at + 1;
 }
 
 } // namespace gq

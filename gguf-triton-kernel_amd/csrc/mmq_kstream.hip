@@ -720,6 +720,31 @@ size_t kstream_partial_bytes(const KItem *items, int n, int64_t N)
 }
 
 namespace {
+// K range z of a matrix: its first super-block, its super-blocks and how many of them each wave takes
+struct KRange {
+    int kofs, nsbp, cw;
+};
+KRange kstream_range(int64_t K, int z)
+{
+    const int S = kstream_splits(K), nsb = (int)(K / 256), per = (nsb + S - 1) / S;
+    KRange r;
+    r.kofs = z * per;
+    r.nsbp = nsb - r.kofs < per ? nsb - r.kofs : per;
+    r.cw = (r.nsbp + KW - 1) / KW;
+    return r;
+}
+// The kstream_kernel<NB, CWM> of a launch: its token tiles and its largest chunk (launch_kstream, kstream_plan_info)
+struct KInst {
+    int nb, cwm;
+};
+KInst kstream_instance(int64_t N, int cwm) { return {N <= 16 ? 1 : 2, cwm <= 1 ? 1 : 2}; }
+// one workgroup per 16-row item up to the chip's share
+unsigned kstream_grid(int64_t items_total)
+{
+    const int64_t wgs = num_cus() * KWPC;
+    return (unsigned)(items_total < wgs ? items_total : wgs);
+}
+unsigned kstream_reduce_blocks(int64_t N, int64_t M) { return (unsigned)((N * (M / 4) + 255) / 256); }
 // C[t][m] = fp16(sum over the splits, in order, of the fp32 partials P[z][t][m]); four outputs per
 // thread, every split part of a launch in one grid
 struct KRed {
@@ -759,7 +784,7 @@ hipError_t launch_kstream(const KItem *items, int n, int64_t N, int aq, void *pa
     for (int i = 0; i < n; ++i) {
         const KItem &it = items[i];
         if (!kstream_ok(it.fmt, it.M, N, it.K)) return hipErrorInvalidValue;
-        const int S = kstream_splits(it.K), nsb = (int)(it.K / 256), per = (nsb + S - 1) / S;
+        const int S = kstream_splits(it.K);
         float *P = nullptr;
         if (S > 1) {
             if (!partials || rd.n == kKMaxParts) return hipErrorInvalidValue;
@@ -771,7 +796,7 @@ hipError_t launch_kstream(const KItem *items, int n, int64_t N, int aq, void *pa
             rd.M[rd.n] = (int)it.M;
             rd.S[rd.n] = S;
             rd.blk0[rd.n] = (int)rblk;
-            rblk += (N * (it.M / 4) + 255) / 256;
+            rblk += kstream_reduce_blocks(N, it.M);
             ++rd.n;
         }
         for (int z = 0; z < S; ++z) {
@@ -786,9 +811,10 @@ hipError_t launch_kstream(const KItem *items, int n, int64_t N, int aq, void *pa
             p.M = (int)it.M;
             p.K = (int)it.K;
             p.fmt = it.fmt;
-            p.kofs = z * per;
-            p.nsbp = nsb - p.kofs < per ? nsb - p.kofs : per;
-            p.cw = (p.nsbp + KW - 1) / KW;
+            const KRange kr = kstream_range(it.K, z);
+            p.kofs = kr.kofs;
+            p.nsbp = kr.nsbp;
+            p.cw = kr.cw;
             const int64_t sbb = fmt_info(it.fmt).sb_bytes();
             // the deal's cost of a 16-row item: per super-block its bytes - 55: Q4_K 89,
             // Q6_K 155, Q8_0 217 -- a Q6_K super-block's dequantization costs more per byte than the
@@ -812,15 +838,53 @@ hipError_t launch_kstream(const KItem *items, int n, int64_t N, int aq, void *pa
     a.wtot = wcum;
     a.slot = kb;
     a.ns = KRGN / kb > KNSMAX ? KNSMAX : KRGN / kb; // ring slots per wave (3 or 4)
-    const int64_t wgs = num_cus() * KWPC;
-    const unsigned grid = (unsigned)(items_total < wgs ? items_total : wgs);
+    const unsigned grid = kstream_grid(items_total);
+    const KInst k = kstream_instance(N, cwm);
     hipError_t e;
-    if (N <= 16) e = cwm <= 1 ? run<1, 1>(a, grid, s) : run<1, 2>(a, grid, s);
-    else e = cwm <= 1 ? run<2, 1>(a, grid, s) : run<2, 2>(a, grid, s);
+    if (k.nb == 1) e = k.cwm == 1 ? run<1, 1>(a, grid, s) : run<1, 2>(a, grid, s);
+    else e = k.cwm == 1 ? run<2, 1>(a, grid, s) : run<2, 2>(a, grid, s);
     if (e != hipSuccess || rd.n == 0) return e;
     rd.blk0[rd.n] = (int)rblk;
     kstream_reduce_kernel<<<dim3((unsigned)rblk), dim3(256), 0, s>>>(rd);
     return hipGetLastError();
+}
+
+// kstream_kernel and the K ranges' sum as launch_kstream launches them
+int kstream_plan_info(const KItem *items, int n, int64_t N, int aq, const int *item_ids, GemmPlanInfo *out, int at,
+                      int max_out)
+{
+    if (n < 1 || n > kKMaxParts || N < 1 || N > 32) return at;
+    int np = 0, nred = 0, cwm = 1, smax = 1;
+    int64_t items_total = 0, rblk = 0;
+    for (int i = 0; i < n; ++i) {
+        const KItem &it = items[i];
+        if (!kstream_ok(it.fmt, it.M, N, it.K)) return at;
+        const int S = kstream_splits(it.K);
+        if (S > 1) {
+            if (nred++ == kKMaxParts) return at;
+            rblk += kstream_reduce_blocks(N, it.M);
+        }
+        for (int z = 0; z < S; ++z) {
+            if (np++ == kKMaxParts) return at;
+            const int cw = kstream_range(it.K, z).cw;
+            items_total += it.M / 16;
+            cwm = cw > cwm ? cw : cwm;
+        }
+        smax = S > smax ? S : smax;
+    }
+    const KInst k = kstream_instance(N, cwm);
+    GemmPlanInfo e{};
+    e.kernel = GK_KSTREAM, e.fmt = n == 1 ? items[0].fmt : -1, e.nb = k.nb, e.cwm = k.cwm, e.aq = aq, e.splits = smax;
+    e.tiles_m = (int)items_total, e.tiles_n = 1, e.blocks = (int)kstream_grid(items_total);
+    e.item = n == 1 && item_ids ? item_ids[0] : (n == 1 ? 0 : -1);
+    e.rows = n == 1 ? items[0].M : 0, e.toks = N, e.partial_bytes = kstream_partial_bytes(items, n, N);
+    if (at < max_out) out[at] = e;
+    ++at;
+    if (nred == 0) return at;
+    GemmPlanInfo r{};
+    r.kernel = GK_KSTREAM_REDUCE, r.fmt = e.fmt, r.splits = smax, r.blocks = (int)rblk, r.item = e.item, r.rows = e.rows, r.toks = N;
+    if (at < max_out) out[at] = r;
+    return at + 1;
 }
 
 unsigned int kstream_timeouts()

@@ -1161,13 +1161,17 @@ __global__ __launch_bounds__(64 * RW) void sgemm_id_kernel(const uint8_t *__rest
     sgemm_body<F, NB, true>(Ae, Xe, C, nullptr, M, n, K, ldc, 0, id, 0, K / 256, lds, perm + row0);
 }
 
+int sgemm_full_arg(bool grouped); // (below, with the other launch-time decisions)
+// the sorted GEMM's grid: every row tile of every table entry the sort can write
+int64_t sgemm_id_blocks(const SortedPlan &p) { return (int64_t)p.tiles_m * p.t_max; }
+
 template <int F, int NB>
 hipError_t launch_sid(const uint8_t *A, const uint16_t *X, uint16_t *C, const int32_t *perm, const int32_t *hdr,
                       const int32_t *table, const SortedPlan &p, int64_t M, int64_t K, int64_t ldc, hipStream_t s)
 {
     const int64_t expert_bytes = M * (K / Layout<F>::QK) * Layout<F>::BYTES;
-    sgemm_id_kernel<F, NB><<<dim3((unsigned)((int64_t)p.tiles_m * p.t_max)), dim3(64 * RW), 0, s>>>(
-        A, expert_bytes, X, C, perm, hdr, table, M, K, ldc, tuning().sgemm_full != 0, p.tiles_m);
+    sgemm_id_kernel<F, NB><<<dim3((unsigned)sgemm_id_blocks(p)), dim3(64 * RW), 0, s>>>(
+        A, expert_bytes, X, C, perm, hdr, table, M, K, ldc, sgemm_full_arg(false), p.tiles_m);
     return hipGetLastError();
 }
 
@@ -1398,6 +1402,46 @@ template <auto Kernel> int occupancy()
     return occ;
 }
 
+// The launch-time decisions launch_snb / launch_es / launch_nb / launch_sid / launch_sgemm_grouped share
+// with the plan query (the *_plan_info functions at the end of this file).
+// sgemm_kernel's and sgemm_id_kernel's `full` argument (sgemm_full_body where the kernel has it: Q4_K
+// at 16- and 32-token tiles), and the grouped kernel's: GQ_SGEMM_FULL -1 is single matrices only
+int sgemm_full_arg(bool grouped) { return grouped ? tuning().sgemm_full > 0 : tuning().sgemm_full != 0; }
+// sgemm_kernel's grid order in its two-launch form: 2, the split-major order, where the activations
+// outgrow an XCD's 4 MiB L2 (each XCD then holds
+// its splits' slices only; 8192x28672 x128: FETCH / algorithmic bytes 1.39 -> 1.07 at the same
+// time, 97.9 vs 98.1 us).  Below that the 3-D grid's refetches are Infinity-Cache hits that
+// cost nothing and the split-major order measured 1.5-5% slower (4096x11008 x128 31.3 vs 30.7 us
+// -- though 1.80 -> 1.12 traffic --, 28672x8192 106.4 vs 104.8; profiles/r06/sgemm_zorder_ab.txt)
+#ifndef GQ_SGEMM_ZORDER
+#define GQ_SGEMM_ZORDER 1 // (A/B builds: -DGQ_SGEMM_ZORDER=0, the 3-D grid everywhere)
+#endif
+int sgemm_grid_order(const RGemmPlan &p, int64_t N, int64_t K)
+{
+    const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n * p.splits;
+    return GQ_SGEMM_ZORDER && p.splits > 1 && (blocks & 7) == 0 && N * K * 2 > ((int64_t)4 << 20) ? 2 : 0;
+}
+// rgemm_kernel's ES: the early-store form by template parameter, so that the classic form's registers
+// stay its own; built for two token tiles or more
+int rgemm_es(int nb) { return nb > 1 && ABL == 0 && rgemm_estore(nb) ? 1 : 0; }
+// sgemm_grouped_kernel's case set: the largest of the parts' types
+int sgemm_grouped_set(const SGroupItem *items, int n)
+{
+    int set = 0;
+    for (int i = 0; i < n; ++i) set = std::max(set, fmt_info(items[i].fmt).sgemm_set);
+    return set;
+}
+// the grouped kernel's in-launch combine as the plan decides it (launch_sgemm_grouped also asks the
+// runtime whether the grid is resident)
+bool sgemm_grouped_ilc(const SGroupPlan &g) { return g.streamk && tuning().rgemm_ilc != 0; }
+// reduce_grouped_kernel's workgroups per (row tile, token tile) of a split part
+constexpr int kRedUPB = 256; // reduce: threads per workgroup
+int reduce_grouped_bpt(int nb)
+{
+    const int tpu = nb == 1 ? 1 : 2, upt = RW * RRG * (nb / tpu) * 64;
+    return (upt + kRedUPB - 1) / kRedUPB;
+}
+
 template <int F, int NB>
 hipError_t launch_snb(const uint8_t *A, const uint16_t *X, uint16_t *C, void *P, const RGemmPlan &p, int64_t M,
                       int64_t N, int64_t K, int64_t ldc, hipStream_t s)
@@ -1405,24 +1449,16 @@ hipError_t launch_snb(const uint8_t *A, const uint16_t *X, uint16_t *C, void *P,
     const int64_t blocks = (int64_t)p.tiles_m * p.tiles_n * p.splits;
     if (sgemm_ilc(p) && blocks <= (int64_t)num_cus() * occupancy<sgemm_kernel<F, NB>>()) { // one kernel
         sgemm_kernel<F, NB><<<dim3((unsigned)blocks), dim3(64 * RW), 0, s>>>(A, X, C, (uint16_t *)P, M, N, K, ldc, 16,
-                                                                             tuning().sgemm_full != 0, p.tiles_m, p.tiles_n, 1);
+                                                                             sgemm_full_arg(false), p.tiles_m, p.tiles_n, 1);
         return hipGetLastError();
     }
-    // the split-major order where the activations outgrow an XCD's 4 MiB L2 (each XCD then holds
-    // its splits' slices only; 8192x28672 x128: FETCH / algorithmic bytes 1.39 -> 1.07 at the same
-    // time, 97.9 vs 98.1 us).  Below that the 3-D grid's refetches are Infinity-Cache hits that
-    // cost nothing and the split-major order measured 1.5-5% slower (4096x11008 x128 31.3 vs 30.7 us
-    // -- though 1.80 -> 1.12 traffic --, 28672x8192 106.4 vs 104.8; profiles/r06/sgemm_zorder_ab.txt)
-#ifndef GQ_SGEMM_ZORDER
-#define GQ_SGEMM_ZORDER 1 // (A/B builds: -DGQ_SGEMM_ZORDER=0, the 3-D grid everywhere)
-#endif
-    if (GQ_SGEMM_ZORDER && p.splits > 1 && (blocks & 7) == 0 && N * K * 2 > ((int64_t)4 << 20)) {
+    if (sgemm_grid_order(p, N, K) == 2) {
         sgemm_kernel<F, NB><<<dim3((unsigned)blocks), dim3(64 * RW), 0, s>>>(A, X, C, (uint16_t *)P, M, N, K, ldc, kSpol,
-                                                                             tuning().sgemm_full != 0, p.tiles_m, p.tiles_n, 2);
+                                                                             sgemm_full_arg(false), p.tiles_m, p.tiles_n, 2);
     } else {
         const dim3 grid((unsigned)p.tiles_m, (unsigned)p.tiles_n, (unsigned)p.splits);
         sgemm_kernel<F, NB><<<grid, dim3(64 * RW), 0, s>>>(A, X, C, (uint16_t *)P, M, N, K, ldc, kSpol,
-                                                            tuning().sgemm_full != 0, 0, 0, 0);
+                                                            sgemm_full_arg(false), 0, 0, 0);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || p.splits == 1) return e;
@@ -1447,13 +1483,12 @@ hipError_t launch_es(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t 
     return launch_gemm_reduce_f16(NB, RRG, (const uint16_t *)P, C, M, N, ldc, p.splits, p.tiles_m, p.tiles_n, s);
 }
 
-// the early-store form by template parameter, so that the classic form's registers stay its own
 template <int F, int NB, int AQ>
 hipError_t launch_nb(const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *P, const RGemmPlan &p,
                      int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
     if constexpr (NB > 1 && ABL == 0)
-        if (rgemm_estore(NB)) return launch_es<F, NB, AQ, 1>(A, X, ldx, C, P, p, M, N, K, ldc, s);
+        if (rgemm_es(NB)) return launch_es<F, NB, AQ, 1>(A, X, ldx, C, P, p, M, N, K, ldc, s);
     return launch_es<F, NB, AQ, 0>(A, X, ldx, C, P, p, M, N, K, ldc, s);
 }
 
@@ -1719,10 +1754,9 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     a.n = n;
     a.N = N;
     a.spol = kSpol;
-    a.full = tuning().sgemm_full > 0;
+    a.full = sgemm_full_arg(true);
     a.streamk = r.streamk = g.streamk ? 1 : 0;
-    int set = 0; // the kernel's case set
-    for (int i = 0; i < n; ++i) set = std::max(set, fmt_info(items[i].fmt).sgemm_set);
+    const int set = sgemm_grouped_set(items, n); // the kernel's case set
     // fn(ic<NB>, ic<SET>) for the launch's kernel
     auto kernel = [&](auto fn) {
         return dispatch_upto<kSgemmSets - 1>(set, [&](auto st) { return dispatch_nb(g.nb, [&](auto nb) { return fn(nb, st); }); });
@@ -1733,19 +1767,19 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
         return hipSuccess;
     });
     if (e != hipSuccess) return e;
-    a.ilc = g.streamk && tuning().rgemm_ilc != 0 && g.blocks <= num_cus() * oc ? 1 : 0;
+    a.ilc = sgemm_grouped_ilc(g) && g.blocks <= num_cus() * oc ? 1 : 0;
     a.U = r.U = g.U;
     a.W = r.W = g.blocks;
     r.N = N;
     int rb = 0;
-    constexpr int UPB = 256; // reduce: threads per workgroup
+    constexpr int UPB = kRedUPB;
     for (int i = 0; i < n; ++i) {
         uint16_t *P = (uint16_t *)((uint8_t *)partials + g.poff[i]);
         a.p[i] = SPart{items[i].fmt, items[i].A, items[i].X, items[i].C, P, items[i].M, items[i].K, items[i].ldc,
                        g.tiles_m[i], g.tiles_n, g.splits[i], g.wg0[i], g.ustart[i], g.scap[i], g.cost[i], g.cstart[i],
                        (uint64_t *)((uint8_t *)partials + g.foff[i]), (uint32_t *)((uint8_t *)partials + g.noff[i])};
         if (g.splits[i] > 1 && !a.ilc) {
-            const int tpu = g.nb == 1 ? 1 : 2, upt = RW * RRG * (g.nb / tpu) * 64, bpt = (upt + UPB - 1) / UPB;
+            const int bpt = reduce_grouped_bpt(g.nb);
             r.p[r.n++] = RPart{P,         items[i].C, items[i].M, items[i].ldc, g.tiles_m[i], g.tiles_n, g.splits[i], rb,
                                g.ustart[i], (int)(items[i].K / 256), g.scap[i], g.cost[i], g.cstart[i]};
             rb += g.tiles_m[i] * g.tiles_n * bpt;
@@ -1760,11 +1794,15 @@ hipError_t launch_sgemm_grouped(const SGroupItem *items, int n, int64_t N, const
     });
 }
 
+bool rgemm_call_ok(int aq, int64_t ldx, const RGemmPlan &p)
+{
+    return p.ok && aq >= 0 && aq <= 2 && (aq == 0 || ldx % 8 == 0); // 16-byte activation loads
+}
+
 hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, int64_t ldx, uint16_t *C, void *partials,
                         const RGemmPlan &p, int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    if (!p.ok) return hipErrorInvalidValue;
-    if (aq != 0 && ldx % 8 != 0) return hipErrorInvalidValue; // 16-byte activation loads
+    if (!rgemm_call_ok(aq, ldx, p)) return hipErrorInvalidValue;
     return dispatch_resident(fmt, [&](auto f) {
         return dispatch_upto<2>(aq, [&](auto q) { // (rgemm_kernel's AQ: 0, 1, 2)
             return dispatch_nb(p.nb, [&](auto nb) {
@@ -1773,6 +1811,92 @@ hipError_t launch_rgemm(int fmt, int aq, const uint8_t *A, const uint16_t *X, in
             });
         });
     });
+}
+
+// ---- the plans as data (gq_debug_gemm_plan) ----
+namespace {
+bool full_form(int fmt, int nb, bool grouped) { return fmt == Q4_K && nb <= 2 && sgemm_full_arg(grouped); }
+int put(const GemmPlanInfo &e, GemmPlanInfo *out, int at, int max_out)
+{
+    if (at < max_out) out[at] = e;
+    return at + 1;
+}
+int put_reduce_f16(int fmt, const RGemmPlan &p, int64_t M, int64_t N, GemmPlanInfo *out, int at, int max_out)
+{
+    GemmPlanInfo r{};
+    r.kernel = GK_GEMM_REDUCE_F16, r.fmt = fmt, r.nb = p.nb, r.rg = RRG, r.splits = p.splits, r.pf16 = 1;
+    r.tiles_m = p.tiles_m, r.tiles_n = p.tiles_n;
+    r.blocks = gemm_reduce_blocks(p.tiles_m, p.tiles_n, RRG, p.nb);
+    r.rows = M, r.toks = N;
+    return put(r, out, at, max_out);
+}
+} // namespace
+
+// rgemm_kernel as launch_rgemm / launch_nb / launch_es launch it
+int rgemm_plan_info(int fmt, int aq, int64_t ldx, const RGemmPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at,
+                    int max_out)
+{
+    (void)K;
+    if (!rgemm_call_ok(aq, ldx, p) || rgemm_per_cu(fmt, p.nb) == 0) return at; // (rgemm_per_cu: dispatch_resident's types)
+    GemmPlanInfo e{};
+    e.kernel = GK_RGEMM, e.fmt = fmt, e.nb = p.nb, e.rg = RRG, e.aq = aq, e.es = rgemm_es(p.nb);
+    e.splits = p.splits, e.chunks_per_split = 1, e.pf16 = p.splits > 1, e.ilc = rgemm_ilc(fmt, p);
+    e.tiles_m = p.tiles_m, e.tiles_n = p.tiles_n, e.blocks = p.tiles_m * p.tiles_n * p.splits;
+    e.rows = M, e.toks = N, e.partial_bytes = p.partial_bytes;
+    at = put(e, out, at, max_out);
+    return p.splits > 1 && !e.ilc ? put_reduce_f16(fmt, p, M, N, out, at, max_out) : at;
+}
+
+// sgemm_kernel as launch_sgemm / launch_snb launch it
+int sgemm_plan_info(int fmt, const RGemmPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out)
+{
+    if (!p.ok || !known_fmt(fmt)) return at;
+    GemmPlanInfo e{};
+    e.kernel = GK_SGEMM, e.fmt = fmt, e.nb = p.nb, e.rg = RRG;
+    e.splits = p.splits, e.chunks_per_split = (int)((K / 256 + p.splits - 1) / p.splits), e.pf16 = p.splits > 1;
+    e.ilc = sgemm_ilc(p), e.order = e.ilc ? 1 : sgemm_grid_order(p, N, K), e.full = full_form(fmt, p.nb, false);
+    e.tiles_m = p.tiles_m, e.tiles_n = p.tiles_n, e.blocks = p.tiles_m * p.tiles_n * p.splits;
+    e.rows = M, e.toks = N, e.partial_bytes = p.partial_bytes;
+    at = put(e, out, at, max_out);
+    return p.splits > 1 && !e.ilc ? put_reduce_f16(fmt, p, M, N, out, at, max_out) : at;
+}
+
+// sgemm_id_kernel as launch_sgemm_id / launch_sid launch it
+int sgemm_id_plan_info(int fmt, const SortedPlan &p, int64_t M, int64_t K, GemmPlanInfo *out, int at, int max_out)
+{
+    if (!p.ok || !known_fmt(fmt)) return at;
+    GemmPlanInfo e{};
+    e.kernel = GK_SGEMM_ID, e.fmt = fmt, e.nb = p.nb, e.rg = RRG, e.splits = 1, e.chunks_per_split = (int)(K / 256);
+    e.full = full_form(fmt, p.nb, false);
+    e.tiles_m = p.tiles_m, e.tiles_n = p.t_max, e.blocks = (int)sgemm_id_blocks(p);
+    e.rows = M, e.toks = 16 * p.nb;
+    return put(e, out, at, max_out);
+}
+
+// sgemm_grouped_kernel and reduce_grouped_kernel as launch_sgemm_grouped launches them: one entry per
+// part for the GEMM (its splits: the part's), then the reduce when a split part is not summed in the launch
+int sgemm_grouped_plan_info(const SGroupItem *items, int n, int64_t N, const SGroupPlan &g, const int *item_ids,
+                            GemmPlanInfo *out, int at, int max_out)
+{
+    if (!g.ok) return at;
+    const int set = sgemm_grouped_set(items, n);
+    if (set < 0 || set >= kSgemmSets) return at;
+    const bool ilc = sgemm_grouped_ilc(g);
+    int rb = 0;
+    for (int i = 0; i < n; ++i) {
+        GemmPlanInfo e{};
+        e.kernel = GK_SGEMM_GROUPED, e.fmt = items[i].fmt, e.nb = g.nb, e.rg = RRG, e.set = set;
+        e.splits = g.splits[i], e.chunks_per_split = (int)((items[i].K / 256 + g.splits[i] - 1) / g.splits[i]);
+        e.pf16 = g.splits[i] > 1, e.ilc = ilc, e.full = full_form(items[i].fmt, g.nb, true), e.streamk = g.streamk;
+        e.tiles_m = g.tiles_m[i], e.tiles_n = g.tiles_n, e.blocks = g.blocks, e.item = item_ids ? item_ids[i] : i;
+        e.rows = items[i].M, e.toks = N, e.partial_bytes = g.partial_bytes;
+        at = put(e, out, at, max_out);
+        if (g.splits[i] > 1 && !ilc) rb += g.tiles_m[i] * g.tiles_n * reduce_grouped_bpt(g.nb);
+    }
+    if (rb == 0) return at;
+    GemmPlanInfo r{};
+    r.kernel = GK_REDUCE_GROUPED, r.fmt = -1, r.nb = g.nb, r.rg = RRG, r.streamk = g.streamk, r.blocks = rb, r.item = -1, r.toks = N;
+    return put(r, out, at, max_out);
 }
 
 } // namespace gq

@@ -180,14 +180,17 @@ __global__ __launch_bounds__(64 * SW) void skinny_kernel(const uint8_t *__restri
     }
 }
 
+// persistent: one workgroup per CU (the 128 KiB activation ring fills its LDS), each a
+// contiguous range of units (16*rg rows)
+int64_t skinny_units(int64_t M, int rg) { return (M + 16 * rg - 1) / (16 * rg); }
+unsigned skinny_grid(int64_t nunits) { return (unsigned)(nunits < num_cus() ? nunits : num_cus()); }
+
 template <int F, int NT, int RG, int D>
 hipError_t launch_cfg(const uint8_t *A, const uint16_t *X, uint16_t *C, int64_t M, int64_t N, int64_t K, int64_t ldc,
                       hipStream_t s)
 {
-    // persistent: one workgroup per CU (the 128 KiB activation ring fills its LDS), each a
-    // contiguous range of units
-    const int64_t nunits = (M + 16 * RG - 1) / (16 * RG);
-    const unsigned grid = (unsigned)(nunits < num_cus() ? nunits : num_cus());
+    const int64_t nunits = skinny_units(M, RG);
+    const unsigned grid = skinny_grid(nunits);
     skinny_kernel<F, NT, RG, D><<<dim3(grid), dim3(64 * SW), 0, s>>>(A, X, C, (int)M, (int)N, (int)K, (int)ldc,
                                                                      (int)nunits);
     return hipGetLastError();
@@ -198,17 +201,27 @@ hipError_t launch_cfg(const uint8_t *A, const uint16_t *X, uint16_t *C, int64_t 
 template <int F> constexpr int rg_max() { return F == Q6_K ? 3 : 4; }
 int rg_max_of(int fmt) { return fmt == Q6_K ? 3 : 4; }
 
+// The skinny_kernel<F, NT, RG, 2> a plan runs: launch_fmt's choice, and skinny_plan_info's
+struct SkinnyInst {
+    int nt, rg;
+};
+SkinnyInst skinny_instance(int fmt, const SkinnyPlan &p)
+{
+    const int rmax = rg_max_of(fmt);
+    return {p.nb == 1 ? 1 : 2, p.rg >= rmax ? rmax : (p.rg >= 2 ? p.rg : 1)};
+}
+
 template <int F, int NT>
-hipError_t launch_nt(const uint8_t *A, const uint16_t *X, uint16_t *C, const SkinnyPlan &p, int64_t M, int64_t N,
-                     int64_t K, int64_t ldc, hipStream_t s)
+hipError_t launch_nt(const uint8_t *A, const uint16_t *X, uint16_t *C, int rg, int64_t M, int64_t N, int64_t K,
+                     int64_t ldc, hipStream_t s)
 {
     if constexpr (rg_max<F>() >= 4)
-        if (p.rg >= 4) return launch_cfg<F, NT, 4, 2>(A, X, C, M, N, K, ldc, s);
-    switch (p.rg) {
-    case 4:
+        if (rg == 4) return launch_cfg<F, NT, 4, 2>(A, X, C, M, N, K, ldc, s);
+    switch (rg) {
     case 3: return launch_cfg<F, NT, 3, 2>(A, X, C, M, N, K, ldc, s);
     case 2: return launch_cfg<F, NT, 2, 2>(A, X, C, M, N, K, ldc, s);
-    default: return launch_cfg<F, NT, 1, 2>(A, X, C, M, N, K, ldc, s);
+    case 1: return launch_cfg<F, NT, 1, 2>(A, X, C, M, N, K, ldc, s);
+    default: return hipErrorInvalidValue;
     }
 }
 
@@ -216,8 +229,9 @@ template <int F>
 hipError_t launch_fmt(const uint8_t *A, const uint16_t *X, uint16_t *C, const SkinnyPlan &p, int64_t M, int64_t N,
                       int64_t K, int64_t ldc, hipStream_t s)
 {
-    if (p.nb == 1) return launch_nt<F, 1>(A, X, C, p, M, N, K, ldc, s);
-    return launch_nt<F, 2>(A, X, C, p, M, N, K, ldc, s);
+    const SkinnyInst k = skinny_instance(F, p);
+    if (k.nt == 1) return launch_nt<F, 1>(A, X, C, k.rg, M, N, K, ldc, s);
+    return launch_nt<F, 2>(A, X, C, k.rg, M, N, K, ldc, s);
 }
 
 } // namespace
@@ -254,16 +268,35 @@ SkinnyPlan plan_skinny(int fmt, int64_t M, int64_t N, int64_t K, int rg, int d)
     return p;
 }
 
+bool skinny_call_ok(int fmt, const SkinnyPlan &plan, int64_t M, int64_t N, int64_t K)
+{
+    if (N < 1 || N > 32 || K % 256 != 0 || M < 1 || plan.rg < 1) return false;
+    return fmt == Q8_0 || fmt == Q4_K || fmt == Q6_K; // (no form of the other types)
+}
+
 hipError_t launch_skinny(int fmt, const uint8_t *A, const uint16_t *X, uint16_t *C, const SkinnyPlan &plan, int64_t M,
                          int64_t N, int64_t K, int64_t ldc, hipStream_t s)
 {
-    if (N < 1 || N > 32 || K % 256 != 0 || M < 1 || plan.rg < 1) return hipErrorInvalidValue;
+    if (!skinny_call_ok(fmt, plan, M, N, K)) return hipErrorInvalidValue;
     switch (fmt) {
     case Q8_0: return launch_fmt<Q8_0>(A, X, C, plan, M, N, K, ldc, s);
     case Q4_K: return launch_fmt<Q4_K>(A, X, C, plan, M, N, K, ldc, s);
-    case Q6_K: return launch_fmt<Q6_K>(A, X, C, plan, M, N, K, ldc, s);
-    default: return hipErrorInvalidValue; // (no Q5_K form)
+    default: return launch_fmt<Q6_K>(A, X, C, plan, M, N, K, ldc, s);
     }
+}
+
+// skinny_kernel as launch_fmt / launch_cfg launch it
+int skinny_plan_info(int fmt, const SkinnyPlan &p, int64_t M, int64_t N, int64_t K, GemmPlanInfo *out, int at, int max_out)
+{
+    if (!skinny_call_ok(fmt, p, M, N, K)) return at;
+    const SkinnyInst k = skinny_instance(fmt, p);
+    GemmPlanInfo e{};
+    e.kernel = GK_SKINNY, e.fmt = fmt, e.nb = k.nt, e.rg = k.rg, e.splits = 1;
+    e.tiles_m = (int)skinny_units(M, k.rg), e.tiles_n = 1;
+    e.blocks = (int)skinny_grid(e.tiles_m);
+    e.rows = M, e.toks = N;
+    if (at < max_out) out[at] = e;
+    return at + 1;
 }
 
 } // namespace gq

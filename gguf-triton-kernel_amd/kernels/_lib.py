@@ -52,6 +52,19 @@ class DecodePlan(ctypes.Structure):
                                               "ngroups", "stash_rows", "tokens", "set", "item", "lds")]
 
 
+class GemmPlan(ctypes.Structure):
+    """gq_gemm_plan (include/gguf_mmq.h)."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("kernel", "fmt", "nb", "rg", "am", "nl", "aq", "es", "set", "cwm", "splits",
+                                              "chunks_per_split", "pf16", "ilc", "order", "full", "streamk", "tiles_m",
+                                              "tiles_n", "blocks", "item")] + \
+               [("rows", _I64), ("toks", _I64), ("partial_bytes", ctypes.c_uint64)]
+
+
+# gq_gemm_plan.kernel (GQ_GK_*)
+GEMM_KERNELS = ("none", "rgemm_kernel", "sgemm_kernel", "sgemm_id_kernel", "sgemm_grouped_kernel", "reduce_grouped_kernel",
+                "gemm_kernel", "gemm_reduce_f16_kernel", "gemm_reduce_kernel", "skinny_kernel", "kstream_kernel",
+                "kstream_reduce_kernel")
+GEMM_ENTRIES = {"ex": 0, "prepared": 1, "id_sorted": 2, "grouped_prepared": 3, "grouped_ex": 4}
 DECODE_FAMILIES = {"dense": 0, "id": 1, "id_glu": 2, "glu": 3, "grouped": 4}
 
 SIGNATURES = {
@@ -92,6 +105,7 @@ SIGNATURES = {
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
     "gq_debug_decode_cap": ([_I, _I, _I, _I, _I], _I),
+    "gq_debug_gemm_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, _I64, _I64, ctypes.POINTER(GemmPlan), _I], _I),
     "gq_mmq_grouped_prepared_workspace_size": ([_I, ctypes.POINTER(GemmItem), _I, _I64], _SZ),
     "gq_mmq_grouped_prepared": ([_I, ctypes.POINTER(GemmItem), _I, _I64, _P, _SZ, _P], _I),
     "gq_last_error": ([], ctypes.c_char_p),
@@ -172,6 +186,21 @@ def decode_plan(family: str, items, N: int, act: str = "q8_1") -> list:
 def decode_cap(family: str, gtype: int, nt: int, fp8: bool = False, group_set: int = 0) -> int:
     """The most cached chunks a decode kernel of the family exists for (gq_debug_decode_cap), -1: none."""
     return int(lib().gq_debug_decode_cap(DECODE_FAMILIES[family], group_set, gtype, nt, int(fp8)))
+
+
+def gemm_plan(entry: str, items, N: int, act: str = "q8_1", E: int = 0, S: int = 0) -> list:
+    """The GEMM kernels a call would launch (gq_debug_gemm_plan; host only once GQ_CUS is set): a list of
+    GemmPlan in launch order, empty when the call takes none of them.  entry: "ex" (gq_mmq_ex),
+    "prepared", "id_sorted" (N tokens x S slots on E experts), "grouped_prepared", "grouped_ex";
+    items: (gtype, M, K), one for the first three, the launch's list for the grouped entries."""
+    arr = (GroupItem * len(items))(*[GroupItem(t, None, None, K, None, M, M, K) for t, M, K in items])
+    cap = 48
+    while True:  # (the entry counts every launch and writes the first `cap`: asked again when there are more)
+        out = (GemmPlan * cap)()
+        n = lib().gq_debug_gemm_plan(GEMM_ENTRIES[entry], ACTS[act], arr, len(items), N, E, S, out, cap)
+        if n <= cap:
+            return [out[i] for i in range(n)]
+        cap = n
 
 
 def reset_tuning():

@@ -619,6 +619,47 @@ int gq_debug_decode_plan(int family, gq_act act, const gq_group_item *items, int
 /* The most cached chunks (itc) a decode kernel of the family exists for at (type, token tile nt in
  * 1, 2, 4, fp8 form), or -1 when it has none; family as above, set: family 4's case set (0..4). */
 int gq_debug_decode_cap(int family, int set, gq_type t, int nt, int fp8);
+/* The GEMM kernels a call would launch under the current tuning, host only (no device is touched once
+ * GQ_CUS is set): what tests/gemm_cases.py builds its case table from.  entry: 0 gq_mmq_ex, 1
+ * gq_mmq_prepared_ex, 2 gq_mmq_id_sorted (N tokens x S slots on E experts) -- items[0]'s type, M and K
+ * with n = 1 --, 3 gq_mmq_grouped_prepared, 4 gq_mmq_grouped_ex at 5..32 tokens (fp8: 3..32) on the n
+ * items; E and S are read by entry 2 alone.  Pointers and strides in the items are not read: the call
+ * is taken as contiguous and aligned, as gq_debug_route takes it.  Returns how many entries the call's
+ * launches have, at most max_out of them written to out: one per launched kernel in launch order (a
+ * raw call's act_quant launch is not listed), sgemm_grouped_kernel one per item of its launch; 0 when
+ * the call takes no kernel of mmq_rgemm / mmq_gemm / mmq_skinny / mmq_kstream (decode, GEMV, the
+ * library GEMM, a refused shape).  Fields that do not apply to a kernel are 0.
+ *   kernel            : GQ_GK_*
+ *   fmt               : the weight type (-1: a launch of several items)
+ *   nb, rg, am, nl, aq, es, set, cwm : the template parameters -- token tiles of 16 (skinny, kstream: NT, NB), row
+ *                       groups, activation form, loader waves, in-kernel quantization (1 q8_1, 2 fp8),
+ *                       early store, the grouped case set, kstream's chunk form
+ *   splits, chunks_per_split, pf16 : the K splits, super-blocks per split (the longest), fp16 partials
+ *   ilc               : the split-K sum inside the launch AS THE PLAN DECIDES IT.  The launchers also ask
+ *                       the runtime how many workgroups of the kernel a CU admits and take the
+ *                       two-launch form when the grid would not be resident; that check needs the
+ *                       device and is not part of this answer
+ *   order             : sgemm_kernel's grid order (0 3-D grid, 1 in-launch sum, 2 split-major)
+ *   full, streamk     : sgemm_full_body runs (Q4_K, 16/32-token tiles); the stream-K unit split
+ *   tiles_m, tiles_n, blocks : row tiles (skinny: units, kstream: 16-row items), token tiles (sorted:
+ *                       table entries), workgroups of the launch
+ *   item              : the entry's index in items (-1: a launch of several)
+ *   rows, toks        : rows and tokens of this launch (the chunked kernels: the chunk's)
+ *   partial_bytes     : the partials this launch's plan needs (the ABI's workspace sizes cover them)
+ * A debug entry point: it does not move gq_version. */
+enum {
+    GQ_GK_NONE = 0, GQ_GK_RGEMM, GQ_GK_SGEMM, GQ_GK_SGEMM_ID, GQ_GK_SGEMM_GROUPED, GQ_GK_REDUCE_GROUPED, GQ_GK_GEMM,
+    GQ_GK_GEMM_REDUCE_F16, GQ_GK_GEMM_REDUCE, GQ_GK_SKINNY, GQ_GK_KSTREAM, GQ_GK_KSTREAM_REDUCE
+};
+typedef struct gq_gemm_plan {
+    int32_t kernel, fmt, nb, rg, am, nl, aq, es, set, cwm;
+    int32_t splits, chunks_per_split, pf16, ilc, order, full, streamk;
+    int32_t tiles_m, tiles_n, blocks, item;
+    int64_t rows, toks;
+    uint64_t partial_bytes;
+} gq_gemm_plan;
+int gq_debug_gemm_plan(int entry, gq_act act, const gq_group_item *items, int n, int64_t N, int64_t E, int64_t S,
+                       gq_gemm_plan *out, int max_out);
 /* How many synchronisation waits inside a kernel gave up since the library was loaded: the
  * resident GEMM's in-launch split-K combine (only possible when another kernel holds CUs its grid
  * needed) and the K-chunked stream's cross-wave hand-off.  A wait gives up after a bounded spin
