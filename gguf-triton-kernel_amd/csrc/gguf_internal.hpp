@@ -34,6 +34,7 @@ struct Tuning {
                                               // 1 every streaming GEMM, 0 none, -1 single matrices (measured gain)
     int kstream = -1;                         // GQ_KSTREAM: K-chunked streaming MMQ -1 auto / 0 off / 1 wherever it applies
     int cus = 0;                              // GQ_CUS: compute units to plan for (0: the device's count)
+    int attn_w = 0;                           // GQ_ATTN_W: decode attention's workgroups per (sequence, kv head) (0: auto)
     int ablate = 0;                           // GQ_ABLATE (GQ_ABLATION diagnostic builds only)
 };
 const Tuning &tuning();
@@ -92,6 +93,34 @@ struct NormArgs {
     uint16_t *xdeq, *xraw;
 };
 hipError_t launch_rmsnorm(const NormArgs &a, int64_t N, hipStream_t s);
+
+// Decode attention over an fp16 (kv 0) or Q8_0 (kv 1) KV cache (attn_decode.hip; gq_attn_decode):
+// B * n_kv_head * W workgroups, each its contiguous share of its sequence's kAttnTile-key tiles (the
+// length read from kv_len on the device), then a combine of the W fp32 partials of every row.
+// None of the three constants was measured against another value: kAttnTile is one k-step of the
+// second product, kAttnRing the least that keeps a tile in flight under the current one (at fp16,
+// D = 128 it fills the LDS), kAttnMaxW bounds the partials a row's combine reads.
+constexpr int kAttnTile = 32;  // keys per tile (one wave's unit of work)
+constexpr int kAttnRing = 2;   // LDS ring slots per wave (K tile + V tile each)
+constexpr int kAttnMaxW = 64;  // workgroups per (sequence, kv head), at most
+struct AttnPlan {
+    bool ok = false;           // D in {64, 128}, n_head % n_kv_head == 0, R <= 32
+    int R = 0, W = 0, grid = 0;
+    size_t workspace_bytes = 0;
+};
+struct AttnCall {
+    const void *Q, *Kc, *Vc;
+    const int32_t *kv_len;
+    void *O, *workspace;
+    int64_t ldq, ldo, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D;
+    float scale;
+};
+AttnPlan plan_attn(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D);
+hipError_t launch_attn_decode(int kv, const AttnCall &c, const AttnPlan &p, hipStream_t s);
+// The N new tokens' k and v rows (fp16, rows ldn apart) into the caches at kv_len[b] - N .. kv_len[b] - 1
+hipError_t launch_kv_append(int kv, const void *Kn, const void *Vn, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
+                            int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B,
+                            int64_t N, int64_t n_kv_head, int64_t D, hipStream_t s);
 
 // Decode-shaped GEMV (mmq_gemv.hip): C[t][m] for t < N_tok <= 8 from SOA activations.
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,

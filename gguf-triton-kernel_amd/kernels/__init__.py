@@ -10,4 +10,17 @@
 
 Each computes C = (A @ B^T)^T with A a packed GGUF weight tensor (int8, flat) and B fp16
 activations (N, K), returning fp16 (N, M) -- the reference's signature and layout.
+
+Beyond the reference, decode attention over an fp16 or Q8_0 KV cache (kernels/attention.py):
+
+    from kernels import KVCache, attn_decode, kv_append
 """
+_LAZY = {"KVCache": "attention", "attn_decode": "_lib", "kv_append": "_lib"}
+__all__ = list(_LAZY)
+
+
+def __getattr__(name):  # (on first use: importing the package loads neither torch nor the library)
+    if name in _LAZY:
+        import importlib
+        return getattr(importlib.import_module(f"{__name__}.{_LAZY[name]}"), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

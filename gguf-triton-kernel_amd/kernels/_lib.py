@@ -101,6 +101,11 @@ SIGNATURES = {
     "gq_moe_route": ([_P, _I, _P, _I64, _P, _I64, _P, _I, _I, ctypes.c_float, _P, _P, _I, _I64, _I64, _I64, _I64, _P], _I),
     "gq_rmsnorm": ([_P, _P, _P, _P, ctypes.c_float, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_rmsnorm_prepare": ([_P, _P, _P, _P, ctypes.c_float, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
+    "gq_attn_decode_workspace_size": ([_I64, _I64, _I64, _I64, _I64], _SZ),
+    "gq_attn_decode": ([_I, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64,
+                        _I64, _P, _SZ, _P], _I),
+    "gq_debug_attn_plan": ([_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
+    "gq_kv_append": ([_I, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
@@ -968,6 +973,84 @@ def rmsnorm_prepare(x: torch.Tensor, w: torch.Tensor, eps: float, workspace: tor
         return None
     _check(rc)
     return y
+
+
+KV_KINDS = {"f16": 0, "q8_0": 1}  # gq_kv_type
+
+
+def kv_row_bytes(kind: str, D: int) -> int:
+    """Bytes of one (position, kv head) cache row: D fp16 values or D/32 Q8_0 blocks."""
+    return 2 * D if kind == "f16" else 34 * (D // 32)
+
+
+def attn_plan(B: int, N: int, n_head: int, n_kv_head: int, D: int):
+    """(keys per tile, workgroups W per (sequence, kv head)) of an attn_decode call (gq_debug_attn_plan)."""
+    tile, W = ctypes.c_int(), ctypes.c_int()
+    _check(lib().gq_debug_attn_plan(B, N, n_head, n_kv_head, D, ctypes.byref(tile), ctypes.byref(W)))
+    return tile.value, W.value
+
+
+def attn_workspace_size(B: int, N: int, n_head: int, n_kv_head: int, D: int) -> int:
+    return int(lib().gq_attn_decode_workspace_size(B, N, n_head, n_kv_head, D))
+
+
+def _kv_rows(t: torch.Tensor, name: str, rows: int, cols: int, dev):
+    _require_device(t, name)
+    if t.device != dev or t.dtype != torch.float16 or t.dim() != 2 or tuple(t.shape) != (rows, cols) or t.stride(1) != 1 \
+            or t.stride(0) < cols:
+        raise RuntimeError(f"{name} must be an fp16 ({rows}, {cols}) tensor on {dev} with unit column stride")
+    return t.stride(0)
+
+
+def _kv_caches(Kc, Vc, kv_len, B, dev):
+    for t, name in ((Kc, "Kc"), (Vc, "Vc"), (kv_len, "kv_len")):
+        _require_device(t, name)
+        if t.device != dev:
+            raise RuntimeError(f"{name} on {t.device}, expected {dev}")
+    if kv_len.dtype != torch.int32 or kv_len.numel() != B or not kv_len.is_contiguous():
+        raise RuntimeError(f"kv_len must hold B = {B} contiguous int32 values")
+
+
+def attn_decode(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, strides, kv_len: torch.Tensor,
+                capacity: int, B: int, N: int, n_head: int, n_kv_head: int, D: int, workspace: torch.Tensor,
+                scale: float | None = None, out: torch.Tensor | None = None, kv_offset: int = 0) -> torch.Tensor:
+    """Causal attention of the N new tokens of B sequences over their KV caches (gq_attn_decode):
+    q fp16 (B*N, n_head*D) -> fp16 (B*N, n_head*D).  Kc / Vc: the cache tensors (any dtype; the rows
+    start kv_offset bytes in), strides = (tok, head, seq) in bytes, kv_len int32 (B) on the device --
+    the lengths including the new tokens.  scale: 1/sqrt(D) when None.  No host sync, no fallback."""
+    _require_device(q, "q")
+    dev = q.device
+    ldq = _kv_rows(q, "q", B * N, n_head * D, dev)
+    _kv_caches(Kc, Vc, kv_len, B, dev)
+    if out is None:
+        out = torch.empty((B * N, n_head * D), dtype=torch.float16, device=dev)
+    ldo = _kv_rows(out, "out", B * N, n_head * D, dev)
+    _check_workspace(workspace, 0, dev)
+    tok, head, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_attn_decode(KV_KINDS[kind], q.data_ptr(), ldq, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset,
+                                    tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
+                                    float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D,
+                                    workspace.data_ptr(), workspace.numel(), _stream(dev)))
+    return out
+
+
+def kv_append(kind: str, k: torch.Tensor, v: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, strides,
+              kv_len: torch.Tensor, capacity: int, B: int, N: int, n_kv_head: int, D: int, kv_offset: int = 0):
+    """The N new tokens' k and v rows, fp16 (B*N, n_kv_head*D), into the caches at positions
+    kv_len[b] - N .. kv_len[b] - 1 (gq_kv_append): a copy, or Q8_0 blocks with the weight producer's
+    bytes.  Arguments as attn_decode's."""
+    _require_device(k, "k")
+    dev = k.device
+    ldn = _kv_rows(k, "k", B * N, n_kv_head * D, dev)
+    if _kv_rows(v, "v", B * N, n_kv_head * D, dev) != ldn:
+        raise RuntimeError("k and v must have the same row stride")
+    _kv_caches(Kc, Vc, kv_len, B, dev)
+    tok, head, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_kv_append(KV_KINDS[kind], k.data_ptr(), v.data_ptr(), ldn, Kc.data_ptr() + kv_offset,
+                                  Vc.data_ptr() + kv_offset, tok, head, seq, kv_len.data_ptr(), capacity, B, N, n_kv_head, D,
+                                  _stream(dev)))
 
 
 def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N: int, K: int,

@@ -29,6 +29,8 @@
  *   gq_moe_route                        the router product and that selection, for decode
  *   gq_rmsnorm                          residual add + RMSNorm of the hidden state, one launch
  *   gq_rmsnorm_prepare                  the same, written as gq_act_prepare's q8_1 activations
+ *   gq_attn_decode                      decode attention over an fp16 or Q8_0 KV cache, grouped query heads
+ *   gq_kv_append                        the new tokens' k and v rows into that cache, on the device
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -538,6 +540,59 @@ int gq_rmsnorm(const void *X, const void *R, void *H, const float *w, float eps,
 int gq_rmsnorm_prepare(const void *X, const void *R, void *H, const float *w, float eps, void *Y, int64_t N, int64_t K,
                        int64_t ldx, int64_t ldr, int64_t ldh, int64_t ldy, void *workspace, size_t workspace_bytes,
                        void *stream);
+
+/*
+ * Decode attention: causal softmax attention of the N new query tokens of each of B sequences against
+ * that sequence's KV cache, with grouped query heads.  Two launches (the attention on a fixed grid,
+ * then a combine of its fp32 partials); the cached lengths are read from device memory, so a captured
+ * graph stays valid as the cache grows.
+ *   kv     : GQ_KV_F16 (a cache row is D fp16 values) or GQ_KV_Q8_0 (D/32 Q8_0 blocks of 34 bytes:
+ *            fp16 d, then 32 int8; value = float(d) * code).
+ *   Q      : fp16 (B*N, n_head*D), row b*N + i at element (b*N + i)*ldq; RoPE already applied.
+ *   Kc, Vc : the caches.  The row of (sequence b, kv head h, position t) starts at byte
+ *            b*seq_stride + h*head_stride + t*tok_stride of each (the same strides for both), which
+ *            covers a token-major cache (llama.cpp's) and a head-major one.  2-byte alignment.
+ *   kv_len : B int32 values in device memory: sequence b's cached tokens INCLUDING the N new ones.
+ *   capacity : the tokens each sequence's cache can hold.
+ *   O      : fp16 (B*N, n_head*D), rows ldo apart.  Only a row's n_head*D elements are written.
+ *   o = softmax(scale * q k^T) v over positions 0 .. kv_len[b] - N + i for query token i; query head j
+ *   reads kv head j / (n_head / n_kv_head).  Scores, softmax and the sums are fp32 (the probabilities
+ *   enter the second product as fp16; for Q8_0 the value block's scale is folded into them, so that
+ *   no cache value is rounded); o is rounded to fp16 once.  Every |o - exact| <= 2^-9 * max|v| over
+ *   the attended positions.  Positions at or beyond kv_len[b] are never used, whatever bytes they
+ *   hold.  kv_len[b] < N or kv_len[b] > capacity is the caller's error: the length is clamped to
+ *   [0, capacity], nothing outside the cache is read, and a query left without a position gives zeros.
+ *   A sequence's output does not depend on B or on the other sequences.
+ * Shapes: D 64 or 128, n_head % n_kv_head == 0, N * n_head / n_kv_head <= 32, strides multiples of 2
+ * with tok_stride >= a row's bytes, N <= capacity, capacity * tok_stride < 1 GiB, B * n_kv_head <=
+ * 2^20; anything else (and an unknown kv): GQ_EUNSUPPORTED.  Null pointers, negative sizes,
+ * ldq or ldo < n_head*D and a workspace that is null, not 16-byte aligned or below
+ * gq_attn_decode_workspace_size(B, N, n_head, n_kv_head, D) (0 for an unsupported shape): GQ_EINVAL.
+ * B, N or n_head == 0: a no-op.  Every check precedes the launches.  Asynchronous, no host sync, no
+ * allocation, graph-capturable.  Detected by its symbol; gq_version() did not change with it.
+ */
+typedef enum { GQ_KV_F16 = 0, GQ_KV_Q8_0 = 1 } gq_kv_type;
+size_t gq_attn_decode_workspace_size(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D);
+int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                   int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                   float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *workspace,
+                   size_t workspace_bytes, void *stream);
+/* The plan of that call: the keys per tile and the workgroups W per (sequence, kv head); workgroup w
+ * takes tiles [T*w/W, T*(w+1)/W) of the T = ceil(kv_len / tile).  W follows the device's compute
+ * units, B and n_kv_head -- never a length -- or the GQ_ATTN_W tuning.  GQ_EUNSUPPORTED: no such shape. */
+int gq_debug_attn_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *tile, int *W);
+
+/*
+ * The N new tokens' k and v rows -- Knew, Vnew: fp16 (B*N, n_kv_head*D), rows ldn apart -- into the
+ * caches (gq_attn_decode's kv, strides, kv_len and capacity) at positions kv_len[b] - N .. kv_len[b] - 1:
+ * a copy for GQ_KV_F16; for GQ_KV_Q8_0 the blocks gq_quantize_weights(GQ_Q8_0, ...) makes of the same
+ * 32 values, byte for byte.  Nothing outside those rows is written; a position outside [0, capacity)
+ * (the caller's error) is skipped.  Checks as gq_attn_decode's with one query head per kv head
+ * (N <= 32; ldn < n_kv_head*D: GQ_EINVAL).  One launch, graph-capturable.  Detected by its symbol.
+ */
+int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
+                 int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B, int64_t N,
+                 int64_t n_kv_head, int64_t D, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE
