@@ -35,7 +35,9 @@ struct Tuning {
     int kstream = -1;                         // GQ_KSTREAM: K-chunked streaming MMQ -1 auto / 0 off / 1 wherever it applies
     int cus = 0;                              // GQ_CUS: compute units to plan for (0: the device's count)
     int attn_w = 0;                           // GQ_ATTN_W: decode attention's workgroups per (sequence, kv head) (0: auto)
-    int ablate = 0;                           // GQ_ABLATE (GQ_ABLATION diagnostic builds only)
+    int attn_trv = 1;                         // GQ_ATTN_TRV: fp16 prefill attention's V^T fragments 1 by the transposing LDS
+                                              // read / 0 by decode's element-wise gather (the measured alternative)
+    int ablate = 0;                          // GQ_ABLATE (GQ_ABLATION diagnostic builds only)
 };
 const Tuning &tuning();
 // key = the environment variable's name ("GQ_GEMM_SPLITS", ...); value validated (an override
@@ -117,6 +119,21 @@ struct AttnCall {
 };
 AttnPlan plan_attn(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D);
 hipError_t launch_attn_decode(int kv, const AttnCall &c, const AttnPlan &p, hipStream_t s);
+// Prefill attention over the same caches (attn_prefill.hip; gq_attn_prefill): B * n_kv_head * nblk
+// workgroups, each a block of `rows` consecutive query rows of one (sequence, kv head) walking the
+// keys in tiles of kPrefillTile through a workgroup-wide LDS ring of kPrefillSlots slots; no split
+// along the keys, no workspace.  rows is 128 where that still gives every compute unit a workgroup,
+// 64 otherwise.  Neither constant was measured against another value: two slots are the least that
+// keep a tile in flight under the current one, and 64 keys x 2 slots fill 64 KiB at fp16, D = 128.
+constexpr int kPrefillTile = 64;  // keys per ring slot (two 32-key steps of the second product)
+constexpr int kPrefillSlots = 2;  // LDS ring slots per workgroup (K tile + V tile each)
+struct PrefillPlan {
+    bool ok = false;           // D in {64, 128}, n_head % n_kv_head == 0, the grid below 2^31
+    int rows = 0, nblk = 0;    // query rows per workgroup, row blocks per (sequence, kv head)
+    int64_t grid = 0;
+};
+PrefillPlan plan_attn_prefill(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D);
+hipError_t launch_attn_prefill(int kv, const AttnCall &c, const PrefillPlan &p, hipStream_t s); // (c.workspace unused)
 // The N new tokens' k and v rows (fp16, rows ldn apart) into the caches at kv_len[b] - N .. kv_len[b] - 1
 hipError_t launch_kv_append(int kv, const void *Kn, const void *Vn, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
                             int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B,

@@ -75,7 +75,8 @@ bool parse_key(Tuning &t, const char *key, long long v)
     } else if (k == "GQ_ATTN_W") {
         if (v < 0 || v > kAttnMaxW) return false;
         t.attn_w = (int)v;
-    } else if (k == "GQ_KSTREAM") {
+    } else if (k == "GQ_ATTN_TRV") t.attn_trv = v != 0;
+    else if (k == "GQ_KSTREAM") {
         if (!in({-1, 0, 1})) return false;
         t.kstream = (int)v;
     } else if (k == "GQ_ABLATE") t.ablate = (int)v;
@@ -90,7 +91,7 @@ void tuning_from_env(Tuning &t)
                                        "GQ_DECODE_Q6_IMG", "GQ_DECODE_F8_ITC", "GQ_GEMM_AQ", "GQ_GEMM_RG", "GQ_GEMM_SPLITS",
                                        "GQ_GEMM_PARTIAL", "GQ_SKINNY", "GQ_SKINNY_RG", "GQ_RGEMM", "GQ_SGEMM",
                                        "GQ_SGEMM_SPLITS", "GQ_SGEMM_STREAMK", "GQ_RGEMM_ILC", "GQ_RGEMM_ESTORE", "GQ_SGEMM_FULL", "GQ_CUS",
-                                       "GQ_KSTREAM", "GQ_ATTN_W", "GQ_ABLATE"};
+                                       "GQ_KSTREAM", "GQ_ATTN_W", "GQ_ATTN_TRV", "GQ_ABLATE"};
     for (const char *k : keys) {
         const char *e = getenv(k); // the only getenv of the library: once per process
         if (!e || !*e) continue;
@@ -1473,11 +1474,12 @@ int gq_rmsnorm_prepare(const void *X, const void *R, void *H, const float *w, fl
     return hip_rc(gq::launch_rmsnorm(a, N, (hipStream_t)stream), "rmsnorm");
 }
 
-// ---- decode attention (attn_decode.hip) ----
-// The checks gq_attn_decode and gq_kv_append share, in this order: the cache kind, the sizes, then
-// (not empty) the shape and the cache geometry.  empty: nothing to do.
+// ---- attention (attn_decode.hip, attn_prefill.hip) ----
+// The checks gq_attn_decode, gq_attn_prefill and gq_kv_append share, in this order: the cache kind,
+// the sizes, then (not empty) the shape and the cache geometry.  decode: the call is held to decode's
+// 32 query rows per kv head and its plan.  empty: nothing to do.
 static int check_kv_cache(gq_kv_type kv, int64_t tok_stride, int64_t head_stride, int64_t seq_stride, int64_t capacity,
-                          int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, bool &empty)
+                          int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, bool decode, bool &empty)
 {
     empty = false;
     if (kv != GQ_KV_F16 && kv != GQ_KV_Q8_0) return fail(GQ_EUNSUPPORTED, "unknown kv cache type %d", (int)kv);
@@ -1489,10 +1491,11 @@ static int check_kv_cache(gq_kv_type kv, int64_t tok_stride, int64_t head_stride
     if (D != 64 && D != 128) return fail(GQ_EUNSUPPORTED, "D=%lld is neither 64 nor 128", (long long)D);
     if (n_kv_head == 0 || n_head % n_kv_head != 0)
         return fail(GQ_EUNSUPPORTED, "n_head=%lld is not a multiple of n_kv_head=%lld", (long long)n_head, (long long)n_kv_head);
-    if (N * (n_head / n_kv_head) > 32)
+    if (decode && N * (n_head / n_kv_head) > 32)
         return fail(GQ_EUNSUPPORTED, "R = N * n_head / n_kv_head = %lld query rows per kv head, at most 32",
                     (long long)(N * (n_head / n_kv_head)));
-    if (!gq::plan_attn(B, N, n_head, n_kv_head, D).ok) return fail(GQ_EUNSUPPORTED, "B * n_kv_head = %lld is above 2^20", (long long)(B * n_kv_head));
+    if (decode ? !gq::plan_attn(B, N, n_head, n_kv_head, D).ok : B > (1 << 20) / n_kv_head)
+        return fail(GQ_EUNSUPPORTED, "B * n_kv_head = %lld is above 2^20", (long long)(B * n_kv_head));
     const int64_t rb = kv == GQ_KV_Q8_0 ? 34 * (D / 32) : 2 * D;
     if (((tok_stride | head_stride | seq_stride) & 1) != 0) return fail(GQ_EUNSUPPORTED, "the cache strides must be multiples of 2");
     if (tok_stride < rb || head_stride < 0 || seq_stride < 0)
@@ -1532,7 +1535,7 @@ int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, co
         if (ldq < n_head * D) return fail(GQ_EINVAL, "ldq=%lld < n_head*D=%lld", (long long)ldq, (long long)(n_head * D));
         if (ldo < n_head * D) return fail(GQ_EINVAL, "ldo=%lld < n_head*D=%lld", (long long)ldo, (long long)(n_head * D));
     }
-    const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D, empty);
+    const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D, true, empty);
     if (rc != GQ_OK || empty) return rc;
     const gq::AttnPlan p = gq::plan_attn(B, N, n_head, n_kv_head, D);
     if (!workspace || workspace_bytes < p.workspace_bytes) return fail_workspace(workspace, workspace_bytes, p.workspace_bytes);
@@ -1540,6 +1543,38 @@ int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, co
     const gq::AttnCall c{Q, Kc, Vc, kv_len, O, workspace, ldq, ldo, tok_stride, head_stride, seq_stride, capacity,
                          B, N, n_head, n_kv_head, D, scale};
     return hip_rc(gq::launch_attn_decode(kv == GQ_KV_Q8_0, c, p, (hipStream_t)stream), "attn_decode");
+}
+
+int gq_debug_attn_prefill_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *rows, int *tile)
+{
+    g_err.clear();
+    const gq::PrefillPlan p = gq::plan_attn_prefill(B, N, n_head, n_kv_head, D);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "not a prefill-attention shape");
+    if (rows) *rows = p.rows;
+    if (tile) *tile = gq::kPrefillTile;
+    return GQ_OK;
+}
+
+int gq_attn_prefill(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                    int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                    float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    // (the sizes first: a negative one has no row length to hold ldq against)
+    if (B >= 0 && N >= 0 && n_head > 0 && D >= 0 && B * N > 0) {
+        if (!Q || !Kc || !Vc || !kv_len || !O)
+            return fail(GQ_EINVAL, "null pointer (Q=%p Kc=%p Vc=%p kv_len=%p O=%p)", Q, Kc, Vc, (const void *)kv_len, O);
+        if (ldq < n_head * D) return fail(GQ_EINVAL, "ldq=%lld < n_head*D=%lld", (long long)ldq, (long long)(n_head * D));
+        if (ldo < n_head * D) return fail(GQ_EINVAL, "ldo=%lld < n_head*D=%lld", (long long)ldo, (long long)(n_head * D));
+    }
+    const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D, false, empty);
+    if (rc != GQ_OK || empty) return rc;
+    const gq::PrefillPlan p = gq::plan_attn_prefill(B, N, n_head, n_kv_head, D);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "B * n_kv_head * ceil(N * n_head / n_kv_head / %d) workgroups are 2^31 or more", p.rows);
+    const gq::AttnCall c{Q, Kc, Vc, kv_len, O, nullptr, ldq, ldo, tok_stride, head_stride, seq_stride, capacity,
+                         B, N, n_head, n_kv_head, D, scale};
+    return hip_rc(gq::launch_attn_prefill(kv == GQ_KV_Q8_0, c, p, (hipStream_t)stream), "attn_prefill");
 }
 
 int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
@@ -1553,9 +1588,10 @@ int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn,
             return fail(GQ_EINVAL, "null pointer (Knew=%p Vnew=%p Kc=%p Vc=%p kv_len=%p)", Knew, Vnew, Kc, Vc, (const void *)kv_len);
         if (ldn < n_kv_head * D) return fail(GQ_EINVAL, "ldn=%lld < n_kv_head*D=%lld", (long long)ldn, (long long)(n_kv_head * D));
     }
-    // (one query head per kv head: the shape limits that are the cache's own, and N <= 32)
-    const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_kv_head, n_kv_head, D, empty);
+    // (one query head per kv head: the shape limits that are the cache's own; any N the capacity holds)
+    const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_kv_head, n_kv_head, D, false, empty);
     if (rc != GQ_OK || empty) return rc;
+    if (B * n_kv_head * N >= ((int64_t)1 << 32)) return fail(GQ_EUNSUPPORTED, "B * n_kv_head * N = %lld rows is 2^32 or more", (long long)(B * n_kv_head * N));
     return hip_rc(gq::launch_kv_append(kv == GQ_KV_Q8_0, Knew, Vnew, ldn, Kc, Vc, tok_stride, head_stride, seq_stride, kv_len,
                                        capacity, B, N, n_kv_head, D, (hipStream_t)stream), "kv_append");
 }

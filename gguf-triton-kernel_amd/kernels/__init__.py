@@ -11,11 +11,11 @@
 Each computes C = (A @ B^T)^T with A a packed GGUF weight tensor (int8, flat) and B fp16
 activations (N, K), returning fp16 (N, M) -- the reference's signature and layout.
 
-Beyond the reference, decode attention over an fp16 or Q8_0 KV cache (kernels/attention.py):
+Beyond the reference, decode and prefill attention over an fp16 or Q8_0 KV cache (kernels/attention.py):
 
-    from kernels import KVCache, attn_decode, kv_append
+    from kernels import KVCache, attn_decode, attn_prefill, kv_append
 """
-_LAZY = {"KVCache": "attention", "attn_decode": "_lib", "kv_append": "_lib"}
+_LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib"}
 __all__ = list(_LAZY)
 
 

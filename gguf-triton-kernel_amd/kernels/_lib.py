@@ -105,6 +105,9 @@ SIGNATURES = {
     "gq_attn_decode": ([_I, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64,
                         _I64, _P, _SZ, _P], _I),
     "gq_debug_attn_plan": ([_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
+    "gq_attn_prefill": ([_I, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64,
+                         _I64, _P], _I),
+    "gq_debug_attn_prefill_plan": ([_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
     "gq_kv_append": ([_I, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
@@ -1032,6 +1035,33 @@ def attn_decode(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, 
                                     tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
                                     float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D,
                                     workspace.data_ptr(), workspace.numel(), _stream(dev)))
+    return out
+
+
+def attn_prefill_plan(B: int, N: int, n_head: int, n_kv_head: int, D: int):
+    """(query rows per workgroup, keys per LDS tile) of an attn_prefill call (gq_debug_attn_prefill_plan)."""
+    rows, tile = ctypes.c_int(), ctypes.c_int()
+    _check(lib().gq_debug_attn_prefill_plan(B, N, n_head, n_kv_head, D, ctypes.byref(rows), ctypes.byref(tile)))
+    return rows.value, tile.value
+
+
+def attn_prefill(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, strides, kv_len: torch.Tensor,
+                 capacity: int, B: int, N: int, n_head: int, n_kv_head: int, D: int, scale: float | None = None,
+                 out: torch.Tensor | None = None, kv_offset: int = 0) -> torch.Tensor:
+    """attn_decode for a prompt or a chunk of one (gq_attn_prefill): any N <= capacity, one launch, no
+    workspace.  Arguments as attn_decode's.  No host sync, no fallback."""
+    _require_device(q, "q")
+    dev = q.device
+    ldq = _kv_rows(q, "q", B * N, n_head * D, dev)
+    _kv_caches(Kc, Vc, kv_len, B, dev)
+    if out is None:
+        out = torch.empty((B * N, n_head * D), dtype=torch.float16, device=dev)
+    ldo = _kv_rows(out, "out", B * N, n_head * D, dev)
+    tok, head, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_attn_prefill(KV_KINDS[kind], q.data_ptr(), ldq, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset,
+                                     tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
+                                     float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D, _stream(dev)))
     return out
 
 

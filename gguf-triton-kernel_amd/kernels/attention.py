@@ -1,4 +1,4 @@
-"""Decode attention over a KV cache that lives on the device: the step between a block's q/k/v
+"""Attention over a KV cache that lives on the device: the step between a block's q/k/v
 projections and its attn_output (kernels/layer_mix.py LayerMix.forward takes the result as `attn`).
 
     cache = KVCache(B, capacity, n_kv_head, D, kind="q8_0")     # or "f16"
@@ -6,8 +6,9 @@ projections and its attn_output (kernels/layer_mix.py LayerMix.forward takes the
     a = cache.attend(q)               # (B*N, n_head*D) fp16
 
 append advances the lengths on the device and writes the rows there (gq_kv_append; Q8_0 blocks with
-the weight producer's bytes); attend is gq_attn_decode.  Neither syncs the host or allocates, the
-lengths are read by the kernels, so one captured graph of a decode step serves every length up to
+the weight producer's bytes); attend is gq_attn_decode up to 32 query rows per kv head and
+gq_attn_prefill (a prompt, or a chunk of one after a prefix) beyond.  Neither syncs the host or
+allocates, the lengths are read by the kernels, so one captured graph of a step serves every length up to
 the capacity.  No fallback: a shape the library refuses raises.  No reference counterpart.
 """
 from __future__ import annotations
@@ -61,6 +62,9 @@ class KVCache:
         if q.shape[1] % self.D:
             raise ValueError(f"q has {q.shape[1]} columns, not a multiple of D = {self.D}")
         n_head = q.shape[1] // self.D
+        if N * (n_head // self.n_kv_head) > 32:  # beyond decode's rows per kv head: the prefill kernel, no workspace
+            return _lib.attn_prefill(self.kind, q, self.k, self.v, self.strides, self.kv_len, self.capacity, self.B, N, n_head,
+                                     self.n_kv_head, self.D, scale, out)
         ws = self._ws.get((N, n_head))
         if ws is None:
             need = _lib.attn_workspace_size(self.B, N, n_head, self.n_kv_head, self.D)

@@ -30,6 +30,7 @@
  *   gq_rmsnorm                          residual add + RMSNorm of the hidden state, one launch
  *   gq_rmsnorm_prepare                  the same, written as gq_act_prepare's q8_1 activations
  *   gq_attn_decode                      decode attention over an fp16 or Q8_0 KV cache, grouped query heads
+ *   gq_attn_prefill                     the same for a prompt or a chunk of one: any number of new tokens, one launch
  *   gq_kv_append                        the new tokens' k and v rows into that cache, on the device
  */
 #ifndef GGUF_MMQ_H
@@ -583,12 +584,36 @@ int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, co
 int gq_debug_attn_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *tile, int *W);
 
 /*
+ * Prefill attention: gq_attn_decode's operation -- the same arguments, cache layout, kv_len semantics,
+ * arithmetic and error bound, |o - exact| <= 2^-9 * max|v| -- for any number of new tokens, built for
+ * hundreds to thousands of them.  Query token i of sequence b attends positions 0 .. kv_len[b] - N + i,
+ * so a chunk appended after an existing prefix works as a fresh prompt does.  ONE launch: a workgroup
+ * owns 64 or 128 consecutive query rows of one (sequence, kv head) and walks that sequence's keys up to
+ * its last row's limit; nothing is split along the keys, so there is no workspace and no combine, and a
+ * call with few rows (B * n_kv_head * N * n_head / n_kv_head / 64 below the compute units) leaves part
+ * of the chip idle -- gq_attn_decode is the entry for <= 32 rows per kv head.  The grid depends on B, N
+ * and the head counts only, the lengths are read on the device: a captured graph serves every prefix.
+ * Shapes: D 64 or 128, n_head % n_kv_head == 0, strides multiples of 2 with tok_stride >= a row's bytes,
+ * 1 <= N <= capacity, capacity * tok_stride < 1 GiB, B * n_kv_head <= 2^20; anything else (and an unknown
+ * kv): GQ_EUNSUPPORTED.  Null pointers, negative sizes, ldq or ldo < n_head*D: GQ_EINVAL.  The checks
+ * come in gq_attn_decode's order with its messages.  B, N or n_head == 0: a no-op.  Every check precedes
+ * the launch.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol;
+ * gq_version() did not change with it.
+ */
+int gq_attn_prefill(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                    int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                    float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *stream);
+/* The plan of that call: the query rows per workgroup (64 or 128: 128 where that still gives every
+ * compute unit a workgroup) and the keys per LDS tile.  GQ_EUNSUPPORTED: no such shape. */
+int gq_debug_attn_prefill_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *rows, int *tile);
+
+/*
  * The N new tokens' k and v rows -- Knew, Vnew: fp16 (B*N, n_kv_head*D), rows ldn apart -- into the
  * caches (gq_attn_decode's kv, strides, kv_len and capacity) at positions kv_len[b] - N .. kv_len[b] - 1:
  * a copy for GQ_KV_F16; for GQ_KV_Q8_0 the blocks gq_quantize_weights(GQ_Q8_0, ...) makes of the same
  * 32 values, byte for byte.  Nothing outside those rows is written; a position outside [0, capacity)
- * (the caller's error) is skipped.  Checks as gq_attn_decode's with one query head per kv head
- * (N <= 32; ldn < n_kv_head*D: GQ_EINVAL).  One launch, graph-capturable.  Detected by its symbol.
+ * (the caller's error) is skipped.  Checks as gq_attn_prefill's with one query head per kv head
+ * (any N <= capacity; ldn < n_kv_head*D: GQ_EINVAL).  One launch, graph-capturable.  Detected by its symbol.
  */
 int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
                  int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B, int64_t N,

@@ -14,6 +14,13 @@ rotate.  Every replay is timed alone by device events (bench.timed_rotation), th
 measured interleaved in one process, `repeats` passes; a cell is the median over the passes, their
 spread (max - min), and the live cache bytes (K and V rows below kv_len) per second against the HBM
 figure bench.py uses.  Needs the GPU.
+
+    python tools/attn_bench.py --prefill [--steps 10] [--out profiles/attn_prefill_bench.json]
+
+Prefill attention (kernels._lib.attn_prefill: gq_attn_prefill) by the same method: the same heads, B = 1,
+N in {128, 512, 2048, 8192} new tokens without a prefix and 512 after a prefix of 4096, and one B = 4
+cell; a cell is the median time, its spread, the causal TFLOP/s (4 D flops per attended (row, key) pair)
+and that as a share of bench.py's MFMA_F16_PEAK_TF (PrefillCase).
 """
 import argparse
 import json
@@ -73,6 +80,99 @@ class Case:
         return d
 
 
+class PrefillCase:
+    """N new tokens after a prefix of P per sequence: kernels._lib.attn_prefill over an fp16 and a Q8_0
+    cache exactly P + N long, beside torch SDPA on the same fp16 cache (is_causal=True without a prefix,
+    an explicit (N, P + N) boolean mask with one; grouped heads by enable_gqa=True, i.e. K and V are
+    not repeated by the caller).  The caches rotate as in Case; q does not."""
+
+    def __init__(self, nh, kvh, D, N, B, P, dev, steps):
+        import kernels._lib as kl
+        L = P + N
+        self.kl, self.dev, self.dims = kl, dev, (nh, kvh, D, N, B, L)
+        ncopies, self.plans = bench.rotation_plan(2 * B * L * kvh * kl.kv_row_bytes("q8_0", D), steps)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        rnd = lambda *s: torch.randn(s, device=dev, generator=gen).to(torch.float16)  # noqa: E731
+        # (every copy holds the same values: a copy per step is about where the bytes come from)
+        self.f16 = [tuple(t.expand(ncopies, B, L, kvh, D).contiguous().unbind(0)) for t in (rnd(B, L, kvh, D), rnd(B, L, kvh, D))]
+        self.q8 = [tuple(bench.device_random_blocks("q8_0", B * L * kvh, D, dev, s).expand(ncopies, -1).contiguous().unbind(0))
+                   for s in (0, 1)]
+        self.q = rnd(B * N, nh * D)
+        self.kv_len = torch.full((B,), L, dtype=torch.int32, device=dev)
+        self.out = torch.empty(B * N, nh * D, dtype=torch.float16, device=dev)
+        self.mask = None if P == 0 else torch.ones(N, L, dtype=torch.bool, device=dev).tril(P)
+        self.flops = 4.0 * D * B * nh * (N * P + N * (N + 1) // 2)  # 4 D per attended (row, key) pair
+
+    def step(self, form, c, i):
+        nh, kvh, D, N, B, L = self.dims
+        if form == "torch":
+            k, v = (t[c].permute(0, 2, 1, 3) for t in self.f16)
+            q = self.q.view(B, N, nh, D).permute(0, 2, 1, 3)
+            o = torch.nn.functional.scaled_dot_product_attention(q, k, v, attn_mask=self.mask, is_causal=self.mask is None,
+                                                                 enable_gqa=nh != kvh)
+            return o.permute(0, 2, 1, 3).reshape(B * N, nh * D)
+        kind = "q8_0" if form == "q8_0" else "f16"
+        k, v = (t[c] for t in (self.q8 if form == "q8_0" else self.f16))
+        rb = self.kl.kv_row_bytes(kind, D)
+        self.kl.set_tuning("GQ_ATTN_TRV", int(form != "f16_gather"))  # (read at the launch, so at the capture)
+        o = self.kl.attn_prefill(kind, self.q, k, v, (kvh * rb, rb, L * kvh * rb), self.kv_len, L, B, N, nh, kvh, D,
+                                 out=self.out)
+        self.kl.reset_tuning()
+        return o
+
+    check = Case.check
+
+
+# "f16_gather": the fp16 form with V^T gathered element by element (GQ_ATTN_TRV=0), the alternative
+# the transposing LDS read was measured against
+PREFILL_FORMS = ("torch", "f16", "f16_gather", "q8_0")
+
+
+def measure_prefill(case, steps, repeats, dev):
+    diff = case.check()
+    gs = {f: graphs(case, f) for f in PREFILL_FORMS}
+    ts = {f: [] for f in PREFILL_FORMS}
+    for _ in range(repeats):  # interleaved: one pass over the forms per repeat
+        for f in PREFILL_FORMS:
+            ts[f].append(bench.timed_rotation(gs[f], dev) / steps * 1e6)
+    row = {"f16_vs_torch_max_rel_diff": round(diff, 5), "causal_gflop": round(case.flops / 1e9, 2)}
+    for f in PREFILL_FORMS:
+        us = float(np.median(ts[f]))
+        tf = case.flops / us / 1e6
+        row[f] = {"us": round(us, 1), "spread_us": round(max(ts[f]) - min(ts[f]), 1), "causal_TFLOPs": round(tf, 1),
+                  "mfma_frac": round(tf / bench.MFMA_F16_PEAK_TF, 4)}
+    return row
+
+
+# (heads, B, N, prefix)
+PREFILL_CELLS = [(h, 1, N, 0) for h in HEADS for N in (128, 512, 2048, 8192)] + [(h, 1, 512, 4096) for h in HEADS] + \
+    [("llama3_8b", 4, 2048, 0)]
+
+
+def main_prefill(a, dev):
+    rows = []
+    for name, B, N, P in PREFILL_CELLS:
+        if P + N > a.max_len:
+            continue
+        nh, kvh, D = HEADS[name]
+        case = PrefillCase(nh, kvh, D, N, B, P, dev, a.steps)
+        rows_wg, tile = case.kl.attn_prefill_plan(B, N, nh, kvh, D)
+        grid = B * kvh * -(-N * (nh // kvh) // rows_wg)
+        row = {"heads": name, "B": B, "N": N, "prefix": P, "rows_per_workgroup": rows_wg, "workgroups": grid,
+               **measure_prefill(case, a.steps, a.repeats, dev)}
+        row["f16_slower_than_torch"] = bool(row["f16"]["us"] - row["torch"]["us"] >
+                                            max(row["f16"]["spread_us"], row["torch"]["spread_us"]))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del case
+        torch.cuda.empty_cache()
+        if a.out:  # (after every cell: a run cut short keeps what it measured)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump({"steps": a.steps, "repeats": a.repeats, "mfma_f16_peak_TF": bench.MFMA_F16_PEAK_TF,
+                           "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count, "rows": rows}, f, indent=1)
+
+
 def graphs(case, form):
     grs = []
     for plan in case.plans:
@@ -106,10 +206,13 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--max-len", type=int, default=32768)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--prefill", action="store_true", help="prefill attention (attn_prefill) instead of decode")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("attn_bench.py needs a ROCm device: there is no CPU timing path")
     dev = torch.device("cuda:0")
+    if a.prefill:
+        return main_prefill(a, dev)
     rows = []
     for name, (nh, kvh, D) in HEADS.items():
         for L in (512, 4096, 32768):
