@@ -138,6 +138,18 @@ hipError_t launch_attn_prefill(int kv, const AttnCall &c, const PrefillPlan &p, 
 hipError_t launch_kv_append(int kv, const void *Kn, const void *Vn, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
                             int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B,
                             int64_t N, int64_t n_kv_head, int64_t D, hipStream_t s);
+// Per-head norm (optional) + RoPE of the N new tokens' q and k rows, q to Qout, k and v into the caches
+// at those positions (rope.hip; gq_rope_append): one launch on a grid fixed by B * N, the head counts
+// and the compute units.  mode: gq_rope_mode.
+struct RopeCall {
+    const void *Q, *Knew, *Vnew;
+    void *Qout, *Kc, *Vc;
+    const int32_t *kv_len;
+    const float *inv_freq, *q_norm_w, *k_norm_w;
+    int64_t ldq, ldk, ldv, ldqo, tok_stride, head_stride, seq_stride, capacity, n_rot, B, N, n_head, n_kv_head, D;
+    float mscale, eps;
+};
+hipError_t launch_rope_append(int kv, int mode, const RopeCall &c, hipStream_t s);
 
 // Decode-shaped GEMV (mmq_gemv.hip): C[t][m] for t < N_tok <= 8 from SOA activations.
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,

@@ -1596,6 +1596,36 @@ int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn,
                                        capacity, B, N, n_kv_head, D, (hipStream_t)stream), "kv_append");
 }
 
+int gq_rope_append(gq_kv_type kv, gq_rope_mode mode, const void *Q, int64_t ldq, const void *Knew, int64_t ldk,
+                   const void *Vnew, int64_t ldv, void *Qout, int64_t ldqo, void *Kc, void *Vc, int64_t tok_stride,
+                   int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, const float *inv_freq,
+                   int64_t n_rot, float mscale, const float *q_norm_w, const float *k_norm_w, float eps, int64_t B, int64_t N,
+                   int64_t n_head, int64_t n_kv_head, int64_t D, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    if (B >= 0 && N >= 0 && n_head > 0 && n_kv_head >= 0 && D >= 0 && B * N > 0) {
+        if (!Q || !Knew || !Vnew || !Qout || !Kc || !Vc || !kv_len || !inv_freq)
+            return fail(GQ_EINVAL, "null pointer (Q=%p Knew=%p Vnew=%p Qout=%p Kc=%p Vc=%p kv_len=%p inv_freq=%p)", Q, Knew, Vnew,
+                        Qout, Kc, Vc, (const void *)kv_len, (const void *)inv_freq);
+        if (ldq < n_head * D) return fail(GQ_EINVAL, "ldq=%lld < n_head*D=%lld", (long long)ldq, (long long)(n_head * D));
+        if (ldqo < n_head * D) return fail(GQ_EINVAL, "ldqo=%lld < n_head*D=%lld", (long long)ldqo, (long long)(n_head * D));
+        if (ldk < n_kv_head * D) return fail(GQ_EINVAL, "ldk=%lld < n_kv_head*D=%lld", (long long)ldk, (long long)(n_kv_head * D));
+        if (ldv < n_kv_head * D) return fail(GQ_EINVAL, "ldv=%lld < n_kv_head*D=%lld", (long long)ldv, (long long)(n_kv_head * D));
+        if (!q_norm_w != !k_norm_w)
+            return fail(GQ_EINVAL, "one norm weight without the other (q_norm_w=%p k_norm_w=%p)", (const void *)q_norm_w, (const void *)k_norm_w);
+    }
+    const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D, false, empty);
+    if (rc != GQ_OK || empty) return rc;
+    if (mode != GQ_ROPE_NORM && mode != GQ_ROPE_NEOX) return fail(GQ_EUNSUPPORTED, "unknown rope mode %d", (int)mode);
+    if (n_rot < 2 || n_rot > D || (n_rot & 1) != 0)
+        return fail(GQ_EUNSUPPORTED, "n_rot=%lld is not an even count in [2, D=%lld]", (long long)n_rot, (long long)D);
+    if (B * N >= ((int64_t)1 << 31)) return fail(GQ_EUNSUPPORTED, "B * N = %lld tokens is 2^31 or more", (long long)(B * N));
+    const gq::RopeCall c{Q, Knew, Vnew, Qout, Kc, Vc, kv_len, inv_freq, q_norm_w, k_norm_w, ldq, ldk, ldv, ldqo, tok_stride,
+                         head_stride, seq_stride, capacity, n_rot, B, N, n_head, n_kv_head, D, mscale, eps};
+    return hip_rc(gq::launch_rope_append(kv == GQ_KV_Q8_0, mode == GQ_ROPE_NEOX, c, (hipStream_t)stream), "rope_append");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

@@ -448,22 +448,36 @@ GQ_QHD inline void q2k_block(const float *x, uint8_t *blk)
 // ---------------- Q8_0 / Q8_1 (the reference's torch producers, fp16 arithmetic) ----------------
 // d = fp16(amax / 127); q = clamp(rne(fp16(x / d)), +-127).  Q8_0 stores d = 1 for an all-zero
 // block; Q8_1 stores d = 0 there (dividing by 1) and s = fp16(d * fp16(sum q)).
+// The block's two steps, for a producer that holds one block across lanes (rope.hip) as for q8_block:
+// the stored scale of a block whose largest magnitude is amax, and one element's code under div = h2f(d).
+template <bool WITH_SUM>
+GQ_QHD inline uint16_t q8_scale(float amax)
+{
+    uint16_t d = WITH_SUM ? (uint16_t)0 : (uint16_t)0x3c00;
+    if (amax != 0.f) d = f2h(amax / 127.0f);
+    return d;
+}
+
+GQ_QHD inline int8_t q8_code(uint16_t x, float div)
+{
+    float q = std::nearbyint(h2f(f2h(h2f(x) / div)));
+    if (q != q) q = 0.f; // 0/0 when d underflowed to 0 (tiny Q8_0 block): torch's int8 cast gives 0
+    q = std::min(127.f, std::max(-127.f, q));
+    return (int8_t)q;
+}
+
 template <bool WITH_SUM>
 GQ_QHD inline void q8_block(const uint16_t *x, uint8_t *blk)
 {
     float amax = 0.f;
     for (int i = 0; i < 32; ++i) amax = std::max(amax, std::fabs(h2f(x[i])));
-    uint16_t d = WITH_SUM ? (uint16_t)0 : (uint16_t)0x3c00;
-    if (amax != 0.f) d = f2h(amax / 127.0f);
+    const uint16_t d = q8_scale<WITH_SUM>(amax);
     float div = h2f(d);
     if (WITH_SUM && div == 0.f) div = 1.f;
     uint8_t *qs = blk + (WITH_SUM ? 4 : 2);
     int32_t sum = 0;
     for (int i = 0; i < 32; ++i) {
-        float q = std::nearbyint(h2f(f2h(h2f(x[i]) / div)));
-        if (q != q) q = 0.f; // 0/0 when d underflowed to 0 (tiny Q8_0 block): torch's int8 cast gives 0
-        q = std::min(127.f, std::max(-127.f, q));
-        int8_t qi = (int8_t)q;
+        const int8_t qi = q8_code(x[i], div);
         qs[i] = (uint8_t)qi;
         sum += qi;
     }

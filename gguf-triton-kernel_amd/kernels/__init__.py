@@ -14,8 +14,13 @@ activations (N, K), returning fp16 (N, M) -- the reference's signature and layou
 Beyond the reference, decode and prefill attention over an fp16 or Q8_0 KV cache (kernels/attention.py):
 
     from kernels import KVCache, attn_decode, attn_prefill, kv_append
+
+and the rotary embedding (with the per-head q/k norm) fused into the append:
+
+    from kernels import RoPE, rope_append
 """
-_LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib"}
+_LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib", "RoPE": "attention",
+         "rope_append": "_lib"}
 __all__ = list(_LAZY)
 
 

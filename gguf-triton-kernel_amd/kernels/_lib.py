@@ -109,6 +109,8 @@ SIGNATURES = {
                          _I64, _P], _I),
     "gq_debug_attn_prefill_plan": ([_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
     "gq_kv_append": ([_I, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_rope_append": ([_I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64,
+                        ctypes.c_float, _P, _P, ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
@@ -1081,6 +1083,40 @@ def kv_append(kind: str, k: torch.Tensor, v: torch.Tensor, Kc: torch.Tensor, Vc:
         _check(lib().gq_kv_append(KV_KINDS[kind], k.data_ptr(), v.data_ptr(), ldn, Kc.data_ptr() + kv_offset,
                                   Vc.data_ptr() + kv_offset, tok, head, seq, kv_len.data_ptr(), capacity, B, N, n_kv_head, D,
                                   _stream(dev)))
+
+
+ROPE_MODES = {"norm": 0, "neox": 1}  # gq_rope_mode
+
+
+def rope_append(kind: str, mode: str, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor,
+                strides, kv_len: torch.Tensor, capacity: int, inv_freq: torch.Tensor, n_rot: int, B: int, N: int, n_head: int,
+                n_kv_head: int, D: int, mscale: float = 1.0, q_norm: torch.Tensor | None = None,
+                k_norm: torch.Tensor | None = None, eps: float = 1e-6, out: torch.Tensor | None = None,
+                kv_offset: int = 0) -> torch.Tensor:
+    """Per-head norm (q_norm / k_norm: fp32 (D), or neither) + RoPE of the N new tokens' q (B*N, n_head*D)
+    and k (B*N, n_kv_head*D), k and v into the caches at positions kv_len[b] - N .. kv_len[b] - 1
+    (gq_rope_append: one launch, the positions read on the device) -> the rotated q (`out`, which may
+    be q itself).  q, k and v may be column slices of one buffer.  inv_freq: fp32 (n_rot/2) on the
+    device.  The other arguments as kv_append's.  No host sync, no fallback."""
+    _require_device(q, "q")
+    dev = q.device
+    ldq = _kv_rows(q, "q", B * N, n_head * D, dev)
+    ldk = _kv_rows(k, "k", B * N, n_kv_head * D, dev)
+    ldv = _kv_rows(v, "v", B * N, n_kv_head * D, dev)
+    _kv_caches(Kc, Vc, kv_len, B, dev)
+    if out is None:
+        out = torch.empty((B * N, n_head * D), dtype=torch.float16, device=dev)
+    ldqo = _kv_rows(out, "out", B * N, n_head * D, dev)
+    for t, name, n in ((inv_freq, "inv_freq", n_rot // 2), (q_norm, "q_norm", D), (k_norm, "k_norm", D)):
+        if t is not None and (t.device != dev or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous()):
+            raise RuntimeError(f"{name} must hold {n} contiguous float32 values on {dev}")
+    tok, head, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_rope_append(KV_KINDS[kind], ROPE_MODES[mode], q.data_ptr(), ldq, k.data_ptr(), ldk, v.data_ptr(), ldv,
+                                    out.data_ptr(), ldqo, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset, tok, head, seq,
+                                    kv_len.data_ptr(), capacity, inv_freq.data_ptr(), n_rot, float(mscale), _ptr(q_norm),
+                                    _ptr(k_norm), float(eps), B, N, n_head, n_kv_head, D, _stream(dev)))
+    return out
 
 
 def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N: int, K: int,

@@ -5,6 +5,13 @@ projections and its attn_output (kernels/layer_mix.py LayerMix.forward takes the
     cache.append(k, v)                # the N new tokens' rows, RoPE already applied to k
     a = cache.attend(q)               # (B*N, n_head*D) fp16
 
+or, from the projections as they come, with the rotary embedding (and the per-head q/k norm of Qwen3,
+Gemma-3 and OLMo-2) applied on the way -- one launch instead of append, no position tensor:
+
+    rope = RoPE.from_gguf(meta, tensors, layer)                 # the file's rope.* metadata and norm weights
+    q = cache.append_rope(q, k, v, rope)                        # gq_rope_append; q, k, v may be slices of one qkv buffer
+    a = cache.attend(q)
+
 append advances the lengths on the device and writes the rows there (gq_kv_append; Q8_0 blocks with
 the weight producer's bytes); attend is gq_attn_decode up to 32 query rows per kv head and
 gq_attn_prefill (a prompt, or a chunk of one after a prefix) beyond.  Neither syncs the host or
@@ -13,9 +20,88 @@ the capacity.  No fallback: a shape the library refuses raises.  No reference co
 """
 from __future__ import annotations
 
+import math
+
+import numpy as np
 import torch
 
 from . import _lib
+
+# the pairing of a rotation's two elements by architecture (llama.cpp's rope types)
+ROPE_MODE = {a: "norm" for a in ("llama", "llama4", "deepseek", "deepseek2")}
+ROPE_MODE.update({a: "neox" for a in ("qwen2", "qwen2moe", "qwen3", "qwen3moe", "gemma", "gemma2", "gemma3", "phi3", "falcon",
+                                      "stablelm", "olmo2", "gptneox")})
+
+
+def _f32_values(t) -> np.ndarray:
+    """A GGUF f32 / f16 tensor (gguf.file.GGUFTensor) or any array as flat float64."""
+    if hasattr(t, "type_name"):
+        t = np.frombuffer(np.ascontiguousarray(t.data), dtype={"f32": np.float32, "f16": np.float16}[t.type_name])
+    return np.asarray(t, dtype=np.float64).reshape(-1)
+
+
+class RoPE:
+    """What gq_rope_append needs beside the rows: the frequency table inv_freq (float32 (n_rot/2), on
+    the device), n_rot, the mode ("norm": pairs (2j, 2j+1); "neox": (j, j + n_rot/2)), the factor mscale
+    on cos and sin, and the optional per-head norm weights (float32 (D), both or neither) with their eps.
+    Every frequency scaling is linear in the position, so it lives in the table."""
+
+    def __init__(self, inv_freq: torch.Tensor, n_rot: int, mode: str, mscale: float = 1.0, q_norm: torch.Tensor | None = None,
+                 k_norm: torch.Tensor | None = None, eps: float = 1e-6):
+        if mode not in _lib.ROPE_MODES:
+            raise ValueError(f"mode={mode!r} is neither 'norm' nor 'neox'")
+        if n_rot < 2 or n_rot % 2 or inv_freq.numel() != n_rot // 2:
+            raise ValueError(f"n_rot={n_rot} must be even and inv_freq hold n_rot/2 values (it holds {inv_freq.numel()})")
+        if (q_norm is None) != (k_norm is None):
+            raise ValueError("q_norm and k_norm come together or not at all")
+        self.inv_freq, self.n_rot, self.mode, self.mscale = inv_freq.to(torch.float32).contiguous(), int(n_rot), mode, float(mscale)
+        self.q_norm, self.k_norm = (None if w is None else w.to(torch.float32).contiguous() for w in (q_norm, k_norm))
+        self.eps = float(eps)
+
+    @staticmethod
+    def table(n_rot: int, base: float = 10000.0, scaling: str = "none", factor: float = 1.0, n_ctx_orig: int = 0,
+              freq_factors=None):
+        """(inv_freq float64 (n_rot/2), mscale): f_j = base^(-2j/n_rot) / freq_factors[j]; "linear" multiplies
+        by 1/factor; "yarn" (beta_fast 32, beta_slow 1) blends f_j / factor and f_j over the ramp between the
+        pairs that turn 32 times and once in n_ctx_orig positions, with mscale = 1 + 0.1 ln(factor)."""
+        j = np.arange(n_rot // 2, dtype=np.float64)
+        f = float(base) ** (-2.0 * j / n_rot)
+        if freq_factors is not None:
+            f = f / _f32_values(freq_factors)[:n_rot // 2]
+        mscale = 1.0
+        if scaling == "linear":
+            f = f / factor
+        elif scaling == "yarn":
+            corr = lambda beta: n_rot * math.log(n_ctx_orig / (2 * math.pi * beta)) / (2 * math.log(base))  # noqa: E731
+            lo, hi = max(0, math.floor(corr(32.0))), min(n_rot - 1, math.ceil(corr(1.0)))
+            ramp = 1.0 - np.clip((j - lo) / max(0.001, hi - lo), 0.0, 1.0)
+            f = f * ((1.0 - ramp) / factor + ramp)
+            mscale = 1.0 + 0.1 * math.log(factor)
+        elif scaling != "none":
+            raise ValueError(f"rope scaling type {scaling!r} is none of 'none', 'linear', 'yarn'")
+        return f, mscale
+
+    @classmethod
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", mode: str | None = None) -> "RoPE":
+        """From a GGUF file's metadata and tensors (gguf.file.read_gguf): {arch}.rope.freq_base,
+        .dimension_count, .scaling.{type, factor, original_context_length}, the optional rope_freqs.weight
+        (Llama-3.1) and blk.<layer>.attn_{q,k}_norm.weight; the mode from the architecture unless given.
+        The table is computed in float64 and rounded to float32 once."""
+        arch = meta["general.architecture"]
+        if mode is None:
+            if arch not in ROPE_MODE:
+                raise ValueError(f"no rope mode known for architecture {arch!r}: pass mode='norm' or 'neox'")
+            mode = ROPE_MODE[arch]
+        get = lambda key, default=None: meta.get(f"{arch}.{key}", default)  # noqa: E731
+        D = get("attention.key_length") or get("embedding_length") // get("attention.head_count")
+        n_rot = int(get("rope.dimension_count", D))
+        ff = tensors.get("rope_freqs.weight")
+        f, mscale = cls.table(n_rot, float(get("rope.freq_base", 10000.0)), get("rope.scaling.type", "none"),
+                              float(get("rope.scaling.factor", 1.0)), int(get("rope.scaling.original_context_length", 0)), ff)
+        norms = [tensors.get(f"blk.{layer}.attn_{n}_norm.weight") for n in "qk"]
+        qn, kn = (None if w is None else torch.from_numpy(_f32_values(w).astype(np.float32)).to(device) for w in norms)
+        return cls(torch.from_numpy(f.astype(np.float32)).to(device), n_rot, mode, mscale, qn, kn,
+                   float(get("attention.layer_norm_rms_epsilon", 1e-6)))
 
 
 class KVCache:
@@ -53,6 +139,23 @@ class KVCache:
         _lib.kv_append(self.kind, k, v, self.k, self.v, self.strides, self.kv_len, self.capacity, self.B, N,
                        self.n_kv_head, self.D)
         self._n = N
+
+    def append_rope(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, rope: RoPE, out: torch.Tensor | None = None):
+        """append with the rotary embedding on the way (gq_rope_append): q fp16 (B*N, n_head*D), k and v
+        (B*N, n_kv_head*D) as the projections wrote them, possibly column slices of one buffer.  The
+        per-head norm (where rope has one) and the rotation by each token's position are applied to q and
+        k, k and v go into the caches, and the rotated q is returned (in `out`; out=q rotates in place)."""
+        N = q.shape[0] // self.B
+        if N * self.B != q.shape[0] or N < 1:
+            raise ValueError(f"q has {q.shape[0]} rows, not a positive multiple of B = {self.B}")
+        if q.shape[1] % self.D:
+            raise ValueError(f"q has {q.shape[1]} columns, not a multiple of D = {self.D}")
+        self.kv_len += N
+        out = _lib.rope_append(self.kind, rope.mode, q, k, v, self.k, self.v, self.strides, self.kv_len, self.capacity,
+                               rope.inv_freq, rope.n_rot, self.B, N, q.shape[1] // self.D, self.n_kv_head, self.D, rope.mscale,
+                               rope.q_norm, rope.k_norm, rope.eps, out)
+        self._n = N
+        return out
 
     def attend(self, q: torch.Tensor, scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
         """q: fp16 (B*N, n_head*D), the queries of the N tokens last appended -> (B*N, n_head*D) fp16."""

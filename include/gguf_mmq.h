@@ -32,6 +32,7 @@
  *   gq_attn_decode                      decode attention over an fp16 or Q8_0 KV cache, grouped query heads
  *   gq_attn_prefill                     the same for a prompt or a chunk of one: any number of new tokens, one launch
  *   gq_kv_append                        the new tokens' k and v rows into that cache, on the device
+ *   gq_rope_append                      per-head norm + RoPE of q and k, then that append, in one launch
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -618,6 +619,47 @@ int gq_debug_attn_prefill_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_k
 int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
                  int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B, int64_t N,
                  int64_t n_kv_head, int64_t D, void *stream);
+
+/*
+ * The step between the q/k/v projections and the attention, in ONE launch: an optional per-head RMSNorm
+ * of q and k (Qwen3, Gemma-3, OLMo-2: attn_q_norm / attn_k_norm), the rotary position embedding of both,
+ * q to Qout, and k and v into the caches as gq_kv_append writes them.  Token i of sequence b has
+ * position p = kv_len[b] - N + i, read on the device (gq_kv_append's kv_len: it includes the N new
+ * tokens), so a captured graph of a step needs no position tensor.
+ *   Q, Knew, Vnew : fp16 (B*N, n_head*D) and (B*N, n_kv_head*D), rows ldq / ldk / ldv apart: they may be
+ *            column slices of one packed qkv buffer.  Qout: fp16, rows ldqo apart; Qout == Q with
+ *            ldqo == ldq rotates q in place.
+ *   Kc, Vc, tok_stride, head_stride, seq_stride, kv_len, capacity : as gq_attn_decode's.
+ *   inv_freq : fp32 (n_rot/2) in device memory; mscale: a factor on cos and sin.  Every frequency-scaling
+ *            scheme (linear, YaRN, Llama-3.1's factors) is a table and an mscale: the caller's.
+ *   q_norm_w, k_norm_w : fp32 (D) in device memory, or both NULL: no norm.
+ *   y = x * rsqrt(mean_D(x^2) + eps) * w in fp32, NOT rounded to fp16 (y = x without a norm); for pair
+ *   j < n_rot/2, theta = p * inv_freq[j], (c, s) = mscale * (cos theta, sin theta), out0 = fp16(y0 c - y1 s),
+ *   out1 = fp16(y0 s + y1 c), the pair being elements (2j, 2j+1) for GQ_ROPE_NORM (llama) and
+ *   (j, j + n_rot/2) for GQ_ROPE_NEOX; elements at or beyond n_rot pass through as fp16(y).  theta is
+ *   formed and reduced in fp64 -- an fp32 product is off by theta * 2^-24, 2^-8 rad at position 131072 --
+ *   and sin and cos are fp32 polynomials of the reduced angle.  Every rotated element is within
+ *     |out - exact| <= 2^-11 |exact| + 2^-25 + kappa * mscale * (|y0| + |y1|)
+ *   of the float64 result from theta = double(p) * double(inv_freq[j]) and the exact norm; kappa = 2^-19
+ *   without a norm, 2^-16 with one; a pass-through element within 2^-11 |y| + 2^-25 + kappa |y|.
+ *   The rotated k goes into the K cache row of (b, kv head, p): its fp16 values for GQ_KV_F16, for
+ *   GQ_KV_Q8_0 the blocks gq_kv_append makes of those fp16 values, byte for byte.  v goes into the V cache
+ *   exactly as gq_kv_append writes it.  A position outside [0, capacity) is the caller's error: that
+ *   token's cache rows are skipped, nothing outside the cache is written, its q row is still rotated by p.
+ * The grid depends on B, N, the head counts and the device only.  Checks in gq_kv_append's order with its
+ * messages (n_head % n_kv_head == 0 as gq_attn_prefill's); besides: a null Qout or inv_freq, ldq or ldqo
+ * < n_head*D, ldk or ldv < n_kv_head*D, exactly one norm weight null: GQ_EINVAL; an unknown mode, n_rot
+ * odd, < 2 or > D, B*N >= 2^31: GQ_EUNSUPPORTED.  B, N or n_head == 0: a no-op.  Every check precedes the
+ * launch.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol;
+ * gq_version() did not change with it.
+ */
+typedef enum { GQ_ROPE_NORM = 0, GQ_ROPE_NEOX = 1 } gq_rope_mode;
+int gq_rope_append(gq_kv_type kv, gq_rope_mode mode, const void *Q, int64_t ldq, const void *Knew, int64_t ldk,
+                   const void *Vnew, int64_t ldv, void *Qout, int64_t ldqo, void *Kc, void *Vc,
+                   int64_t tok_stride, int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity,
+                   const float *inv_freq, int64_t n_rot, float mscale,
+                   const float *q_norm_w, const float *k_norm_w, float eps,   /* both NULL: no norm */
+                   int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE

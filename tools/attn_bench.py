@@ -21,6 +21,18 @@ Prefill attention (kernels._lib.attn_prefill: gq_attn_prefill) by the same metho
 N in {128, 512, 2048, 8192} new tokens without a prefix and 512 after a prefix of 4096, and one B = 4
 cell; a cell is the median time, its spread, the causal TFLOP/s (4 D flops per attended (row, key) pair)
 and that as a share of bench.py's MFMA_F16_PEAK_TF (PrefillCase).
+
+    python tools/attn_bench.py --rope [--steps 20] [--out profiles/rope_bench.json]
+
+The fused per-head norm + RoPE + KV append (kernels._lib.rope_append: gq_rope_append) beside the path a
+caller had before it: torch RoPE from a position tensor (arange + kv_len - N, outer product, cos, sin,
+rotate, cast), the torch per-head RMSNorm where the model has one, then kv_append (RopeCase).  Llama-3-8B
+heads (32 / 8, D 128, NORM pairs) and Qwen3-8B heads (32 / 8, D 128, NEOX pairs, q/k norm), fp16 and Q8_0
+caches, B = 1 with N in {1, 4, 512, 8192} new tokens into an empty cache of that capacity.  Every step uses
+another copy of the packed qkv rows, the q output and the caches; the copies hold >= 1 GiB together, but
+never more than 256 of them, so the cells at N <= 4 (KiB per step) measure launches on cached data.  A cell
+is the median time of both forms, their spread, and for N >= 512 the bytes a step must move (qkv read, q and
+cache rows written) per second against bench.py's HBM figure.
 """
 import argparse
 import json
@@ -123,6 +135,97 @@ class PrefillCase:
     check = Case.check
 
 
+ROPE_HEADS = {"llama3_8b": (32, 8, 128, "norm", False), "qwen3_8b": (32, 8, 128, "neox", True)}
+
+
+class RopeCase:
+    def __init__(self, nh, kvh, D, mode, norm, kind, T, dev, steps):
+        import kernels._lib as kl
+        from kernels import RoPE
+        self.kl, self.dev, self.dims, self.kind = kl, dev, (nh, kvh, D, T), kind
+        rb, J = kl.kv_row_bytes(kind, D), nh + 2 * kvh
+        self.bytes = 2 * T * J * D + 2 * T * nh * D + 2 * T * kvh * rb
+        ncopies, self.plans = bench.rotation_plan(max(self.bytes, bench.ROTATE_BYTES // 256), steps)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        self.qkv = torch.randn(ncopies, T, J * D, device=dev, generator=gen).to(torch.float16)
+        self.qo = torch.empty(ncopies, T, nh * D, dtype=torch.float16, device=dev)
+        # (kv_append wants k and v rows one stride apart: the base gets its v rows contiguous, made here, not in the step)
+        self.v = self.qkv[:, :, (nh + kvh) * D:].contiguous()
+        self.caches = torch.zeros(ncopies, 2, T * kvh * rb, dtype=torch.uint8, device=dev)
+        self.strides = (kvh * rb, rb, T * kvh * rb)
+        self.kv_len = torch.full((1,), T, dtype=torch.int32, device=dev)
+        f, m = RoPE.table(D, 500000.0 if mode == "norm" else 1e6)
+        w = [1 + 0.1 * torch.randn(D, device=dev, generator=gen) for _ in range(2)] if norm else [None, None]
+        self.rope = RoPE(torch.from_numpy(f).float().to(dev), D, mode, m, w[0], w[1], 1e-6)
+
+    def _torch_rope(self, x, heads, w, cos, sin):
+        nh, kvh, D, T = self.dims
+        y = x.float().view(T, heads, D)
+        if w is not None:
+            y = y * torch.rsqrt(y.pow(2).mean(-1, keepdim=True) + self.rope.eps) * w
+        if self.rope.mode == "norm":
+            y0, y1 = y[..., 0::2], y[..., 1::2]
+            o = torch.stack((y0 * cos - y1 * sin, y0 * sin + y1 * cos), dim=-1)
+        else:
+            y0, y1 = y[..., :D // 2], y[..., D // 2:]
+            o = torch.cat((y0 * cos - y1 * sin, y0 * sin + y1 * cos), dim=-1)
+        return o.reshape(T, heads * D).to(torch.float16)
+
+    def step(self, form, c, i):
+        nh, kvh, D, T = self.dims
+        q, k, v = self.qkv[c, :, :nh * D], self.qkv[c, :, nh * D:(nh + kvh) * D], self.qkv[c, :, (nh + kvh) * D:]
+        Kc, Vc = self.caches[c, 0], self.caches[c, 1]
+        r = self.rope
+        if form == "fused":
+            return self.kl.rope_append(self.kind, r.mode, q, k, v, Kc, Vc, self.strides, self.kv_len, T, r.inv_freq, D, 1, T, nh, kvh,
+                                       D, r.mscale, r.q_norm, r.k_norm, r.eps, out=self.qo[c])
+        pos = torch.arange(T, device=self.dev, dtype=torch.int32) + (self.kv_len - T)  # the caller's position tensor
+        ang = torch.outer(pos.float(), r.inv_freq)[:, None, :]
+        cos, sin = ang.cos() * r.mscale, ang.sin() * r.mscale
+        self.qo[c].copy_(self._torch_rope(q, nh, r.q_norm, cos, sin))
+        self.kl.kv_append(self.kind, self._torch_rope(k, kvh, r.k_norm, cos, sin), self.v[c], Kc, Vc, self.strides, self.kv_len, T, 1, T, kvh, D)
+        return self.qo[c]
+
+    def check(self):
+        a = self.step("torch", 0, 0).float().clone()
+        b = self.step("fused", 0, 0).float()
+        torch.cuda.synchronize(self.dev)
+        d = float((a - b).abs().max() / a.abs().max())
+        assert d <= 2e-3, d  # (the base forms its angles in fp32)
+        return d
+
+
+def main_rope(a, dev):
+    rows, forms = [], ("torch", "fused")
+    for name, (nh, kvh, D, mode, norm) in ROPE_HEADS.items():
+        for kind in ("f16", "q8_0"):
+            for T in (1, 4, 512, 8192):
+                case = RopeCase(nh, kvh, D, mode, norm, kind, T, dev, a.steps)
+                diff = case.check()
+                gs = {f: graphs(case, f) for f in forms}
+                ts = {f: [] for f in forms}
+                for _ in range(a.repeats):  # interleaved: one pass over the forms per repeat
+                    for f in forms:
+                        ts[f].append(bench.timed_rotation(gs[f], dev) / a.steps * 1e6)
+                row = {"heads": name, "mode": mode, "qk_norm": norm, "kv": kind, "tokens": T, "step_bytes": case.bytes,
+                       "copies": int(case.qkv.shape[0]), "fused_vs_torch_max_rel_diff": round(diff, 6)}
+                for f in forms:
+                    us = float(np.median(ts[f]))
+                    row[f] = {"us": round(us, 2), "spread_us": round(max(ts[f]) - min(ts[f]), 2)}
+                    if T >= 512:
+                        row[f]["GBs"] = round(case.bytes / us / 1e3, 1)
+                        row[f]["hbm_frac"] = round(case.bytes / us / 1e3 / bench.HBM_PEAK_GBS, 4)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                del case, gs
+                torch.cuda.empty_cache()
+                if a.out:  # (after every cell: a run cut short keeps what it measured)
+                    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                    with open(a.out, "w") as f:
+                        json.dump({"steps": a.steps, "repeats": a.repeats, "hbm_peak_GBs": bench.HBM_PEAK_GBS,
+                                   "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count, "rows": rows}, f, indent=1)
+
+
 # "f16_gather": the fp16 form with V^T gathered element by element (GQ_ATTN_TRV=0), the alternative
 # the transposing LDS read was measured against
 PREFILL_FORMS = ("torch", "f16", "f16_gather", "q8_0")
@@ -207,12 +310,15 @@ def main():
     ap.add_argument("--max-len", type=int, default=32768)
     ap.add_argument("--out", default=None)
     ap.add_argument("--prefill", action="store_true", help="prefill attention (attn_prefill) instead of decode")
+    ap.add_argument("--rope", action="store_true", help="the fused norm + RoPE + append (rope_append) beside torch RoPE + kv_append")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("attn_bench.py needs a ROCm device: there is no CPU timing path")
     dev = torch.device("cuda:0")
     if a.prefill:
         return main_prefill(a, dev)
+    if a.rope:
+        return main_rope(a, dev)
     rows = []
     for name, (nh, kvh, D) in HEADS.items():
         for L in (512, 4096, 32768):
