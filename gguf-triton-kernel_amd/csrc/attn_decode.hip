@@ -35,6 +35,32 @@
 // Each workgroup merges its four waves through LDS and writes one fp32 partial (m, l, o[R][D]) to
 // the workspace; attn_combine_kernel merges the W partials of a row in w order.  No atomics, no
 // workgroup waits for another.
+//
+// D = 256 (Gemma).  Two slots per wave would be 4 x 2 x 32 KiB at fp16 against 160 KiB of LDS, so a
+// wave keeps ONE slot and refills it by halves: the K half as soon as QK^T has read it (in flight
+// under the softmax and the second product of the same tile), the V half after the second product
+// (in flight under the next tile's QK^T).  Half a tile per wave, 64 KiB per compute unit at fp16, is
+// always on its way under MFMAs; the slot's LDS reads are drained (lgkmcnt(0)) before the DMA that
+// overwrites it is issued.  Ring 4 x 32 KiB = 128 KiB (Q8_0: 4 x 18 KiB); the merge area,
+// 4 * ROWS * (D + 2) * 4 = 129 KiB at two row tiles, overlays it.  fp16 rows are 512 bytes = 32
+// pieces, piece p of row r at p ^ (r & 15): a row is two bank lines, the xor moves the piece within
+// its line, so the 16 rows of a K fragment read still cover the 64 banks once.  fp16 V^T comes from
+// prefill's two transposing reads (ds_read_b64_tr_b16) per 16 columns, not from eight 2-byte gathers:
+// with the gather the two-row-tile kernel spilled to scratch.  The DMA geometry is recomputed per
+// issue (2 x 16 registers otherwise live across the loop).
+//
+// Sliding window (gq_attn_opts.window > 0): row of position p attends [max(0, p - window + 1), p].
+// The tile range is cut, not only masked: the W workgroups share the tiles from the one that holds
+// the FIRST row's window start to the last row's limit, rows before that start are not fetched, and
+// the per-row lower bound is one more compare on the key index.  A masked score is -inf, its p an
+// exact 0, so a fetched key outside a row's window adds 0 * (finite) = 0.
+//
+// Soft-cap (gq_attn_opts.softcap > 0; the CAP instantiations -- the others keep their code): the
+// score becomes cap * tanh(scale s / cap), in the exp2 domain cc * tanh(x) with cc = cap log2(e),
+// x = s * scale / cap, and tanh(x) = 1 - 2 / (1 + 2^(2 log2(e) x)): one v_exp_f32, one v_rcp_f32,
+// one fma, saturating to +-1 through inf and 0 without a branch.  Absolute error of the tanh below
+// 2^-21, i.e. cap * 2^-21 in the exponent: 2^-15 at cap 50.
+#include "gguf_attn.hpp"
 #include "gguf_blocks.hpp"
 #include "gguf_internal.hpp"
 #include "gguf_mfma.hpp"
@@ -45,6 +71,7 @@ namespace {
 
 constexpr int kAttnWaves = 4;
 constexpr float kNegInf = -__builtin_huge_valf();
+typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 struct AttnArgs {
     const uint16_t *Q;
@@ -54,7 +81,9 @@ struct AttnArgs {
     float *ws;
     int64_t ldq, ldo, tok_stride, head_stride, seq_stride;
     int capacity, N, G, n_kv, W;
-    float c; // scale * log2(e): scores are kept in the exp2 domain
+    int window;   // 0: unbounded
+    float c;      // scale * log2(e): scores are kept in the exp2 domain
+    float cx, cc; // soft-cap: 2 log2(e) scale / cap and cap log2(e)
 };
 
 // floats per partial slot: o[R][D], then (m, l)[R], padded to 16 bytes
@@ -67,19 +96,16 @@ template <int KV, int D> struct ATile {
     static constexpr int NI = (kAttnTile * PPR + 63) / 64;       // DMA instructions per K (or V) tile
     static constexpr int TILEB = 1024 * NI;
     static constexpr int SLOT = 2 * TILEB;                       // K tile, V tile
-    static constexpr int RING = kAttnWaves * kAttnRing * SLOT;
+    static constexpr int SLOTS = D == 256 ? 1 : kAttnRing;       // D = 256: one slot, refilled by halves
+    static constexpr int RING = kAttnWaves * SLOTS * SLOT;
 };
 
-template <int D> __device__ __forceinline__ int f16_swz(int r) { return D == 128 ? (r & 15) : ((r >> 1) & 7); }
-
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float xor_lanes(float v, int m) { return __shfl_xor(v, m, 64); }
-
-template <int KV, int D, int RT>
+template <int KV, int D, int RT, bool CAP>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
 {
     using T = ATile<KV, D>;
     constexpr int ROWS = 16 * RT, NI = T::NI, KS = D / 32, NG = D / 16;
+    constexpr bool HALVES = T::SLOTS == 1;
     constexpr int MERGE = kAttnWaves * ROWS * (D + 2) * 4;
     __shared__ __attribute__((aligned(16))) uint8_t smem[T::RING > MERGE ? T::RING : MERGE];
 
@@ -90,8 +116,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
     const int R = a.N * a.G;
     int len = a.kv_len[b];
     len = len < 0 ? 0 : (len > a.capacity ? a.capacity : len); // never outside the cache
-    const int ntiles = (len + kAttnTile - 1) / kAttnTile;
-    const int t0 = (int)((int64_t)ntiles * w / a.W), t1 = (int)((int64_t)ntiles * (w + 1) / a.W);
+    // the first row's window start (0 without a window): no tile and no row before it is fetched
+    const int wlo = a.window > 0 && len - a.N - a.window + 1 > 0 ? len - a.N - a.window + 1 : 0;
+    const int tlo = wlo / kAttnTile, ntiles = (len + kAttnTile - 1) / kAttnTile - tlo;
+    const int t0 = tlo + (int)((int64_t)ntiles * w / a.W), t1 = tlo + (int)((int64_t)ntiles * (w + 1) / a.W);
     float *part = a.ws + (int64_t)blockIdx.x * attn_slot_floats(R, D);
     if (t1 == t0) { // an empty share: the neutral partial (the combine skips its o)
         if (tid < R) *(f32x2 *)(part + (int64_t)R * D + 2 * tid) = (f32x2){kNegInf, 0.f};
@@ -101,13 +129,14 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
 
     // ---- Q fragments, and the last key each of the lane's rows attends ----
     f16x8 qf[RT][KS];
-    int lim[RT];
+    int lim[RT], lo[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int r = 16 * rt + c;
         const bool live = r < R;
         const int tok = live ? r / a.G : 0, jh = live ? r - tok * a.G : 0;
         lim[rt] = live ? len - a.N + tok : -1;
+        lo[rt] = a.window > 0 ? lim[rt] - a.window + 1 : 0; // (negative: no lower bound)
         const uint16_t *q = a.Q + ((int64_t)b * a.N + tok) * a.ldq + ((int64_t)h * a.G + jh) * D + 8 * g;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -124,28 +153,44 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
     const int64_t base = (int64_t)b * a.seq_stride + (int64_t)h * a.head_stride;
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.Kc + base), 0, (int)span, 0x00020000);
     const __amdgpu_buffer_rsrc_t vrs = __builtin_amdgcn_make_buffer_rsrc((void *)(a.Vc + base), 0, (int)span, 0x00020000);
-    int drow[NI];
-    uint32_t doff[NI];
+    auto geom = [&](int ln, int k, int &row, uint32_t &at) {
+        const int s = 64 * k + ln, r = s / T::PPR, p = s - r * T::PPR;
+        row = r < kAttnTile ? r : 0x40000000; // (Q8_0: the last instruction's spare lanes fetch nothing)
+        at = (uint32_t)(r & (kAttnTile - 1)) * (uint32_t)a.tok_stride + 16u * (uint32_t)(KV ? p : (p ^ f16_swz<D>(r)));
+    };
+    // D = 256: 2 x 16 registers of geometry would not fit beside the accumulators -- recomputed per issue instead
+    int drow[HALVES ? 1 : NI];
+    uint32_t doff[HALVES ? 1 : NI];
+    if constexpr (!HALVES) {
 #pragma unroll
-    for (int k = 0; k < NI; ++k) {
-        const int s = 64 * k + lane, r = s / T::PPR, p = s - r * T::PPR;
-        drow[k] = r < kAttnTile ? r : 0x40000000; // (Q8_0: the last instruction's spare lanes fetch nothing)
-        doff[k] = (uint32_t)(r & (kAttnTile - 1)) * (uint32_t)a.tok_stride + 16u * (uint32_t)(KV ? p : (p ^ f16_swz<D>(r)));
+        for (int k = 0; k < NI; ++k) geom(lane, k, drow[k], doff[k]);
     }
-    uint8_t *ring = smem + wave * (kAttnRing * T::SLOT);
-    auto issue = [&](int i) {
+    uint8_t *ring = smem + wave * (T::SLOTS * T::SLOT);
+    // which: 1 the K tile, 2 the V tile, 3 both
+    auto issue = [&](int i, int which) {
         const int t = t0 + wave + kAttnWaves * i;
         const bool real = i < ntile;
-        uint8_t *dst = ring + (i % kAttnRing) * T::SLOT;
+        uint8_t *dst = ring + (i % T::SLOTS) * T::SLOT;
         const uint32_t tb = (uint32_t)t * kAttnTile * (uint32_t)a.tok_stride;
         uint32_t off[NI];
+        int ln = lane;
+        if constexpr (HALVES) asm volatile("" : "+v"(ln)); // (opaque: keeps the geometry out of the loop's live registers)
 #pragma unroll
-        for (int k = 0; k < NI; ++k) // no tile, a spare lane, a dead row: outside the resource -- zeros, no access
-            off[k] = real && t * kAttnTile + drow[k] < len ? tb + doff[k] : 0x80000000u;
+        for (int k = 0; k < NI; ++k) { // no tile, a spare lane, a dead row, a row before the window: outside the resource -- zeros, no access
+            int row = drow[HALVES ? 0 : k];
+            uint32_t at = doff[HALVES ? 0 : k];
+            if constexpr (HALVES) geom(ln, k, row, at);
+            const int key = t * kAttnTile + row;
+            off[k] = real && key < len && key >= wlo ? tb + at : 0x80000000u;
+        }
+        if (which & 1) {
 #pragma unroll
-        for (int k = 0; k < NI; ++k) dma16(krs, dst + 1024 * k, off[k], 0);
+            for (int k = 0; k < NI; ++k) dma16(krs, dst + 1024 * k, off[k], 0);
+        }
+        if (which & 2) {
 #pragma unroll
-        for (int k = 0; k < NI; ++k) dma16(vrs, dst + T::TILEB + 1024 * k, off[k], 0);
+            for (int k = 0; k < NI; ++k) dma16(vrs, dst + T::TILEB + 1024 * k, off[k], 0);
+        }
     };
 
     float m[RT], l[RT];
@@ -166,11 +211,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[rt][ks])); // (used here: no wait for Q inside the loop)
-    issue(0);
+    issue(0, 3);
     for (int i = 0; i < ntile; ++i) {
-        issue(i + 1); // (past the last tile: zeros, the same count)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * NI) : "memory"); // tile i's K
-        const uint8_t *Kt = ring + (i % kAttnRing) * T::SLOT, *Vt = Kt + T::TILEB;
+        if constexpr (!HALVES) issue(i + 1, 3); // (past the last tile: zeros, the same count)
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HALVES ? NI : 3 * NI) : "memory"); // tile i's K
+        const uint8_t *Kt = ring + (i % T::SLOTS) * T::SLOT, *Vt = Kt + T::TILEB;
         const int key0 = (t0 + wave + kAttnWaves * i) * kAttnTile;
 
         // ---- S^T = K Q^T, two 16-key tiles ----
@@ -212,6 +257,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
             }
         }
 
+        if constexpr (HALVES) { // the K half is read: tile i + 1's K goes into it, under the softmax and the second product
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            issue(i + 1, 1);
+        }
+
         // ---- online softmax in fp32, per row (a row's four lanes g hold 8 keys each) ----
         f16x8 pf[RT];
         float p[RT][8];
@@ -221,7 +271,8 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int key = key0 + vrow[j];
-                sc[j] = key <= lim[rt] ? s[j >> 2][rt][j & 3] * a.c : kNegInf;
+                const float sv = s[j >> 2][rt][j & 3];
+                sc[j] = key <= lim[rt] && key >= lo[rt] ? (CAP ? capped(sv * a.cx, a.cc) : sv * a.c) : kNegInf;
                 mx = fmaxf(mx, sc[j]);
             }
             mx = fmaxf(mx, xor_lanes(mx, 16));
@@ -245,15 +296,28 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
         }
 
         // ---- O^T += V^T P^T ----
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NI) : "memory"); // tile i's V
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(HALVES ? NI : 2 * NI) : "memory"); // tile i's V
         if constexpr (KV == 0) {
 #pragma unroll
             for (int n = 0; n < NG; ++n) {
                 f16x8 vf;
+                if constexpr (D == 256) {
+                    // two transposing reads (ds_read_b64_tr_b16), as prefill's: lane c of group g sends rows 4g + c / 4
+                    // and 16 more, columns 16n + 4 (c % 4) .. + 3, and receives column 16n + c of the group's four rows
+                    s16x4 half[2];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int r = vrow[j];
-                    vf[j] = *(const _Float16 *)(Vt + r * T::ROWB + 16 * ((2 * n + (c >> 3)) ^ f16_swz<D>(r)) + 2 * (c & 7));
+                    for (int u = 0; u < 2; ++u) {
+                        const int r = 16 * u + 4 * g + (c >> 2);
+                        const uint8_t *at = Vt + r * T::ROWB + 16 * ((2 * n + ((c >> 1) & 1)) ^ f16_swz<D>(r)) + 8 * (c & 1);
+                        half[u] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3))) *)at);
+                    }
+                    vf = __builtin_bit_cast(f16x8, __builtin_shufflevector(half[0], half[1], 0, 1, 2, 3, 4, 5, 6, 7));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int r = vrow[j];
+                        vf[j] = *(const _Float16 *)(Vt + r * T::ROWB + 16 * ((2 * n + (c >> 3)) ^ f16_swz<D>(r)) + 2 * (c & 7));
+                    }
                 }
 #pragma unroll
                 for (int rt = 0; rt < RT; ++rt) o[rt][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pf[rt], o[rt][n], 0, 0, 0);
@@ -284,6 +348,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
             }
         }
         asm volatile("" ::: "memory"); // the slot's reads stay above the next issue into it
+        if constexpr (HALVES) { // the V half is read: tile i + 1's V goes into it, under the next QK^T
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            issue(i + 1, 2);
+        }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the trailing (empty) tile has landed: the ring is dead
     __syncthreads();
@@ -321,9 +389,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AttnArgs a)
     }
 }
 
-// Row (b, h, r) of the output from its W partials, in w order: block = one row, thread t columns 2t, 2t + 1
+// Row (b, h, r) of the output from its W partials, in w order: block = one row (64 threads, 128 at D = 256),
+// thread t columns 2t, 2t + 1
 template <int D>
-__global__ __launch_bounds__(64) void attn_combine_kernel(const AttnArgs a)
+__global__ __launch_bounds__(D > 128 ? D / 2 : 64) void attn_combine_kernel(const AttnArgs a)
 {
     const int R = a.N * a.G;
     const int r = (int)(blockIdx.x % (unsigned)R), bh = (int)(blockIdx.x / (unsigned)R);
@@ -383,17 +452,20 @@ __global__ __launch_bounds__(64) void kv_append_kernel(const AppendArgs a)
 
 } // namespace
 
-AttnPlan plan_attn(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D)
+AttnPlan plan_attn(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int64_t window)
 {
     AttnPlan p;
-    if (B <= 0 || N <= 0 || n_head <= 0 || n_kv_head <= 0 || (D != 64 && D != 128) || n_head % n_kv_head != 0) return p;
+    if (B <= 0 || N <= 0 || n_head <= 0 || n_kv_head <= 0 || (D != 64 && D != 128 && D != 256) || n_head % n_kv_head != 0) return p;
     const int64_t G = n_head / n_kv_head, R = N * G, BH = B * n_kv_head;
     if (R > 32 || BH > (1 << 20)) return p;
     p.ok = true;
     p.R = (int)R;
     // one workgroup per compute unit (the fp16 D = 128 ring fills its LDS), spread over the (b, h)
     const int64_t cus = num_cus(), pin = tuning().attn_w;
-    const int64_t W = pin > 0 ? pin : (cus / BH < 1 ? 1 : (cus / BH > kAttnMaxW ? kAttnMaxW : cus / BH));
+    int64_t W = pin > 0 ? pin : (cus / BH < 1 ? 1 : (cus / BH > kAttnMaxW ? kAttnMaxW : cus / BH));
+    // a window: no more workgroups than the tiles its window + N - 1 positions can touch (one more when they straddle)
+    const int64_t wtiles = window > 0 ? (window + N - 2) / kAttnTile + 2 : W;
+    if (pin <= 0 && wtiles < W) W = wtiles;
     p.W = (int)W;
     p.grid = (int)(BH * W);
     // sized by a bound on BH * W that grows with B and n_kv_head: min(kAttnMaxW BH, max(BH, cus))
@@ -410,18 +482,22 @@ hipError_t launch_attn_decode(int kv, const AttnCall &c, const AttnPlan &p, hipS
     a.ldq = c.ldq, a.ldo = c.ldo, a.tok_stride = c.tok_stride, a.head_stride = c.head_stride, a.seq_stride = c.seq_stride;
     a.capacity = (int)c.capacity, a.N = (int)c.N, a.G = (int)(c.n_head / c.n_kv_head), a.n_kv = (int)c.n_kv_head, a.W = p.W;
     a.c = c.scale * 1.4426950408889634f;
+    a.window = (int)c.window; // (the entry passes 0 for a window of the capacity or more: it bounds nothing)
+    const bool cap = c.softcap > 0.f;
+    if (cap) a.cx = softcap_consts(c.scale, c.softcap).cx, a.cc = softcap_consts(c.scale, c.softcap).cc;
     const dim3 grid((unsigned)p.grid), block(256);
     const int rt = p.R > 16 ? 2 : 1;
-#define GQ_ATTN(KV, D, RT) attn_decode_kernel<KV, D, RT><<<grid, block, 0, s>>>(a)
-    if (kv == 0 && c.D == 128) rt == 2 ? GQ_ATTN(0, 128, 2) : GQ_ATTN(0, 128, 1);
-    else if (kv == 0) rt == 2 ? GQ_ATTN(0, 64, 2) : GQ_ATTN(0, 64, 1);
-    else if (c.D == 128) rt == 2 ? GQ_ATTN(1, 128, 2) : GQ_ATTN(1, 128, 1);
-    else rt == 2 ? GQ_ATTN(1, 64, 2) : GQ_ATTN(1, 64, 1);
+#define GQ_ATTN(KV, D, RT) (cap ? attn_decode_kernel<KV, D, RT, true><<<grid, block, 0, s>>>(a) : attn_decode_kernel<KV, D, RT, false><<<grid, block, 0, s>>>(a))
+#define GQ_ATTN_D(KV, RT) (c.D == 256 ? GQ_ATTN(KV, 256, RT) : c.D == 128 ? GQ_ATTN(KV, 128, RT) : GQ_ATTN(KV, 64, RT))
+    if (kv == 0) rt == 2 ? GQ_ATTN_D(0, 2) : GQ_ATTN_D(0, 1);
+    else rt == 2 ? GQ_ATTN_D(1, 2) : GQ_ATTN_D(1, 1);
+#undef GQ_ATTN_D
 #undef GQ_ATTN
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const dim3 cgrid((unsigned)(c.B * c.n_kv_head * p.R)), cblock(64);
-    if (c.D == 128) attn_combine_kernel<128><<<cgrid, cblock, 0, s>>>(a);
+    const dim3 cgrid((unsigned)(c.B * c.n_kv_head * p.R)), cblock(c.D == 256 ? 128 : 64);
+    if (c.D == 256) attn_combine_kernel<256><<<cgrid, cblock, 0, s>>>(a);
+    else if (c.D == 128) attn_combine_kernel<128><<<cgrid, cblock, 0, s>>>(a);
     else attn_combine_kernel<64><<<cgrid, cblock, 0, s>>>(a);
     return hipGetLastError();
 }

@@ -37,6 +37,18 @@
 // the 16 rows x 32 bytes a wave reads cover every bank twice, which is what 512 bytes cost anyway.
 // Q8_0 keeps the byte gather.  LDS rows: decode's swizzled 16-byte pieces (fp16), raw 34-byte blocks
 // in 144 / 80-byte rows (Q8_0).
+//
+// D = 256 (Gemma): a slot holds ONE 32-key step (PTile::TK = 32), so the fp16 ring is 2 x 2 x 16 KiB =
+// 64 KiB as at D = 128 and two workgroups still fit a compute unit's LDS (Q8_0: 2 x 2 x 12 KiB); the
+// barrier then comes once per 32 keys.  512-byte rows keep decode's piece ^ (row & 15) swizzle.
+//
+// Sliding window (gq_attn_opts.window > 0; attn_decode.hip has the rule).  A workgroup starts at the
+// tile that holds its FIRST row's window start and fetches no row before it; a wave skips the steps
+// that end before its own FIRST row's window start -- the earliest of its rows' starts -- (wave-uniform,
+// like the causal skip), and the lower-bound compare runs only in steps that begin before its LAST
+// row's start, the latest.  Soft-cap: the CAP instantiations, decode's
+// formula.
+#include "gguf_attn.hpp"
 #include "gguf_blocks.hpp"
 #include "gguf_internal.hpp"
 #include "gguf_mfma.hpp"
@@ -56,28 +68,28 @@ struct PrefillArgs {
     uint16_t *O;
     int64_t ldq, ldo, tok_stride, head_stride, seq_stride;
     int capacity, N, G, n_kv, nblk, nbh, o8;
-    float c; // scale * log2(e): scores are kept in the exp2 domain
+    int window;   // 0: unbounded
+    float c;      // scale * log2(e): scores are kept in the exp2 domain
+    float cx, cc; // soft-cap: 2 log2(e) scale / cap and cap log2(e)
 };
 
 template <int KV, int D> struct PTile {
+    static constexpr int TK = prefill_tile(D);                               // keys per ring slot
     static constexpr int RB = KV ? 34 * (D / 32) : 2 * D;                    // bytes of a cache row
     static constexpr int PPR = (RB + 15) / 16;                               // 16-byte pieces per LDS row
     static constexpr int ROWB = 16 * PPR;
-    static constexpr int NIW = ((kPrefillTile * PPR + 63) / 64 + kWaves - 1) / kWaves; // DMAs per wave per K (or V) tile
+    static constexpr int NIW = ((TK * PPR + 63) / 64 + kWaves - 1) / kWaves; // DMAs per wave per K (or V) tile
     static constexpr int TILEB = 1024 * kWaves * NIW;
     static constexpr int SLOT = 2 * TILEB;                                   // K tile, V tile
     static constexpr int RING = kPrefillSlots * SLOT;
 };
 
-template <int D> __device__ __forceinline__ int f16_swz(int r) { return D == 128 ? (r & 15) : ((r >> 1) & 7); }
-__device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ float xor_lanes(float v, int m) { return __shfl_xor(v, m, 64); }
 
-template <int KV, int D, int RT, bool TRV = false>
+template <int KV, int D, int RT, bool TRV, bool CAP>
 __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
 {
     using T = PTile<KV, D>;
-    constexpr int WR = 16 * RT, ROWS = kWaves * WR, NIW = T::NIW, KS = D / 32, NG = D / 16;
+    constexpr int WR = 16 * RT, ROWS = kWaves * WR, NIW = T::NIW, KS = D / 32, NG = D / 16, TK = T::TK;
     __shared__ __attribute__((aligned(16))) uint8_t smem[T::RING];
 
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15;
@@ -92,19 +104,25 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
     const int r0 = rb * ROWS, rlast = (r0 + ROWS < R ? r0 + ROWS : R) - 1;
     int nkeys = len - a.N + rlast / a.G + 1;
     nkeys = nkeys < 0 ? 0 : nkeys;
-    const int ntiles = (nkeys + kPrefillTile - 1) / kPrefillTile;
+    const int ntiles = (nkeys + TK - 1) / TK;
     const int wr0 = r0 + wave * WR, wlast = (wr0 + WR < R ? wr0 + WR : R) - 1;
     const int wmin = wr0 < R ? len - a.N + wr0 / a.G : -1, wmax = wr0 < R ? len - a.N + wlast / a.G : -1;
+    // the window starts (0 without a window) of the block's first row -- nothing before it is fetched -- and
+    // of the wave's first and last rows: no row of the wave attends a key before wlo0, every row all keys from wlo1
+    const int wnd = a.window, pfirst = len - a.N + r0 / a.G;
+    const int klo = wnd > 0 && pfirst - wnd + 1 > 0 ? pfirst - wnd + 1 : 0, tfirst = klo / TK;
+    const int wlo0 = wnd > 0 && wmin - wnd + 1 > 0 ? wmin - wnd + 1 : 0, wlo1 = wnd > 0 && wmax - wnd + 1 > 0 ? wmax - wnd + 1 : 0;
 
     // ---- Q fragments, and the last key each of the lane's rows attends ----
     f16x8 qf[RT][KS];
-    int lim[RT];
+    int lim[RT], lo[RT];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
         const int r = wr0 + 16 * rt + c;
         const bool live = r < R;
         const int tok = live ? r / a.G : 0, jh = live ? r - tok * a.G : 0;
         lim[rt] = live ? len - a.N + tok : -1;
+        lo[rt] = wnd > 0 ? lim[rt] - wnd + 1 : 0; // (negative: no lower bound)
         const uint16_t *q = a.Q + ((int64_t)b * a.N + tok) * a.ldq + ((int64_t)h * a.G + jh) * D + 8 * g;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -126,16 +144,18 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
 #pragma unroll
     for (int k = 0; k < NIW; ++k) {
         const int s = 64 * (NIW * wave + k) + lane, r = s / T::PPR, p = s - r * T::PPR;
-        drow[k] = r < kPrefillTile ? r : 0x40000000; // (Q8_0: the spare lanes past the tile fetch nothing)
-        doff[k] = (uint32_t)(r & (kPrefillTile - 1)) * (uint32_t)a.tok_stride + 16u * (uint32_t)(KV ? p : (p ^ f16_swz<D>(r)));
+        drow[k] = r < TK ? r : 0x40000000; // (Q8_0: the spare lanes past the tile fetch nothing)
+        doff[k] = (uint32_t)(r & (TK - 1)) * (uint32_t)a.tok_stride + 16u * (uint32_t)(KV ? p : (p ^ f16_swz<D>(r)));
     }
     auto issue = [&](int t) {
         uint8_t *dst = smem + (t % kPrefillSlots) * T::SLOT + 1024 * NIW * wave;
-        const uint32_t tb = (uint32_t)t * kPrefillTile * (uint32_t)a.tok_stride;
+        const uint32_t tb = (uint32_t)t * TK * (uint32_t)a.tok_stride;
         uint32_t off[NIW];
 #pragma unroll
-        for (int k = 0; k < NIW; ++k) // a spare lane, a row no row of the block attends: outside the resource -- zeros, no access
-            off[k] = t * kPrefillTile + drow[k] < nkeys ? tb + doff[k] : 0x80000000u;
+        for (int k = 0; k < NIW; ++k) { // a spare lane, a row no row of the block attends: outside the resource -- zeros, no access
+            const int key = t * TK + drow[k];
+            off[k] = key < nkeys && key >= klo ? tb + doff[k] : 0x80000000u;
+        }
 #pragma unroll
         for (int k = 0; k < NIW; ++k) dma16(krs, dst + 1024 * k, off[k], 0);
 #pragma unroll
@@ -160,16 +180,16 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[rt][ks])); // (used here: no wait for Q inside the loop)
-    if (ntiles > 0) issue(0);
-    for (int i = 0; i < ntiles; ++i) {
+    if (ntiles > tfirst) issue(tfirst);
+    for (int i = tfirst; i < ntiles; ++i) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's quarter of tile i
         __syncthreads();                                  // tile i has landed; tile i - 1's slot is drained
         if (i + 1 < ntiles) issue(i + 1);
         const uint8_t *Kt0 = smem + (i % kPrefillSlots) * T::SLOT;
 #pragma unroll
-        for (int st = 0; st < kPrefillTile / kStep; ++st) {
-            const int key0 = i * kPrefillTile + st * kStep;
-            if (key0 > wmax) continue; // wholly beyond this wave's rows (wave-uniform)
+        for (int st = 0; st < TK / kStep; ++st) {
+            const int key0 = i * TK + st * kStep;
+            if (key0 > wmax || key0 + kStep <= wlo0) continue; // wholly beyond this wave's rows, or before all their windows (wave-uniform)
             const uint8_t *Kt = Kt0 + st * kStep * T::ROWB, *Vt = Kt + T::TILEB;
 
             // ---- S^T = K Q^T, two 16-key tiles ----
@@ -213,6 +233,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
 
             // ---- online softmax in fp32, per row (a row's four lanes g hold 8 keys each) ----
             const bool crosses = key0 + kStep - 1 > wmin; // some row of the wave ends inside this step
+            const bool starts = key0 < wlo1;              // some row's window starts inside or after it
             f16x8 pf[RT];
             float p[RT][8];
 #pragma unroll
@@ -220,8 +241,10 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
                 float sc[8], mx = kNegInf;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    sc[j] = s[j >> 2][rt][j & 3] * a.c;
+                    const float sv = s[j >> 2][rt][j & 3];
+                    sc[j] = CAP ? capped(sv * a.cx, a.cc) : sv * a.c;
                     if (crosses && key0 + vrow[j] > lim[rt]) sc[j] = kNegInf;
+                    if (starts && key0 + vrow[j] < lo[rt]) sc[j] = kNegInf;
                     mx = fmaxf(mx, sc[j]);
                 }
                 mx = fmaxf(mx, xor_lanes(mx, 16));
@@ -326,7 +349,7 @@ __global__ __launch_bounds__(256) void attn_prefill_kernel(const PrefillArgs a)
 PrefillPlan plan_attn_prefill(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D)
 {
     PrefillPlan p;
-    if (B <= 0 || N <= 0 || n_head <= 0 || n_kv_head <= 0 || (D != 64 && D != 128) || n_head % n_kv_head != 0) return p;
+    if (B <= 0 || N <= 0 || n_head <= 0 || n_kv_head <= 0 || (D != 64 && D != 128 && D != 256) || n_head % n_kv_head != 0) return p;
     if (B > INT32_MAX / n_kv_head || N > INT32_MAX / (n_head / n_kv_head)) return p;
     const int64_t R = N * (n_head / n_kv_head), BH = B * n_kv_head;
     // 128 rows where every compute unit still gets a workgroup, 64 otherwise
@@ -348,14 +371,19 @@ hipError_t launch_attn_prefill(int kv, const AttnCall &c, const PrefillPlan &p, 
     a.nblk = p.nblk, a.nbh = (int)(c.B * c.n_kv_head);
     a.o8 = (((uintptr_t)c.O | (uintptr_t)(2 * c.ldo)) & 7) == 0; // 8-byte stores of 4 columns
     a.c = c.scale * 1.4426950408889634f;
+    a.window = (int)c.window; // (the entry passes 0 for a window of the capacity or more: it bounds nothing)
+    const bool cap = c.softcap > 0.f;
+    if (cap) a.cx = softcap_consts(c.scale, c.softcap).cx, a.cc = softcap_consts(c.scale, c.softcap).cc;
     const dim3 grid((unsigned)p.grid), block(256);
     const bool trv = tuning().attn_trv != 0;
-#define GQ_PREFILL(KV, D, TRV) (p.rows == 128 ? attn_prefill_kernel<KV, D, 2, TRV><<<grid, block, 0, s>>>(a) : attn_prefill_kernel<KV, D, 1, TRV><<<grid, block, 0, s>>>(a))
-    if (kv == 0 && c.D == 128) trv ? GQ_PREFILL(0, 128, true) : GQ_PREFILL(0, 128, false);
-    else if (kv == 0) trv ? GQ_PREFILL(0, 64, true) : GQ_PREFILL(0, 64, false);
-    else if (c.D == 128) GQ_PREFILL(1, 128, false);
-    else GQ_PREFILL(1, 64, false);
+#define GQ_PREFILL_RT(KV, D, RT, TRV) (cap ? attn_prefill_kernel<KV, D, RT, TRV, true><<<grid, block, 0, s>>>(a) : attn_prefill_kernel<KV, D, RT, TRV, false><<<grid, block, 0, s>>>(a))
+#define GQ_PREFILL(KV, D, TRV) (p.rows == 128 ? GQ_PREFILL_RT(KV, D, 2, TRV) : GQ_PREFILL_RT(KV, D, 1, TRV))
+#define GQ_PREFILL_D(KV, TRV) (c.D == 256 ? GQ_PREFILL(KV, 256, TRV) : c.D == 128 ? GQ_PREFILL(KV, 128, TRV) : GQ_PREFILL(KV, 64, TRV))
+    if (kv == 0) trv ? GQ_PREFILL_D(0, true) : GQ_PREFILL_D(0, false);
+    else GQ_PREFILL_D(1, false);
+#undef GQ_PREFILL_D
 #undef GQ_PREFILL
+#undef GQ_PREFILL_RT
     return hipGetLastError();
 }
 

@@ -103,10 +103,10 @@ hipError_t launch_rmsnorm(const NormArgs &a, int64_t N, hipStream_t s);
 // second product, kAttnRing the least that keeps a tile in flight under the current one (at fp16,
 // D = 128 it fills the LDS), kAttnMaxW bounds the partials a row's combine reads.
 constexpr int kAttnTile = 32;  // keys per tile (one wave's unit of work)
-constexpr int kAttnRing = 2;   // LDS ring slots per wave (K tile + V tile each)
+constexpr int kAttnRing = 2;   // LDS ring slots per wave (K tile + V tile each); D = 256: one slot, refilled by halves
 constexpr int kAttnMaxW = 64;  // workgroups per (sequence, kv head), at most
 struct AttnPlan {
-    bool ok = false;           // D in {64, 128}, n_head % n_kv_head == 0, R <= 32
+    bool ok = false;           // D in {64, 128, 256}, n_head % n_kv_head == 0, R <= 32
     int R = 0, W = 0, grid = 0;
     size_t workspace_bytes = 0;
 };
@@ -116,8 +116,11 @@ struct AttnCall {
     void *O, *workspace;
     int64_t ldq, ldo, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D;
     float scale;
+    int64_t window = 0;   // gq_attn_opts: the sliding window in positions (0: unbounded) ...
+    float softcap = 0.f;  // ... and the cap of cap * tanh(score / cap) (0: none)
 };
-AttnPlan plan_attn(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D);
+// window: W is chosen for the tiles that window + N positions can span, not for a whole cache
+AttnPlan plan_attn(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int64_t window = 0);
 hipError_t launch_attn_decode(int kv, const AttnCall &c, const AttnPlan &p, hipStream_t s);
 // Prefill attention over the same caches (attn_prefill.hip; gq_attn_prefill): B * n_kv_head * nblk
 // workgroups, each a block of `rows` consecutive query rows of one (sequence, kv head) walking the
@@ -126,9 +129,11 @@ hipError_t launch_attn_decode(int kv, const AttnCall &c, const AttnPlan &p, hipS
 // 64 otherwise.  Neither constant was measured against another value: two slots are the least that
 // keep a tile in flight under the current one, and 64 keys x 2 slots fill 64 KiB at fp16, D = 128.
 constexpr int kPrefillTile = 64;  // keys per ring slot (two 32-key steps of the second product)
+// D = 256: one 32-key step per slot, so that the fp16 ring stays at 64 KiB and two workgroups fit a compute unit
+constexpr int prefill_tile(int64_t D) { return D == 256 ? kPrefillTile / 2 : kPrefillTile; }
 constexpr int kPrefillSlots = 2;  // LDS ring slots per workgroup (K tile + V tile each)
 struct PrefillPlan {
-    bool ok = false;           // D in {64, 128}, n_head % n_kv_head == 0, the grid below 2^31
+    bool ok = false;           // D in {64, 128, 256}, n_head % n_kv_head == 0, the grid below 2^31
     int rows = 0, nblk = 0;    // query rows per workgroup, row blocks per (sequence, kv head)
     int64_t grid = 0;
 };

@@ -1,5 +1,6 @@
 // gq_capi.hip -- the C ABI (include/gguf_mmq.h): argument checks, workspace carving,
 // path selection (decode GEMV vs MFMA GEMM) and launches.  Stateless and re-entrant.
+#include <cfloat>
 #include <climits>
 #include <cstdio>
 #include <dlfcn.h>
@@ -1488,7 +1489,7 @@ static int check_kv_cache(gq_kv_type kv, int64_t tok_stride, int64_t head_stride
                     (long long)N, (long long)n_head, (long long)n_kv_head, (long long)D, (long long)capacity);
     empty = B == 0 || N == 0 || n_head == 0;
     if (empty) return GQ_OK;
-    if (D != 64 && D != 128) return fail(GQ_EUNSUPPORTED, "D=%lld is neither 64 nor 128", (long long)D);
+    if (D != 64 && D != 128 && D != 256) return fail(GQ_EUNSUPPORTED, "D=%lld is none of 64, 128, 256", (long long)D);
     if (n_kv_head == 0 || n_head % n_kv_head != 0)
         return fail(GQ_EUNSUPPORTED, "n_head=%lld is not a multiple of n_kv_head=%lld", (long long)n_head, (long long)n_kv_head);
     if (decode && N * (n_head / n_kv_head) > 32)
@@ -1506,19 +1507,45 @@ static int check_kv_cache(gq_kv_type kv, int64_t tok_stride, int64_t head_stride
     return GQ_OK;
 }
 
-size_t gq_attn_decode_workspace_size(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D)
+// gq_attn_opts: NULL is {0, 0.0f}; a negative window, a negative or non-finite cap: GQ_EINVAL (before every other check)
+static int check_attn_opts(const gq_attn_opts *opts, int64_t &window, float &softcap)
 {
-    return gq::plan_attn(B, N, n_head, n_kv_head, D).workspace_bytes; // (0: empty or not a supported shape)
+    window = opts ? opts->window : 0, softcap = opts ? opts->softcap : 0.f;
+    if (window < 0) return fail(GQ_EINVAL, "window=%lld is negative (0: unbounded)", (long long)window);
+    if (!(softcap >= 0.f) || softcap > FLT_MAX) return fail(GQ_EINVAL, "softcap=%g is negative or not finite (0: none)", (double)softcap);
+    // (scale / softcap must stay finite in fp32 for any sane scale)
+    if (softcap > 0.f && softcap < 1e-6f) return fail(GQ_EINVAL, "softcap=%g is below 1e-6: not a cap (0: none)", (double)softcap);
+    return GQ_OK;
 }
 
-int gq_debug_attn_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *tile, int *W)
+size_t gq_attn_decode_workspace_size_ex(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, const gq_attn_opts *opts)
+{
+    if (opts && opts->window < 0) return 0;
+    return gq::plan_attn(B, N, n_head, n_kv_head, D, opts ? opts->window : 0).workspace_bytes; // (0: empty or not a supported shape)
+}
+
+size_t gq_attn_decode_workspace_size(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D)
+{
+    return gq_attn_decode_workspace_size_ex(B, N, n_head, n_kv_head, D, nullptr);
+}
+
+int gq_debug_attn_plan_ex(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, const gq_attn_opts *opts, int *tile,
+                          int *W)
 {
     g_err.clear();
-    const gq::AttnPlan p = gq::plan_attn(B, N, n_head, n_kv_head, D);
+    int64_t window;
+    float softcap;
+    if (const int rc = check_attn_opts(opts, window, softcap)) return rc;
+    const gq::AttnPlan p = gq::plan_attn(B, N, n_head, n_kv_head, D, window);
     if (!p.ok) return fail(GQ_EUNSUPPORTED, "not a decode-attention shape");
     if (tile) *tile = gq::kAttnTile;
     if (W) *W = p.W;
     return GQ_OK;
+}
+
+int gq_debug_attn_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *tile, int *W)
+{
+    return gq_debug_attn_plan_ex(B, N, n_head, n_kv_head, D, nullptr, tile, W);
 }
 
 int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
@@ -1526,8 +1553,20 @@ int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, co
                    float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *workspace,
                    size_t workspace_bytes, void *stream)
 {
+    return gq_attn_decode_ex(kv, Q, ldq, Kc, Vc, tok_stride, head_stride, seq_stride, kv_len, capacity, O, ldo, scale, B, N, n_head,
+                             n_kv_head, D, workspace, workspace_bytes, nullptr, stream);
+}
+
+int gq_attn_decode_ex(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                      int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                      float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *workspace,
+                      size_t workspace_bytes, const gq_attn_opts *opts, void *stream)
+{
     g_err.clear();
     bool empty;
+    int64_t window;
+    float softcap;
+    if (const int orc = check_attn_opts(opts, window, softcap)) return orc;
     // (the sizes first: a negative one has no row length to hold ldq against)
     if (B >= 0 && N >= 0 && n_head > 0 && D >= 0 && B * N > 0) {
         if (!Q || !Kc || !Vc || !kv_len || !O)
@@ -1537,30 +1576,52 @@ int gq_attn_decode(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, co
     }
     const int rc = check_kv_cache(kv, tok_stride, head_stride, seq_stride, capacity, B, N, n_head, n_kv_head, D, true, empty);
     if (rc != GQ_OK || empty) return rc;
-    const gq::AttnPlan p = gq::plan_attn(B, N, n_head, n_kv_head, D);
+    if (window >= capacity) window = 0; // it bounds nothing: the plan and the kernels see one notion of a window
+    const gq::AttnPlan p = gq::plan_attn(B, N, n_head, n_kv_head, D, window);
     if (!workspace || workspace_bytes < p.workspace_bytes) return fail_workspace(workspace, workspace_bytes, p.workspace_bytes);
     if (((uintptr_t)workspace & 15) != 0) return fail(GQ_EINVAL, "the workspace must be 16-byte aligned");
     const gq::AttnCall c{Q, Kc, Vc, kv_len, O, workspace, ldq, ldo, tok_stride, head_stride, seq_stride, capacity,
-                         B, N, n_head, n_kv_head, D, scale};
+                         B, N, n_head, n_kv_head, D, scale, window, softcap};
     return hip_rc(gq::launch_attn_decode(kv == GQ_KV_Q8_0, c, p, (hipStream_t)stream), "attn_decode");
+}
+
+int gq_debug_attn_prefill_plan_ex(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, const gq_attn_opts *opts,
+                                  int *rows, int *tile)
+{
+    g_err.clear();
+    int64_t window;
+    float softcap;
+    if (const int rc = check_attn_opts(opts, window, softcap)) return rc;
+    const gq::PrefillPlan p = gq::plan_attn_prefill(B, N, n_head, n_kv_head, D); // (the options change no row block)
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "not a prefill-attention shape");
+    if (rows) *rows = p.rows;
+    if (tile) *tile = gq::prefill_tile(D);
+    return GQ_OK;
 }
 
 int gq_debug_attn_prefill_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *rows, int *tile)
 {
-    g_err.clear();
-    const gq::PrefillPlan p = gq::plan_attn_prefill(B, N, n_head, n_kv_head, D);
-    if (!p.ok) return fail(GQ_EUNSUPPORTED, "not a prefill-attention shape");
-    if (rows) *rows = p.rows;
-    if (tile) *tile = gq::kPrefillTile;
-    return GQ_OK;
+    return gq_debug_attn_prefill_plan_ex(B, N, n_head, n_kv_head, D, nullptr, rows, tile);
 }
 
 int gq_attn_prefill(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
                     int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
                     float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *stream)
 {
+    return gq_attn_prefill_ex(kv, Q, ldq, Kc, Vc, tok_stride, head_stride, seq_stride, kv_len, capacity, O, ldo, scale, B, N, n_head,
+                              n_kv_head, D, nullptr, stream);
+}
+
+int gq_attn_prefill_ex(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                       int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                       float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, const gq_attn_opts *opts,
+                       void *stream)
+{
     g_err.clear();
     bool empty;
+    int64_t window;
+    float softcap;
+    if (const int orc = check_attn_opts(opts, window, softcap)) return orc;
     // (the sizes first: a negative one has no row length to hold ldq against)
     if (B >= 0 && N >= 0 && n_head > 0 && D >= 0 && B * N > 0) {
         if (!Q || !Kc || !Vc || !kv_len || !O)
@@ -1573,7 +1634,7 @@ int gq_attn_prefill(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, c
     const gq::PrefillPlan p = gq::plan_attn_prefill(B, N, n_head, n_kv_head, D);
     if (!p.ok) return fail(GQ_EUNSUPPORTED, "B * n_kv_head * ceil(N * n_head / n_kv_head / %d) workgroups are 2^31 or more", p.rows);
     const gq::AttnCall c{Q, Kc, Vc, kv_len, O, nullptr, ldq, ldo, tok_stride, head_stride, seq_stride, capacity,
-                         B, N, n_head, n_kv_head, D, scale};
+                         B, N, n_head, n_kv_head, D, scale, window >= capacity ? 0 : window, softcap};
     return hip_rc(gq::launch_attn_prefill(kv == GQ_KV_Q8_0, c, p, (hipStream_t)stream), "attn_prefill");
 }
 

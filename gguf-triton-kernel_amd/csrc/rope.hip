@@ -28,6 +28,13 @@
 // ds_bpermute reads of the packed fp16 pair, so one quantizer serves every n_rot.  The arithmetic is
 // qblk::q8_scale / q8_code, q8_block's own steps: gq_kv_append's bytes of the same fp16 values.
 //
+// D = 256 (Gemma; rope_append256_kernel).  A head is 128 lane jobs, so a wave takes one head with TWO
+// jobs per lane: virtual lanes l and l + 64 of the layouts above (lane l owns rotation pairs l and
+// l + 64 where they exist).  Everything per lane comes in twos -- the angle, the norm weights, the
+// element indices -- the norm's sum adds the lane's two partial sums before the 64-lane butterfly, a
+// Q8_0 block is still 16 consecutive lanes of one job, and the NEOX-to-NORM gather reads both jobs of
+// the holding lane and picks one.  Same grid, same arithmetic, same bytes.
+//
 // No LDS, no scratch, no atomics, no wait between workgroups.  In place (Qout == Q) is safe: a lane
 // writes the two elements it read.
 #include "gguf_blocks.hpp"
@@ -172,6 +179,122 @@ __global__ __launch_bounds__(256) void rope_append_kernel(const RopeArgs a)
     }
 }
 
+// D = 256: one wave per head, two jobs (virtual lanes lane and lane + 64) per lane -- the file header has the layout
+template <int KV, int MODE, bool HAS_NORM>
+__global__ __launch_bounds__(256) void rope_append256_kernel(const RopeArgs a)
+{
+    constexpr int D = 256, HL = 128;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = a.n_rot >> 1, J = a.n_head + 2 * a.n_kv;
+    int li[2], r0[2], r1[2], from0[2], from1[2], slot0[2], slot1[2];
+    bool rot[2];
+    float f[2], wq0[2], wq1[2], wk0[2], wk1[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        li[s] = lane + 64 * s, rot[s] = li[s] < h;
+        r0[s] = 2 * li[s], r1[s] = 2 * li[s] + 1;
+        if (MODE == 1) r0[s] = rot[s] ? li[s] : li[s] + h, r1[s] = rot[s] ? li[s] + h : li[s] + HL;
+        // NEOX: the virtual lanes that hold elements 2 li and 2 li + 1, and the half of their pair
+        from0[s] = from1[s] = li[s], slot0[s] = 0, slot1[s] = 1;
+        if (MODE == 1 && KV == 1) {
+            auto holder = [&](int e, int &ln, int &slot) {
+                if (e < 2 * h) ln = e < h ? e : e - h, slot = e >= h;
+                else ln = e < HL + h ? e - h : e - HL, slot = e >= HL + h;
+            };
+            holder(2 * li[s], from0[s], slot0[s]);
+            holder(2 * li[s] + 1, from1[s], slot1[s]);
+        }
+        f[s] = rot[s] ? a.inv_freq[li[s]] : 0.f;
+        wq0[s] = wq1[s] = wk0[s] = wk1[s] = 1.f;
+        if (HAS_NORM) wq0[s] = a.wq[r0[s]], wq1[s] = a.wq[r1[s]], wk0[s] = a.wk[r0[s]], wk1[s] = a.wk[r1[s]];
+    }
+
+    for (int64_t t = blockIdx.x; t < a.T; t += gridDim.x) {
+        const int b = (int)(t / a.N), i = (int)(t - (int64_t)b * a.N);
+        const int p = a.kv_len[b] - a.N + i;
+        const bool inside = p >= 0 && p < a.capacity; // (outside: the caller's error, no cache row written)
+        float c[2], sn[2];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) rope_cs(p, f[s], a.mscale, c[s], sn[s]);
+        const int64_t crow = (int64_t)b * a.seq_stride + (int64_t)p * a.tok_stride;
+        for (int k = 0; k < a.passes; ++k) {
+            const int j = ((int)blockIdx.y * a.passes + k) * 4 + wave; // (wave-uniform, as is every branch below)
+            if (j >= J) continue;
+            const bool isq = j < a.n_head, isv = j >= a.n_head + a.n_kv;
+            const int hd = isq ? j : (isv ? j - a.n_head - a.n_kv : j - a.n_head);
+            const uint16_t *src = (isq ? a.Q + t * a.ldq : (isv ? a.Vn + t * a.ldv : a.Kn + t * a.ldk)) + (int64_t)hd * D;
+            const bool adj = MODE == 0 || isv;
+            int e0[2], e1[2];
+            uint32_t o[2];
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                e0[s] = isv ? 2 * li[s] : r0[s], e1[s] = isv ? 2 * li[s] + 1 : r1[s];
+                o[s] = load2(src, e0[s], e1[s], adj && a.rows4);
+            }
+            if (!isv) {
+                float y0[2], y1[2];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) y0[s] = h2f(o[s] & 0xffff), y1[s] = h2f(o[s] >> 16);
+                if (HAS_NORM) {
+                    float ss = __builtin_fmaf(y1[0], y1[0], y0[0] * y0[0]) + __builtin_fmaf(y1[1], y1[1], y0[1] * y0[1]);
+#pragma unroll
+                    for (int m = 1; m < 64; m <<= 1) ss += __shfl_xor(ss, m, 64);
+                    const float scale = 1.0f / sqrtf(ss * (1.0f / D) + a.eps);
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        y0[s] = (y0[s] * scale) * (isq ? wq0[s] : wk0[s]);
+                        y1[s] = (y1[s] * scale) * (isq ? wq1[s] : wk1[s]);
+                    }
+                }
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const float o0 = rot[s] ? y0[s] * c[s] - y1[s] * sn[s] : y0[s], o1 = rot[s] ? y0[s] * sn[s] + y1[s] * c[s] : y1[s];
+                    o[s] = (uint32_t)f2h_bits(o0) | ((uint32_t)f2h_bits(o1) << 16);
+                }
+            }
+            if (isq) {
+#pragma unroll
+                for (int s = 0; s < 2; ++s) store2(a.Qo + t * a.ldqo + (int64_t)hd * D, e0[s], e1[s], adj && a.rows4, o[s]);
+                continue;
+            }
+            uint8_t *dst = (isv ? a.Vc : a.Kc) + crow + (int64_t)hd * a.head_stride;
+            if (KV == 0) {
+                if (inside) {
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) store2((uint16_t *)dst, e0[s], e1[s], adj && a.cache4, o[s]);
+                }
+                continue;
+            }
+            if (MODE == 1 && !isv) { // into the NORM layout: job s gets elements (2 li, 2 li + 1) from the jobs that hold them
+                uint32_t n[2];
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const uint32_t a0 = __shfl(o[0], from0[s] & 63, 64), a1 = __shfl(o[1], from0[s] & 63, 64);
+                    const uint32_t b0 = __shfl(o[0], from1[s] & 63, 64), b1 = __shfl(o[1], from1[s] & 63, 64);
+                    const uint32_t g0 = from0[s] >> 6 ? a1 : a0, g1 = from1[s] >> 6 ? b1 : b0;
+                    n[s] = ((slot0[s] ? g0 >> 16 : g0) & 0xffff) | ((slot1[s] ? g1 >> 16 : g1 & 0xffff) << 16);
+                }
+                o[0] = n[0], o[1] = n[1];
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const uint16_t x0 = (uint16_t)o[s], x1 = (uint16_t)(o[s] >> 16);
+                float amax = fmaxf(fabsf(h2f((uint32_t)x0)), fabsf(h2f((uint32_t)x1))); // (fmaxf drops a NaN, as q8_block's max does)
+#pragma unroll
+                for (int m = 1; m < 16; m <<= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
+                const uint16_t d = qblk::q8_scale<false>(amax);
+                const float div = gq::h2f(d);
+                const uint32_t codes = (uint32_t)(uint8_t)qblk::q8_code(x0, div) | ((uint32_t)(uint8_t)qblk::q8_code(x1, div) << 8);
+                if (inside) {
+                    uint16_t *blk = (uint16_t *)(dst + 34 * (li[s] >> 4));
+                    if ((li[s] & 15) == 0) blk[0] = d;
+                    blk[1 + (li[s] & 15)] = (uint16_t)codes;
+                }
+            }
+        }
+    }
+}
+
 } // namespace
 
 hipError_t launch_rope_append(int kv, int mode, const RopeCall &c, hipStream_t s)
@@ -188,7 +311,7 @@ hipError_t launch_rope_append(int kv, int mode, const RopeCall &c, hipStream_t s
               ((c.ldq | c.ldk | c.ldv | c.ldqo) & 1) == 0;
     a.cache4 = (((uintptr_t)c.Kc | (uintptr_t)c.Vc | (uintptr_t)c.tok_stride | (uintptr_t)c.head_stride | (uintptr_t)c.seq_stride) & 3) == 0;
     // the shares of a token's head jobs: as many as fill the chip twice over, at most one pass each
-    const int64_t J = c.n_head + 2 * c.n_kv_head, per_pass = 4 * (128 / c.D), cus = num_cus();
+    const int64_t J = c.n_head + 2 * c.n_kv_head, per_pass = c.D >= 128 ? 4 : 8, cus = num_cus();
     const int64_t ymax = (J + per_pass - 1) / per_pass, want = (2 * cus + a.T - 1) / a.T;
     const int64_t Y = want < 1 ? 1 : (want > ymax ? ymax : want);
     a.passes = (int)((ymax + Y - 1) / Y);
@@ -197,10 +320,13 @@ hipError_t launch_rope_append(int kv, int mode, const RopeCall &c, hipStream_t s
     const bool norm = c.q_norm_w != nullptr;
 #define GQ_ROPE(KV, D, MODE) \
     (norm ? rope_append_kernel<KV, D, MODE, true><<<grid, block, 0, s>>>(a) : rope_append_kernel<KV, D, MODE, false><<<grid, block, 0, s>>>(a))
-#define GQ_ROPE_D(KV, MODE) (c.D == 128 ? GQ_ROPE(KV, 128, MODE) : GQ_ROPE(KV, 64, MODE))
+#define GQ_ROPE256(KV, MODE) \
+    (norm ? rope_append256_kernel<KV, MODE, true><<<grid, block, 0, s>>>(a) : rope_append256_kernel<KV, MODE, false><<<grid, block, 0, s>>>(a))
+#define GQ_ROPE_D(KV, MODE) (c.D == 256 ? GQ_ROPE256(KV, MODE) : c.D == 128 ? GQ_ROPE(KV, 128, MODE) : GQ_ROPE(KV, 64, MODE))
     if (kv == 0) mode == 0 ? GQ_ROPE_D(0, 0) : GQ_ROPE_D(0, 1);
     else mode == 0 ? GQ_ROPE_D(1, 0) : GQ_ROPE_D(1, 1);
 #undef GQ_ROPE_D
+#undef GQ_ROPE256
 #undef GQ_ROPE
     return hipGetLastError();
 }

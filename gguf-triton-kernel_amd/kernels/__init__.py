@@ -15,12 +15,16 @@ Beyond the reference, decode and prefill attention over an fp16 or Q8_0 KV cache
 
     from kernels import KVCache, attn_decode, attn_prefill, kv_append
 
+with a sliding window and a logit soft-cap per layer, at head dims 64, 128 and 256 (Gemma):
+
+    from kernels import attn_options           # cache.attend(q, **attn_options(meta, layer))
+
 and the rotary embedding (with the per-head q/k norm) fused into the append:
 
     from kernels import RoPE, rope_append
 """
 _LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib", "RoPE": "attention",
-         "rope_append": "_lib"}
+         "rope_append": "_lib", "attn_options": "attention"}
 __all__ = list(_LAZY)
 
 

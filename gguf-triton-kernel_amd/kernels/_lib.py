@@ -108,6 +108,14 @@ SIGNATURES = {
     "gq_attn_prefill": ([_I, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64,
                          _I64, _P], _I),
     "gq_debug_attn_prefill_plan": ([_I64, _I64, _I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
+    "gq_attn_decode_workspace_size_ex": ([_I64, _I64, _I64, _I64, _I64, _P], _SZ),
+    "gq_attn_decode_ex": ([_I, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64,
+                           _I64, _P, _SZ, _P, _P], _I),
+    "gq_attn_prefill_ex": ([_I, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64,
+                            _I64, _P, _P], _I),
+    "gq_debug_attn_plan_ex": ([_I64, _I64, _I64, _I64, _I64, _P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], _I),
+    "gq_debug_attn_prefill_plan_ex": ([_I64, _I64, _I64, _I64, _I64, _P, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int)], _I),
     "gq_kv_append": ([_I, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_rope_append": ([_I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64,
                         ctypes.c_float, _P, _P, ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
@@ -988,15 +996,25 @@ def kv_row_bytes(kind: str, D: int) -> int:
     return 2 * D if kind == "f16" else 34 * (D // 32)
 
 
-def attn_plan(B: int, N: int, n_head: int, n_kv_head: int, D: int):
-    """(keys per tile, workgroups W per (sequence, kv head)) of an attn_decode call (gq_debug_attn_plan)."""
+class AttnOpts(ctypes.Structure):  # gq_attn_opts
+    _fields_ = [("window", ctypes.c_int64), ("softcap", ctypes.c_float)]
+
+
+def _attn_opts(window: int, softcap: float):
+    """gq_attn_opts * for the _ex entries: the sliding window in positions (0: unbounded) and the cap of
+    cap * tanh(score / cap) (0: none)."""
+    return ctypes.byref(AttnOpts(int(window), float(softcap)))
+
+
+def attn_plan(B: int, N: int, n_head: int, n_kv_head: int, D: int, window: int = 0, softcap: float = 0.0):
+    """(keys per tile, workgroups W per (sequence, kv head)) of an attn_decode call (gq_debug_attn_plan_ex)."""
     tile, W = ctypes.c_int(), ctypes.c_int()
-    _check(lib().gq_debug_attn_plan(B, N, n_head, n_kv_head, D, ctypes.byref(tile), ctypes.byref(W)))
+    _check(lib().gq_debug_attn_plan_ex(B, N, n_head, n_kv_head, D, _attn_opts(window, softcap), ctypes.byref(tile), ctypes.byref(W)))
     return tile.value, W.value
 
 
-def attn_workspace_size(B: int, N: int, n_head: int, n_kv_head: int, D: int) -> int:
-    return int(lib().gq_attn_decode_workspace_size(B, N, n_head, n_kv_head, D))
+def attn_workspace_size(B: int, N: int, n_head: int, n_kv_head: int, D: int, window: int = 0, softcap: float = 0.0) -> int:
+    return int(lib().gq_attn_decode_workspace_size_ex(B, N, n_head, n_kv_head, D, _attn_opts(window, softcap)))
 
 
 def _kv_rows(t: torch.Tensor, name: str, rows: int, cols: int, dev):
@@ -1018,11 +1036,14 @@ def _kv_caches(Kc, Vc, kv_len, B, dev):
 
 def attn_decode(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, strides, kv_len: torch.Tensor,
                 capacity: int, B: int, N: int, n_head: int, n_kv_head: int, D: int, workspace: torch.Tensor,
-                scale: float | None = None, out: torch.Tensor | None = None, kv_offset: int = 0) -> torch.Tensor:
-    """Causal attention of the N new tokens of B sequences over their KV caches (gq_attn_decode):
+                scale: float | None = None, out: torch.Tensor | None = None, kv_offset: int = 0, window: int = 0,
+                softcap: float = 0.0) -> torch.Tensor:
+    """Causal attention of the N new tokens of B sequences over their KV caches (gq_attn_decode_ex):
     q fp16 (B*N, n_head*D) -> fp16 (B*N, n_head*D).  Kc / Vc: the cache tensors (any dtype; the rows
     start kv_offset bytes in), strides = (tok, head, seq) in bytes, kv_len int32 (B) on the device --
-    the lengths including the new tokens.  scale: 1/sqrt(D) when None.  No host sync, no fallback."""
+    the lengths including the new tokens.  scale: 1/sqrt(D) when None.  window > 0: a token at position
+    p attends positions p - window + 1 .. p only; softcap > 0: scores pass through softcap * tanh(s /
+    softcap).  The workspace is sized for the same window.  No host sync, no fallback."""
     _require_device(q, "q")
     dev = q.device
     ldq = _kv_rows(q, "q", B * N, n_head * D, dev)
@@ -1033,24 +1054,25 @@ def attn_decode(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, 
     _check_workspace(workspace, 0, dev)
     tok, head, seq = (int(s) for s in strides)
     with torch.cuda.device(dev):
-        _check(lib().gq_attn_decode(KV_KINDS[kind], q.data_ptr(), ldq, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset,
-                                    tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
-                                    float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D,
-                                    workspace.data_ptr(), workspace.numel(), _stream(dev)))
+        _check(lib().gq_attn_decode_ex(KV_KINDS[kind], q.data_ptr(), ldq, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset,
+                                       tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
+                                       float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D,
+                                       workspace.data_ptr(), workspace.numel(), _attn_opts(window, softcap), _stream(dev)))
     return out
 
 
-def attn_prefill_plan(B: int, N: int, n_head: int, n_kv_head: int, D: int):
-    """(query rows per workgroup, keys per LDS tile) of an attn_prefill call (gq_debug_attn_prefill_plan)."""
+def attn_prefill_plan(B: int, N: int, n_head: int, n_kv_head: int, D: int, window: int = 0, softcap: float = 0.0):
+    """(query rows per workgroup, keys per LDS tile) of an attn_prefill call (gq_debug_attn_prefill_plan_ex)."""
     rows, tile = ctypes.c_int(), ctypes.c_int()
-    _check(lib().gq_debug_attn_prefill_plan(B, N, n_head, n_kv_head, D, ctypes.byref(rows), ctypes.byref(tile)))
+    _check(lib().gq_debug_attn_prefill_plan_ex(B, N, n_head, n_kv_head, D, _attn_opts(window, softcap), ctypes.byref(rows),
+                                               ctypes.byref(tile)))
     return rows.value, tile.value
 
 
 def attn_prefill(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor, strides, kv_len: torch.Tensor,
                  capacity: int, B: int, N: int, n_head: int, n_kv_head: int, D: int, scale: float | None = None,
-                 out: torch.Tensor | None = None, kv_offset: int = 0) -> torch.Tensor:
-    """attn_decode for a prompt or a chunk of one (gq_attn_prefill): any N <= capacity, one launch, no
+                 out: torch.Tensor | None = None, kv_offset: int = 0, window: int = 0, softcap: float = 0.0) -> torch.Tensor:
+    """attn_decode for a prompt or a chunk of one (gq_attn_prefill_ex): any N <= capacity, one launch, no
     workspace.  Arguments as attn_decode's.  No host sync, no fallback."""
     _require_device(q, "q")
     dev = q.device
@@ -1061,9 +1083,10 @@ def attn_prefill(kind: str, q: torch.Tensor, Kc: torch.Tensor, Vc: torch.Tensor,
     ldo = _kv_rows(out, "out", B * N, n_head * D, dev)
     tok, head, seq = (int(s) for s in strides)
     with torch.cuda.device(dev):
-        _check(lib().gq_attn_prefill(KV_KINDS[kind], q.data_ptr(), ldq, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset,
-                                     tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
-                                     float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D, _stream(dev)))
+        _check(lib().gq_attn_prefill_ex(KV_KINDS[kind], q.data_ptr(), ldq, Kc.data_ptr() + kv_offset, Vc.data_ptr() + kv_offset,
+                                        tok, head, seq, kv_len.data_ptr(), capacity, out.data_ptr(), ldo,
+                                        float(D ** -0.5 if scale is None else scale), B, N, n_head, n_kv_head, D,
+                                        _attn_opts(window, softcap), _stream(dev)))
     return out
 
 

@@ -12,6 +12,11 @@ Gemma-3 and OLMo-2) applied on the way -- one launch instead of append, no posit
     q = cache.append_rope(q, k, v, rope)                        # gq_rope_append; q, k, v may be slices of one qkv buffer
     a = cache.attend(q)
 
+Gemma-2/3, Mistral, Cohere2 and Phi-3 layers with a sliding window, and Gemma-2's soft-capped scores:
+
+    opts = attn_options(meta, layer)                            # {"window": 4096, "softcap": 50.0} from the file's metadata
+    a = cache.attend(q, **opts)                                 # gq_attn_decode_ex / gq_attn_prefill_ex; D = 256 is served
+
 append advances the lengths on the device and writes the rows there (gq_kv_append; Q8_0 blocks with
 the weight producer's bytes); attend is gq_attn_decode up to 32 query rows per kv head and
 gq_attn_prefill (a prompt, or a chunk of one after a prefix) beyond.  Neither syncs the host or
@@ -104,6 +109,23 @@ class RoPE:
                    float(get("attention.layer_norm_rms_epsilon", 1e-6)))
 
 
+# local layers per global one where the file has no {arch}.attention.sliding_window_pattern (llama.cpp's defaults)
+SWA_PATTERN = {"gemma2": 2, "gemma3": 6}
+
+
+def attn_options(meta: dict, layer: int) -> dict:
+    """KVCache.attend's window and softcap for one layer from a GGUF file's metadata:
+    {arch}.attention.sliding_window and {arch}.attn_logit_softcapping (0 where the file has none).  With
+    a pattern n -- {arch}.attention.sliding_window_pattern, else 2 for gemma2 and 6 for gemma3 -- layer il
+    is windowed unless il % n == n - 1; any other architecture with a window has it on every layer."""
+    arch = meta["general.architecture"]
+    window = int(meta.get(f"{arch}.attention.sliding_window", 0) or 0)
+    n = meta.get(f"{arch}.attention.sliding_window_pattern", SWA_PATTERN.get(arch))
+    if window and n is not None and layer % int(n) == int(n) - 1:
+        window = 0
+    return {"window": window, "softcap": float(meta.get(f"{arch}.attn_logit_softcapping", 0.0) or 0.0)}
+
+
 class KVCache:
     """The K and V caches of one layer, token-major as llama.cpp keeps them: row (b, t, h) at byte
     ((b*capacity + t)*n_kv_head + h) * row_bytes.  kv_len: int32 (B) on the device, the tokens cached
@@ -112,8 +134,8 @@ class KVCache:
     def __init__(self, B: int, capacity: int, n_kv_head: int, D: int, kind: str = "f16", device="cuda"):
         if kind not in _lib.KV_KINDS:
             raise ValueError(f"kind={kind!r} is neither 'f16' nor 'q8_0'")
-        if D not in (64, 128):
-            raise ValueError(f"D={D} is neither 64 nor 128")
+        if D not in (64, 128, 256):
+            raise ValueError(f"D={D} is none of 64, 128, 256")
         if min(B, capacity, n_kv_head) < 1:
             raise ValueError("B, capacity and n_kv_head must be positive")
         self.B, self.capacity, self.n_kv_head, self.D, self.kind = B, capacity, n_kv_head, D, kind
@@ -122,7 +144,7 @@ class KVCache:
         self.k = torch.zeros(B * capacity * n_kv_head * rb, dtype=torch.uint8, device=device)
         self.v = torch.zeros_like(self.k)
         self.kv_len = torch.zeros(B, dtype=torch.int32, device=device)
-        self._ws = {}  # (N, n_head) -> workspace
+        self._ws = {}  # (N, n_head, window, softcap) -> workspace
         self._n = 0    # the last append's token count: attend's N
 
     def reset(self):
@@ -157,8 +179,11 @@ class KVCache:
         self._n = N
         return out
 
-    def attend(self, q: torch.Tensor, scale: float | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
-        """q: fp16 (B*N, n_head*D), the queries of the N tokens last appended -> (B*N, n_head*D) fp16."""
+    def attend(self, q: torch.Tensor, scale: float | None = None, out: torch.Tensor | None = None, window: int = 0,
+               softcap: float = 0.0) -> torch.Tensor:
+        """q: fp16 (B*N, n_head*D), the queries of the N tokens last appended -> (B*N, n_head*D) fp16.
+        window > 0: each token attends its last `window` positions only; softcap > 0: softcap * tanh(s /
+        softcap) on the scaled scores (attn_options reads both from a file's metadata)."""
         N = q.shape[0] // self.B
         if N < 1 or N * self.B != q.shape[0] or N != self._n:
             raise ValueError(f"q has {q.shape[0]} rows; the last append wrote {self._n} tokens for each of {self.B} sequences")
@@ -167,10 +192,11 @@ class KVCache:
         n_head = q.shape[1] // self.D
         if N * (n_head // self.n_kv_head) > 32:  # beyond decode's rows per kv head: the prefill kernel, no workspace
             return _lib.attn_prefill(self.kind, q, self.k, self.v, self.strides, self.kv_len, self.capacity, self.B, N, n_head,
-                                     self.n_kv_head, self.D, scale, out)
-        ws = self._ws.get((N, n_head))
+                                     self.n_kv_head, self.D, scale, out, window=window, softcap=softcap)
+        key = (N, n_head, window, softcap)
+        ws = self._ws.get(key)
         if ws is None:
-            need = _lib.attn_workspace_size(self.B, N, n_head, self.n_kv_head, self.D)
-            ws = self._ws[(N, n_head)] = torch.empty(max(need, 16), dtype=torch.uint8, device=self.k.device)
+            need = _lib.attn_workspace_size(self.B, N, n_head, self.n_kv_head, self.D, window, softcap)
+            ws = self._ws[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=self.k.device)
         return _lib.attn_decode(self.kind, q, self.k, self.v, self.strides, self.kv_len, self.capacity, self.B, N, n_head,
-                                self.n_kv_head, self.D, ws, scale, out)
+                                self.n_kv_head, self.D, ws, scale, out, window=window, softcap=softcap)

@@ -31,6 +31,7 @@
  *   gq_rmsnorm_prepare                  the same, written as gq_act_prepare's q8_1 activations
  *   gq_attn_decode                      decode attention over an fp16 or Q8_0 KV cache, grouped query heads
  *   gq_attn_prefill                     the same for a prompt or a chunk of one: any number of new tokens, one launch
+ *   gq_attn_decode_ex, gq_attn_prefill_ex  the same with a sliding window and a logit soft-cap (Gemma, Mistral, Phi-3)
  *   gq_kv_append                        the new tokens' k and v rows into that cache, on the device
  *   gq_rope_append                      per-head norm + RoPE of q and k, then that append, in one launch
  */
@@ -565,7 +566,7 @@ int gq_rmsnorm_prepare(const void *X, const void *R, void *H, const float *w, fl
  *   hold.  kv_len[b] < N or kv_len[b] > capacity is the caller's error: the length is clamped to
  *   [0, capacity], nothing outside the cache is read, and a query left without a position gives zeros.
  *   A sequence's output does not depend on B or on the other sequences.
- * Shapes: D 64 or 128, n_head % n_kv_head == 0, N * n_head / n_kv_head <= 32, strides multiples of 2
+ * Shapes: D 64, 128 or 256, n_head % n_kv_head == 0, N * n_head / n_kv_head <= 32, strides multiples of 2
  * with tok_stride >= a row's bytes, N <= capacity, capacity * tok_stride < 1 GiB, B * n_kv_head <=
  * 2^20; anything else (and an unknown kv): GQ_EUNSUPPORTED.  Null pointers, negative sizes,
  * ldq or ldo < n_head*D and a workspace that is null, not 16-byte aligned or below
@@ -594,7 +595,7 @@ int gq_debug_attn_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, 
  * call with few rows (B * n_kv_head * N * n_head / n_kv_head / 64 below the compute units) leaves part
  * of the chip idle -- gq_attn_decode is the entry for <= 32 rows per kv head.  The grid depends on B, N
  * and the head counts only, the lengths are read on the device: a captured graph serves every prefix.
- * Shapes: D 64 or 128, n_head % n_kv_head == 0, strides multiples of 2 with tok_stride >= a row's bytes,
+ * Shapes: D 64, 128 or 256, n_head % n_kv_head == 0, strides multiples of 2 with tok_stride >= a row's bytes,
  * 1 <= N <= capacity, capacity * tok_stride < 1 GiB, B * n_kv_head <= 2^20; anything else (and an unknown
  * kv): GQ_EUNSUPPORTED.  Null pointers, negative sizes, ldq or ldo < n_head*D: GQ_EINVAL.  The checks
  * come in gq_attn_decode's order with its messages.  B, N or n_head == 0: a no-op.  Every check precedes
@@ -609,12 +610,54 @@ int gq_attn_prefill(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, c
 int gq_debug_attn_prefill_plan(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, int *rows, int *tile);
 
 /*
+ * Both attention entries with options: a sliding window and a soft-cap on the scores.  opts == NULL or
+ * {0, 0.0f} launches exactly what gq_attn_decode / gq_attn_prefill launch -- those are calls of these
+ * with NULL -- and gives the same bits.
+ *   window  : > 0: query token i of sequence b, at position p = kv_len[b] - N + i, attends the positions
+ *             t with max(0, p - window + 1) <= t <= p (llama.cpp's standard sliding-window mask); 0: every
+ *             position up to p.  The key range is cut, not only masked: decode's workgroups share the
+ *             tiles from the first row's window start to the last row's limit, a prefill workgroup starts
+ *             at the tile of its first row's window start, and no row before such a start is fetched, so
+ *             at a fixed window the bytes read do not grow with the cached length.  A fetched key outside
+ *             a row's window contributes exactly nothing to it, whatever finite bytes it holds.
+ *   softcap : > 0: the score is softcap * tanh(scale * q.k / softcap) (Gemma-2: 50), applied after the
+ *             scale and before the mask and the softmax, in fp32 in the kernel's exp2 domain; 0: none.
+ *             The tanh is 1 - 2 / (1 + 2^(2 log2(e) x)) with an absolute error below 2^-21, i.e. a
+ *             relative error of softcap * 2^-21 in a probability (2^-15 at 50): inside the fourth 2^-11
+ *             term of the bound up to softcap = 1024; beyond, add softcap * 2^-21 * max|v| to it.
+ * The error bound, the kv_len semantics, the shapes and every check are the plain entries', in their
+ * order with their messages; before them: window < 0, softcap < 0, not finite or in (0, 1e-6): GQ_EINVAL.  The grid,
+ * the plan and the workspace may depend on the options (decode takes no more workgroups per (sequence,
+ * kv head) than the window's tiles), never on a length: kv_len is still read on the device.
+ * gq_attn_decode_workspace_size_ex: 0 for a refused shape or a negative window.  Asynchronous, no host
+ * sync, no allocation, graph-capturable.  Each entry is detected by its symbol.
+ */
+typedef struct gq_attn_opts { int64_t window; float softcap; } gq_attn_opts;   /* 0 / 0.0f: off */
+size_t gq_attn_decode_workspace_size_ex(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D,
+                                        const gq_attn_opts *opts);
+int gq_attn_decode_ex(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                      int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                      float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *workspace,
+                      size_t workspace_bytes, const gq_attn_opts *opts, void *stream);
+int gq_attn_prefill_ex(gq_kv_type kv, const void *Q, int64_t ldq, const void *Kc, const void *Vc, int64_t tok_stride,
+                       int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                       float scale, int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D,
+                       const gq_attn_opts *opts, void *stream);
+/* gq_debug_attn_plan's and gq_debug_attn_prefill_plan's outputs for a call with these options (the
+ * prefill tile is 32 keys at D = 256, 64 otherwise). */
+int gq_debug_attn_plan_ex(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, const gq_attn_opts *opts, int *tile,
+                          int *W);
+int gq_debug_attn_prefill_plan_ex(int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, const gq_attn_opts *opts,
+                                  int *rows, int *tile);
+
+/*
  * The N new tokens' k and v rows -- Knew, Vnew: fp16 (B*N, n_kv_head*D), rows ldn apart -- into the
  * caches (gq_attn_decode's kv, strides, kv_len and capacity) at positions kv_len[b] - N .. kv_len[b] - 1:
  * a copy for GQ_KV_F16; for GQ_KV_Q8_0 the blocks gq_quantize_weights(GQ_Q8_0, ...) makes of the same
  * 32 values, byte for byte.  Nothing outside those rows is written; a position outside [0, capacity)
  * (the caller's error) is skipped.  Checks as gq_attn_prefill's with one query head per kv head
  * (any N <= capacity; ldn < n_kv_head*D: GQ_EINVAL).  One launch, graph-capturable.  Detected by its symbol.
+ * D = 256 is served like 64 and 128 (eight blocks a row).
  */
 int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn, void *Kc, void *Vc, int64_t tok_stride,
                  int64_t head_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, int64_t B, int64_t N,
@@ -649,7 +692,7 @@ int gq_kv_append(gq_kv_type kv, const void *Knew, const void *Vnew, int64_t ldn,
  * The grid depends on B, N, the head counts and the device only.  Checks in gq_kv_append's order with its
  * messages (n_head % n_kv_head == 0 as gq_attn_prefill's); besides: a null Qout or inv_freq, ldq or ldqo
  * < n_head*D, ldk or ldv < n_kv_head*D, exactly one norm weight null: GQ_EINVAL; an unknown mode, n_rot
- * odd, < 2 or > D, B*N >= 2^31: GQ_EUNSUPPORTED.  B, N or n_head == 0: a no-op.  Every check precedes the
+ * odd, < 2 or > D, B*N >= 2^31: GQ_EUNSUPPORTED.  D 64, 128 or 256.  B, N or n_head == 0: a no-op.  Every check precedes the
  * launch.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol;
  * gq_version() did not change with it.
  */

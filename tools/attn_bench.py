@@ -33,6 +33,14 @@ another copy of the packed qkv rows, the q output and the caches; the copies hol
 never more than 256 of them, so the cells at N <= 4 (KiB per step) measure launches on cached data.  A cell
 is the median time of both forms, their spread, and for N >= 512 the bytes a step must move (qkv read, q and
 cache rows written) per second against bench.py's HBM figure.
+
+    python tools/attn_bench.py --gemma [--out profiles/attn_gemma_bench.json]
+
+Head dim 256 and the sliding window (gq_attn_decode_ex, gq_attn_prefill at D = 256): Gemma-2-9B heads (16 / 8,
+D 256) at decode over 32768 cached tokens and at a prefill of 8192; then, at Llama-3-8B heads (D 128) and
+Gemma-2-9B heads (D 256), decode with window 1024 over 2048, 8192 and 32768 cached tokens beside the
+yardstick, the plain call over a cache of 1024 tokens.  torch SDPA is the base everywhere (the window as a
+boolean mask).  A windowed cell's bytes are the window's rows; its copies rotate like any other cell's.
 """
 import argparse
 import json
@@ -50,14 +58,16 @@ for p in (os.path.join(ROOT, "gguf-triton-kernel_amd"), ROOT):
 import bench  # noqa: E402
 
 HEADS = {"llama3_8b": (32, 8, 128), "llama2_7b": (32, 32, 128)}
+GEMMA_HEADS = {"llama3_8b": (32, 8, 128), "gemma2_9b": (16, 8, 256)}
 FORMS = ("torch", "f16", "q8_0")
 
 
 class Case:
-    def __init__(self, nh, kvh, D, N, B, L, dev, steps):
+    def __init__(self, nh, kvh, D, N, B, L, dev, steps, window=0):
         import kernels._lib as kl
-        self.kl, self.dev, self.dims = kl, dev, (nh, kvh, D, N, B, L)
-        self.live = {k: 2 * B * L * kvh * kl.kv_row_bytes(k, D) for k in ("f16", "q8_0")}
+        self.kl, self.dev, self.dims, self.window = kl, dev, (nh, kvh, D, N, B, L), window
+        rows = min(L, window + N - 1) if window else L  # the positions some query attends
+        self.live = {k: 2 * B * rows * kvh * kl.kv_row_bytes(k, D) for k in ("f16", "q8_0")}
         ncopies, self.plans = bench.rotation_plan(self.live["q8_0"], steps)
         gen = torch.Generator(device=dev).manual_seed(1)
         rnd = lambda *s: torch.randn(s, device=dev, generator=gen).to(torch.float16)  # noqa: E731
@@ -66,10 +76,12 @@ class Case:
                    for c in range(ncopies)]
         self.q = rnd(B * N, nh * D)
         self.kv_len = torch.full((B,), L, dtype=torch.int32, device=dev)
-        self.ws = torch.empty(kl.attn_workspace_size(B, N, nh, kvh, D), dtype=torch.uint8, device=dev)
+        self.ws = torch.empty(kl.attn_workspace_size(B, N, nh, kvh, D, window), dtype=torch.uint8, device=dev)
         self.out = torch.empty(B * N, nh * D, dtype=torch.float16, device=dev)
         # the N new tokens sit at the cache's end: query i sees positions 0 .. L - N + i
-        self.mask = None if N == 1 else torch.ones(N, L, dtype=torch.bool, device=dev).tril(L - N)
+        self.mask = None if N == 1 and not window else torch.ones(N, L, dtype=torch.bool, device=dev).tril(L - N)
+        if window:  # ... and L - N + i - window + 1 at the least
+            self.mask &= ~torch.ones(N, L, dtype=torch.bool, device=dev).tril(L - N - window)
 
     def step(self, form, c, i):
         nh, kvh, D, N, B, L = self.dims
@@ -81,7 +93,7 @@ class Case:
         k, v = self.f16[c] if form == "f16" else self.q8[c]
         rb = self.kl.kv_row_bytes(form, D)
         return self.kl.attn_decode(form, self.q, k, v, (kvh * rb, rb, L * kvh * rb), self.kv_len, L, B, N, nh, kvh, D,
-                                   self.ws, out=self.out)
+                                   self.ws, out=self.out, window=self.window)
 
     def check(self):
         a, b = self.step("torch", 0, 0).float(), self.step("f16", 0, 0).float()
@@ -276,6 +288,43 @@ def main_prefill(a, dev):
                            "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count, "rows": rows}, f, indent=1)
 
 
+def main_gemma(a, dev):
+    out = {"steps": a.steps, "repeats": a.repeats, "hbm_peak_GBs": bench.HBM_PEAK_GBS, "decode": [], "prefill": [], "window": []}
+
+    def decode(name, L, window=0):
+        nh, kvh, D = GEMMA_HEADS[name]
+        case = Case(nh, kvh, D, 1, 1, L, dev, a.steps, window)
+        row = {"heads": name, "D": D, "N": 1, "B": 1, "kv_len": L, "window": window,
+               "W": case.kl.attn_plan(1, 1, nh, kvh, D, window)[1], **measure(case, a.steps, a.repeats, dev)}
+        print(json.dumps(row), flush=True)
+        del case
+        torch.cuda.empty_cache()
+        return row
+
+    def save():
+        if a.out:  # (after every cell: a run cut short keeps what it measured)
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                json.dump(out, f, indent=1)
+
+    for name in GEMMA_HEADS:  # the yardstick (a cache of `window` tokens, the plain call), then the window over longer caches
+        for L, window in ((1024, 0), (2048, 1024), (8192, 1024), (32768, 1024)):
+            if L <= a.max_len:
+                out["window"].append(decode(name, L, window))
+                save()
+    if 32768 <= a.max_len:
+        out["decode"].append(decode("gemma2_9b", 32768))
+        save()
+    if 8192 <= a.max_len:
+        nh, kvh, D = GEMMA_HEADS["gemma2_9b"]
+        case = PrefillCase(nh, kvh, D, 8192, 1, 0, dev, a.steps)
+        out["prefill"].append({"heads": "gemma2_9b", "D": D, "B": 1, "N": 8192, "prefix": 0,
+                               "rows_per_workgroup": case.kl.attn_prefill_plan(1, 8192, nh, kvh, D)[0],
+                               **measure_prefill(case, a.steps, a.repeats, dev)})
+        print(json.dumps(out["prefill"][-1]), flush=True)
+        save()
+
+
 def graphs(case, form):
     grs = []
     for plan in case.plans:
@@ -310,6 +359,7 @@ def main():
     ap.add_argument("--max-len", type=int, default=32768)
     ap.add_argument("--out", default=None)
     ap.add_argument("--prefill", action="store_true", help="prefill attention (attn_prefill) instead of decode")
+    ap.add_argument("--gemma", action="store_true", help="head dim 256 and windowed decode (Gemma-2-9B heads; window 1024)")
     ap.add_argument("--rope", action="store_true", help="the fused norm + RoPE + append (rope_append) beside torch RoPE + kv_append")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -319,6 +369,8 @@ def main():
         return main_prefill(a, dev)
     if a.rope:
         return main_rope(a, dev)
+    if a.gemma:
+        return main_gemma(a, dev)
     rows = []
     for name, (nh, kvh, D) in HEADS.items():
         for L in (512, 4096, 32768):
