@@ -156,6 +156,47 @@ struct RopeCall {
 };
 hipError_t launch_rope_append(int kv, int mode, const RopeCall &c, hipStream_t s);
 
+// DeepSeek's absorbed multi-head latent attention at decode over an fp16 latent cache of [c_kv (512) |
+// k_pe (64)] rows (attn_mla.hip; gq_mla_decode): B * groups * W workgroups, a group being kMlaRows of the
+// N * n_head query rows, each workgroup its contiguous share of its sequence's kMlaTile-key tiles through
+// a workgroup-wide LDS ring of kMlaSlots tiles, then a combine of the W fp32 partials of every row.
+// None of the constants was measured against another value: kMlaTile is one k-step of the second product,
+// kMlaRows one 16-row MFMA tile per wave, three slots keep two tiles (72 KiB) in flight per compute unit.
+// kMlaMaxW is above kAttnMaxW because one sequence has ONE row stream: at B = 1 and 16 heads, 64 shares
+// would leave three quarters of a 256-unit chip idle; a row's combine then reads up to 256 x 2 KiB.
+constexpr int kMlaRank = 512, kMlaRope = 64; // the one (kv_lora_rank, rope dimension) that is instantiated
+constexpr int kMlaTile = 32;      // keys per tile
+constexpr int kMlaRows = 64;      // query rows per workgroup
+constexpr int kMlaSlots = 3;      // LDS ring slots per workgroup (one 36 KiB tile each)
+constexpr int kMlaMaxW = 256;     // workgroups per (sequence, row group), at most
+constexpr int kMlaMaxN = 4, kMlaMaxHeads = 128;
+struct MlaPlan {
+    bool ok = false;              // 1 <= N <= 4, 1 <= n_head <= 128, B * groups <= 2^20
+    int W = 0, groups = 0;
+    int64_t grid = 0;
+    size_t workspace_bytes = 0;
+};
+struct MlaCall {
+    const void *Q, *C;
+    const int32_t *kv_len;
+    void *O, *workspace;
+    int64_t ldq, ldo, tok_stride, seq_stride, capacity, B, N, n_head;
+    float scale;
+};
+MlaPlan plan_mla(int64_t B, int64_t N, int64_t n_head);
+hipError_t launch_mla_decode(const MlaCall &c, const MlaPlan &p, hipStream_t s);
+// The N new tokens' normalised c_kv and rotated k_pe into that cache, and every head's rotated q_pe into
+// the rope part of gq_mla_decode's Q (attn_mla.hip; gq_mla_append).  mode: gq_rope_mode.
+struct MlaAppendCall {
+    const void *Ckv, *Kpe, *Qpe;
+    void *Qout, *C;
+    const int32_t *kv_len;
+    const float *inv_freq, *norm_w;
+    int64_t ldc, ldk, ldqp, q_head_stride, ldqo, tok_stride, seq_stride, capacity, B, N, n_head;
+    float mscale, eps;
+};
+hipError_t launch_mla_append(int mode, const MlaAppendCall &c, hipStream_t s);
+
 // Decode-shaped GEMV (mmq_gemv.hip): C[t][m] for t < N_tok <= 8 from SOA activations.
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,
                        int64_t M, int64_t N, int64_t K, int64_t ldc, hipStream_t s);

@@ -1687,6 +1687,103 @@ int gq_rope_append(gq_kv_type kv, gq_rope_mode mode, const void *Q, int64_t ldq,
     return hip_rc(gq::launch_rope_append(kv == GQ_KV_Q8_0, mode == GQ_ROPE_NEOX, c, (hipStream_t)stream), "rope_append");
 }
 
+// ---- multi-head latent attention (attn_mla.hip) ----
+// The checks gq_mla_decode and gq_mla_append share, in check_kv_cache's order with its wording where the
+// condition is the same: the sizes, then (not empty) the shape and the cache geometry.  decode: the call is
+// held to gq_mla_decode's N.
+static int check_mla_cache(int64_t tok_stride, int64_t seq_stride, int64_t capacity, int64_t B, int64_t N, int64_t n_head,
+                           int64_t rank, int64_t rope_dim, bool decode, bool &empty)
+{
+    empty = false;
+    if (B < 0 || N < 0 || n_head < 0 || rank < 0 || rope_dim < 0 || capacity < 0)
+        return fail(GQ_EINVAL, "negative size B=%lld N=%lld n_head=%lld rank=%lld rope_dim=%lld capacity=%lld", (long long)B,
+                    (long long)N, (long long)n_head, (long long)rank, (long long)rope_dim, (long long)capacity);
+    empty = B == 0 || N == 0 || n_head == 0;
+    if (empty) return GQ_OK;
+    if (rank != gq::kMlaRank || rope_dim != gq::kMlaRope)
+        return fail(GQ_EUNSUPPORTED, "(rank, rope_dim) = (%lld, %lld) is not (512, 64)", (long long)rank, (long long)rope_dim);
+    if (decode && N > gq::kMlaMaxN) return fail(GQ_EUNSUPPORTED, "N=%lld new tokens, at most 4", (long long)N);
+    if (n_head > gq::kMlaMaxHeads) return fail(GQ_EUNSUPPORTED, "n_head=%lld query heads, at most 128", (long long)n_head);
+    if (B > (1 << 20) / 8) return fail(GQ_EUNSUPPORTED, "B = %lld is above 2^17", (long long)B);
+    const int64_t rb = 2 * (rank + rope_dim);
+    if (((tok_stride | seq_stride) & 1) != 0) return fail(GQ_EUNSUPPORTED, "the cache strides must be multiples of 2");
+    if (tok_stride < rb || seq_stride < 0)
+        return fail(GQ_EUNSUPPORTED, "tok_stride=%lld is below a row's %lld bytes, or a negative stride", (long long)tok_stride, (long long)rb);
+    if (capacity < N) return fail(GQ_EUNSUPPORTED, "capacity=%lld cannot hold the N=%lld new tokens", (long long)capacity, (long long)N);
+    if (capacity > (1 << 30) / tok_stride)
+        return fail(GQ_EUNSUPPORTED, "one sequence spans capacity * tok_stride = 1 GiB or more (32-bit buffer offsets)");
+    return GQ_OK;
+}
+
+size_t gq_mla_decode_workspace_size(int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim)
+{
+    if (rank != gq::kMlaRank || rope_dim != gq::kMlaRope || B > (1 << 20) / 8) return 0;
+    return gq::plan_mla(B, N, n_head).workspace_bytes; // (0: empty or not a supported shape)
+}
+
+int gq_debug_mla_plan(int64_t B, int64_t N, int64_t n_head, int *tile, int *rows_per_group, int *W)
+{
+    g_err.clear();
+    const gq::MlaPlan p = gq::plan_mla(B, N, n_head);
+    if (!p.ok || B > (1 << 20) / 8) return fail(GQ_EUNSUPPORTED, "not an MLA decode shape");
+    if (tile) *tile = gq::kMlaTile;
+    if (rows_per_group) *rows_per_group = gq::kMlaRows;
+    if (W) *W = p.W;
+    return GQ_OK;
+}
+
+int gq_mla_decode(const void *Q, int64_t ldq, const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len,
+                  int64_t capacity, void *O, int64_t ldo, float scale, int64_t B, int64_t N, int64_t n_head, int64_t rank,
+                  int64_t rope_dim, void *workspace, size_t workspace_bytes, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    // (the sizes first: a negative one has no row length to hold ldq against)
+    if (B >= 0 && N >= 0 && n_head > 0 && rank >= 0 && rope_dim >= 0 && B * N > 0) {
+        if (!Q || !C || !kv_len || !O) return fail(GQ_EINVAL, "null pointer (Q=%p C=%p kv_len=%p O=%p)", Q, C, (const void *)kv_len, O);
+        if (ldq < n_head * (rank + rope_dim))
+            return fail(GQ_EINVAL, "ldq=%lld < n_head*(rank+rope_dim)=%lld", (long long)ldq, (long long)(n_head * (rank + rope_dim)));
+        if (ldo < n_head * rank) return fail(GQ_EINVAL, "ldo=%lld < n_head*rank=%lld", (long long)ldo, (long long)(n_head * rank));
+    }
+    const int rc = check_mla_cache(tok_stride, seq_stride, capacity, B, N, n_head, rank, rope_dim, true, empty);
+    if (rc != GQ_OK || empty) return rc;
+    const gq::MlaPlan p = gq::plan_mla(B, N, n_head);
+    if (!workspace || workspace_bytes < p.workspace_bytes) return fail_workspace(workspace, workspace_bytes, p.workspace_bytes);
+    if (((uintptr_t)workspace & 15) != 0) return fail(GQ_EINVAL, "the workspace must be 16-byte aligned");
+    const gq::MlaCall c{Q, C, kv_len, O, workspace, ldq, ldo, tok_stride, seq_stride, capacity, B, N, n_head, scale};
+    return hip_rc(gq::launch_mla_decode(c, p, (hipStream_t)stream), "mla_decode");
+}
+
+int gq_mla_append(gq_rope_mode mode, const void *Ckv, int64_t ldc, const void *Kpe, int64_t ldk, const void *Qpe, int64_t ldqp,
+                  int64_t q_head_stride, void *Qout, int64_t ldqo, void *C, int64_t tok_stride, int64_t seq_stride,
+                  const int32_t *kv_len, int64_t capacity, const float *inv_freq, float mscale, const float *norm_w, float eps,
+                  int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    if (B >= 0 && N >= 0 && n_head > 0 && rank >= 0 && rope_dim >= 0 && B * N > 0) {
+        if (!Ckv || !Kpe || !Qpe || !Qout || !C || !kv_len || !inv_freq || !norm_w)
+            return fail(GQ_EINVAL, "null pointer (Ckv=%p Kpe=%p Qpe=%p Qout=%p C=%p kv_len=%p inv_freq=%p norm_w=%p)", Ckv, Kpe, Qpe,
+                        Qout, C, (const void *)kv_len, (const void *)inv_freq, (const void *)norm_w);
+        if (ldc < rank) return fail(GQ_EINVAL, "ldc=%lld < rank=%lld", (long long)ldc, (long long)rank);
+        if (ldk < rope_dim) return fail(GQ_EINVAL, "ldk=%lld < rope_dim=%lld", (long long)ldk, (long long)rope_dim);
+        if (q_head_stride < rope_dim)
+            return fail(GQ_EINVAL, "q_head_stride=%lld < rope_dim=%lld", (long long)q_head_stride, (long long)rope_dim);
+        if (ldqp < (n_head - 1) * q_head_stride + rope_dim)
+            return fail(GQ_EINVAL, "ldqp=%lld < (n_head-1)*q_head_stride+rope_dim=%lld", (long long)ldqp,
+                        (long long)((n_head - 1) * q_head_stride + rope_dim));
+        if (ldqo < n_head * (rank + rope_dim))
+            return fail(GQ_EINVAL, "ldqo=%lld < n_head*(rank+rope_dim)=%lld", (long long)ldqo, (long long)(n_head * (rank + rope_dim)));
+    }
+    const int rc = check_mla_cache(tok_stride, seq_stride, capacity, B, N, n_head, rank, rope_dim, false, empty);
+    if (rc != GQ_OK || empty) return rc;
+    if (mode != GQ_ROPE_NORM && mode != GQ_ROPE_NEOX) return fail(GQ_EUNSUPPORTED, "unknown rope mode %d", (int)mode);
+    if (B * N >= ((int64_t)1 << 31)) return fail(GQ_EUNSUPPORTED, "B * N = %lld tokens is 2^31 or more", (long long)(B * N));
+    const gq::MlaAppendCall c{Ckv, Kpe, Qpe, Qout, C, kv_len, inv_freq, norm_w, ldc, ldk, ldqp, q_head_stride, ldqo,
+                              tok_stride, seq_stride, capacity, B, N, n_head, mscale, eps};
+    return hip_rc(gq::launch_mla_append(mode == GQ_ROPE_NEOX, c, (hipStream_t)stream), "mla_append");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

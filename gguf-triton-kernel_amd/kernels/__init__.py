@@ -22,9 +22,14 @@ with a sliding window and a logit soft-cap per layer, at head dims 64, 128 and 2
 and the rotary embedding (with the per-head q/k norm) fused into the append:
 
     from kernels import RoPE, rope_append
+
+and DeepSeek's multi-head latent attention at decode over a latent cache (gq_mla_decode, gq_mla_append):
+
+    from kernels import MLACache, MLAttention, mla_decode, mla_append
 """
 _LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib", "RoPE": "attention",
-         "rope_append": "_lib", "attn_options": "attention"}
+         "rope_append": "_lib", "attn_options": "attention", "MLACache": "attention", "MLAttention": "attention",
+         "mla_decode": "_lib", "mla_append": "_lib"}
 __all__ = list(_LAZY)
 
 

@@ -119,6 +119,12 @@ SIGNATURES = {
     "gq_kv_append": ([_I, _P, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_rope_append": ([_I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _P, _I64, _P, _I64,
                         ctypes.c_float, _P, _P, ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_mla_decode_workspace_size": ([_I64, _I64, _I64, _I64, _I64], _SZ),
+    "gq_mla_decode": ([_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
+    "gq_debug_mla_plan": ([_I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                           ctypes.POINTER(ctypes.c_int)], _I),
+    "gq_mla_append": ([_I, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, ctypes.c_float, _P,
+                       ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
@@ -1140,6 +1146,70 @@ def rope_append(kind: str, mode: str, q: torch.Tensor, k: torch.Tensor, v: torch
                                     kv_len.data_ptr(), capacity, inv_freq.data_ptr(), n_rot, float(mscale), _ptr(q_norm),
                                     _ptr(k_norm), float(eps), B, N, n_head, n_kv_head, D, _stream(dev)))
     return out
+
+
+MLA_RANK, MLA_ROPE = 512, 64  # the (kv_lora_rank, rope dimension) gq_mla_decode is instantiated for
+
+
+def mla_plan(B: int, N: int, n_head: int):
+    """(keys per tile, query rows per group, workgroups W per (sequence, group)) of an mla_decode call (gq_debug_mla_plan)."""
+    tile, rows, W = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _check(lib().gq_debug_mla_plan(B, N, n_head, ctypes.byref(tile), ctypes.byref(rows), ctypes.byref(W)))
+    return tile.value, rows.value, W.value
+
+
+def mla_workspace_size(B: int, N: int, n_head: int, rank: int = MLA_RANK, rope_dim: int = MLA_ROPE) -> int:
+    return int(lib().gq_mla_decode_workspace_size(B, N, n_head, rank, rope_dim))
+
+
+def mla_decode(q: torch.Tensor, C: torch.Tensor, strides, kv_len: torch.Tensor, capacity: int, B: int, N: int, n_head: int,
+               workspace: torch.Tensor, scale: float, out: torch.Tensor | None = None, rank: int = MLA_RANK,
+               rope_dim: int = MLA_ROPE, kv_offset: int = 0) -> torch.Tensor:
+    """DeepSeek's absorbed latent attention of the N new tokens of B sequences (gq_mla_decode): q fp16
+    (B*N, n_head*(rank+rope_dim)), head j's row [q_abs | q_pe], over the latent cache C (any dtype; rows of
+    [c_kv | k_pe] fp16 starting kv_offset bytes in, strides = (tok, seq) in bytes) -> fp16 (B*N, n_head*rank).
+    kv_len int32 (B) on the device, the lengths including the new tokens.  No host sync, no fallback."""
+    _require_device(q, "q")
+    dev = q.device
+    ldq = _kv_rows(q, "q", B * N, n_head * (rank + rope_dim), dev)
+    _kv_caches(C, C, kv_len, B, dev)
+    if out is None:
+        out = torch.empty((B * N, n_head * rank), dtype=torch.float16, device=dev)
+    ldo = _kv_rows(out, "out", B * N, n_head * rank, dev)
+    _check_workspace(workspace, 0, dev)
+    tok, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_mla_decode(q.data_ptr(), ldq, C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(), capacity,
+                                   out.data_ptr(), ldo, float(scale), B, N, n_head, rank, rope_dim, workspace.data_ptr(),
+                                   workspace.numel(), _stream(dev)))
+    return out
+
+
+def mla_append(mode: str, ckv: torch.Tensor, kpe: torch.Tensor, qpe: torch.Tensor, q_head_stride: int, qout: torch.Tensor,
+               C: torch.Tensor, strides, kv_len: torch.Tensor, capacity: int, inv_freq: torch.Tensor, mscale: float,
+               norm_w: torch.Tensor, eps: float, B: int, N: int, n_head: int, rank: int = MLA_RANK, rope_dim: int = MLA_ROPE,
+               kv_offset: int = 0):
+    """The N new tokens into the latent cache, and their rotated q_pe into mla_decode's q (gq_mla_append, one
+    launch): ckv fp16 (B*N, rank) is RMS-normalised with norm_w (fp32 (rank)), kpe fp16 (B*N, rope_dim) rotated
+    by each token's position kv_len[b] - N + i, both written to that position's cache row; qpe is a view whose
+    row t holds head h's rope_dim values at element h*q_head_stride (e.g. q[:, 128:] with stride 192), rotated
+    into qout[t, h*(rank+rope_dim) + rank:].  qout: fp16 (B*N, n_head*(rank+rope_dim)).  No host sync."""
+    _require_device(ckv, "ckv")
+    dev = ckv.device
+    ldc = _kv_rows(ckv, "ckv", B * N, rank, dev)
+    ldk = _kv_rows(kpe, "kpe", B * N, rope_dim, dev)
+    ldqp = _kv_rows(qpe, "qpe", B * N, (n_head - 1) * q_head_stride + rope_dim, dev)
+    ldqo = _kv_rows(qout, "qout", B * N, n_head * (rank + rope_dim), dev)
+    _kv_caches(C, C, kv_len, B, dev)
+    for t, name, n in ((inv_freq, "inv_freq", rope_dim // 2), (norm_w, "norm_w", rank)):
+        if t.device != dev or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"{name} must hold {n} contiguous float32 values on {dev}")
+    tok, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_mla_append(ROPE_MODES[mode], ckv.data_ptr(), ldc, kpe.data_ptr(), ldk, qpe.data_ptr(), ldqp,
+                                   q_head_stride, qout.data_ptr(), ldqo, C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(),
+                                   capacity, inv_freq.data_ptr(), float(mscale), norm_w.data_ptr(), float(eps), B, N, n_head,
+                                   rank, rope_dim, _stream(dev)))
 
 
 def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N: int, K: int,

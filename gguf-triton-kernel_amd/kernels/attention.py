@@ -200,3 +200,142 @@ class KVCache:
             ws = self._ws[key] = torch.empty(max(need, 16), dtype=torch.uint8, device=self.k.device)
         return _lib.attn_decode(self.kind, q, self.k, self.v, self.strides, self.kv_len, self.capacity, self.B, N, n_head,
                                 self.n_kv_head, self.D, ws, scale, out, window=window, softcap=softcap)
+
+
+class MLACache:
+    """The latent cache of one DeepSeek-V2/V3 (multi-head latent attention) layer: ONE fp16 row of rank +
+    rope_dim values [c_kv | k_pe] per (sequence, position), at byte (b*capacity + t) * 2 * (rank + rope_dim),
+    shared by every query head as key and value.  kv_len: int32 (B) on the device.  append and attend are
+    gq_mla_append and gq_mla_decode: up to 4 new tokens a step and up to 128 heads; neither syncs the host,
+    and neither allocates after the first call at a given (N, n_head), so one captured graph of a step
+    serves every length up to the capacity.  No fallback: a shape the library refuses raises."""
+
+    def __init__(self, B: int, capacity: int, rank: int = _lib.MLA_RANK, rope_dim: int = _lib.MLA_ROPE, device="cuda"):
+        if (rank, rope_dim) != (_lib.MLA_RANK, _lib.MLA_ROPE):
+            raise ValueError(f"(rank, rope_dim) = ({rank}, {rope_dim}) is not ({_lib.MLA_RANK}, {_lib.MLA_ROPE})")
+        if min(B, capacity) < 1:
+            raise ValueError("B and capacity must be positive")
+        self.B, self.capacity, self.rank, self.rope_dim = B, capacity, rank, rope_dim
+        rb = 2 * (rank + rope_dim)
+        self.strides = (rb, capacity * rb)  # (tok, seq) bytes
+        self.c = torch.zeros(B * capacity * rb, dtype=torch.uint8, device=device)
+        self.kv_len = torch.zeros(B, dtype=torch.int32, device=device)
+        self._bufs = {}  # (N, n_head) -> (q [q_abs | q_pe] rows, workspace, output)
+        self._n = 0      # the last append's token count: attend's N
+
+    def reset(self):
+        self.kv_len.zero_()
+        self._n = 0
+
+    def _for(self, N: int, n_head: int):
+        bufs = self._bufs.get((N, n_head))
+        if bufs is None:
+            dev, T = self.c.device, self.B * N
+            need = _lib.mla_workspace_size(self.B, N, n_head, self.rank, self.rope_dim)
+            bufs = self._bufs[(N, n_head)] = (torch.zeros(T, n_head * (self.rank + self.rope_dim), dtype=torch.float16, device=dev),
+                                              torch.empty(max(need, 16), dtype=torch.uint8, device=dev),
+                                              torch.empty(T, n_head * self.rank, dtype=torch.float16, device=dev))
+        return bufs
+
+    def append(self, ckv: torch.Tensor, kpe: torch.Tensor, q: torch.Tensor, rope: RoPE, norm_w: torch.Tensor, eps: float = 1e-6,
+               q_head_dim: int = 192):
+        """ckv fp16 (B*N, rank) and kpe (B*N, rope_dim): the N new tokens' halves of the attn_kv_a_mqa output
+        (column slices of it will do).  q fp16 (B*N, n_head*q_head_dim): the rope_dim values to rotate are the
+        LAST rope_dim columns of every head (192: [q_nope (128) | q_pe (64)]; rope_dim: q_pe alone).
+        The cache rows are written, kv_len advances by N, and the returned fp16 (B*N, n_head*(rank + rope_dim))
+        buffer -- this cache's own, reused every step -- has every head's rotated q_pe in its last rope_dim
+        columns; the caller writes the absorbed q into the first rank columns of each head and calls attend."""
+        N, n_head, Dq = q.shape[0] // self.B, q.shape[1] // q_head_dim, q_head_dim
+        if N * self.B != q.shape[0] or N < 1:
+            raise ValueError(f"q has {q.shape[0]} rows, not a positive multiple of B = {self.B}")
+        if n_head < 1 or Dq * n_head != q.shape[1] or Dq < self.rope_dim:
+            raise ValueError(f"q has {q.shape[1]} columns, not heads of q_head_dim = {Dq} >= rope_dim = {self.rope_dim}")
+        qbuf = self._for(N, n_head)[0]
+        self.kv_len += N
+        _lib.mla_append(rope.mode, ckv, kpe, q[:, Dq - self.rope_dim:], Dq, qbuf, self.c, self.strides, self.kv_len, self.capacity,
+                        rope.inv_freq, rope.mscale, norm_w, eps, self.B, N, n_head, self.rank, self.rope_dim)
+        self._n = N
+        return qbuf
+
+    def attend(self, q: torch.Tensor, scale: float) -> torch.Tensor:
+        """q: fp16 (B*N, n_head*(rank + rope_dim)), [q_abs | q_pe] per head, of the N tokens last appended
+        (append's buffer, completed) -> fp16 (B*N, n_head*rank), the cache's own output buffer."""
+        N = q.shape[0] // self.B
+        if N < 1 or N * self.B != q.shape[0] or N != self._n:
+            raise ValueError(f"q has {q.shape[0]} rows; the last append wrote {self._n} tokens for each of {self.B} sequences")
+        n_head = q.shape[1] // (self.rank + self.rope_dim)
+        _, ws, out = self._for(N, n_head)
+        return _lib.mla_decode(q, self.c, self.strides, self.kv_len, self.capacity, self.B, N, n_head, ws, scale, out,
+                               self.rank, self.rope_dim)
+
+
+class MLAttention:
+    """A DeepSeek-V2/V3 layer's attention core at decode, between the q / attn_kv_a_mqa projections and
+    attn_output: the absorption of W_UK into q (a torch bmm on dequantized weights), MLACache.append,
+    MLACache.attend, and the product with W_UV (a second bmm).  The two bmm are the caller's matmuls in the
+    C ABI; a HIP form of them is not part of the library yet.  k_b: fp16 (n_head, rank, nope), v_b: fp16
+    (n_head, v_dim, rank)."""
+
+    def __init__(self, k_b: torch.Tensor, v_b: torch.Tensor, norm_w: torch.Tensor, rope: RoPE, eps: float = 1e-6,
+                 scale: float | None = None):
+        self.k_b, self.v_b = k_b.to(torch.float16).contiguous(), v_b.to(torch.float16).contiguous()
+        self.n_head, self.rank, self.nope = self.k_b.shape
+        self.v_dim = self.v_b.shape[1]
+        if self.v_b.shape[0] != self.n_head or self.v_b.shape[2] != self.rank:
+            raise ValueError(f"v_b is {tuple(self.v_b.shape)}, expected ({self.n_head}, v_dim, {self.rank})")
+        self.norm_w, self.rope, self.eps = norm_w.to(torch.float32).contiguous(), rope, float(eps)
+        # llama.cpp's deepseek2 scale: mscale^2 / sqrt(the un-absorbed key length)
+        self.scale = rope.mscale ** 2 / math.sqrt(self.nope + rope.n_rot) if scale is None else float(scale)
+        self.cache = None
+
+    @classmethod
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", scale: float | None = None) -> "MLAttention":
+        """From read_gguf()'s metadata and tensors: {arch}.attention.kv_lora_rank, {arch}.rope.dimension_count
+        and the rope.scaling.* keys (through RoPE.from_gguf), {arch}.attention.layer_norm_rms_epsilon,
+        blk.<layer>.attn_kv_a_norm.weight, and blk.<layer>.attn_k_b.weight (GGUF dims (nope, rank, n_head)) with
+        attn_v_b.weight (dims (rank, v_dim, n_head)) -- or the older fused blk.<layer>.attn_kv_b.weight (dims
+        (rank, n_head * (nope + v_dim)): per head nope rows of W_UK, then v_dim rows of W_UV), split here with
+        {arch}.attention.key_length - rope dimension as nope.  These key and tensor names, their dims and the
+        default scale are written from memory of llama.cpp's deepseek2 graph; nothing here can check them
+        against it.  Quantized weights are dequantized once (gq_dequantize) and kept as fp16."""
+        arch = meta["general.architecture"]
+        rank, n_rot = int(meta[f"{arch}.attention.kv_lora_rank"]), int(meta[f"{arch}.rope.dimension_count"])
+        n_head = int(meta[f"{arch}.attention.head_count"])
+        rope = RoPE.from_gguf(meta, tensors, layer, device, mode=ROPE_MODE.get(arch, "norm"))
+        rope = RoPE(rope.inv_freq, n_rot, rope.mode, rope.mscale)  # (attn_q_norm / attn_k_norm are no MLA tensors)
+
+        def dense(t):
+            if t.type_name in ("f16", "f32"):
+                return torch.from_numpy(_f32_values(t).astype(np.float16)).to(device).reshape(t.shape)
+            rows = int(np.prod(t.shape[:-1]))
+            return _lib.dequantize_device(_lib.TYPES[t.type_name], t.to_device(device), rows, t.shape[-1]).reshape(t.shape)
+
+        kb, vb = tensors.get(f"blk.{layer}.attn_k_b.weight"), tensors.get(f"blk.{layer}.attn_v_b.weight")
+        if kb is not None and vb is not None:
+            k_b, v_b = dense(kb), dense(vb)
+        else:
+            kv = dense(tensors[f"blk.{layer}.attn_kv_b.weight"])  # (n_head * (nope + v_dim), rank)
+            nope = int(meta[f"{arch}.attention.key_length"]) - n_rot
+            kv = kv.view(n_head, -1, rank)
+            k_b, v_b = kv[:, :nope].transpose(1, 2), kv[:, nope:]
+        norm_w = torch.from_numpy(_f32_values(tensors[f"blk.{layer}.attn_kv_a_norm.weight"]).astype(np.float32)).to(device)
+        return cls(k_b, v_b, norm_w, rope, float(meta.get(f"{arch}.attention.layer_norm_rms_epsilon", 1e-6)), scale)
+
+    def new_cache(self, B: int, capacity: int, device="cuda") -> MLACache:
+        """The layer's latent cache, empty: forward appends to it and attends over it."""
+        self.cache = MLACache(B, capacity, self.rank, self.rope.n_rot, device)
+        return self.cache
+
+    def forward(self, q: torch.Tensor, kv_a_out: torch.Tensor, cache: MLACache | None = None) -> torch.Tensor:
+        """q fp16 (B*N, n_head*(nope + rope_dim)) and the attn_kv_a_mqa output (B*N, rank + rope_dim) of the N
+        new tokens -> fp16 (B*N, n_head*v_dim), attn_output's input, over `cache` (new_cache's when None).
+        Four steps: q_nope absorbed by bmm, append, attend, bmm with W_UV."""
+        cache = self.cache if cache is None else cache
+        if cache is None:
+            raise ValueError("no cache: call new_cache(B, capacity) first, or pass one")
+        T, H, rank = q.shape[0], self.n_head, self.rank
+        q_abs = torch.bmm(q.view(T, H, -1)[:, :, :self.nope].transpose(0, 1), self.k_b.transpose(1, 2))  # (H, T, rank)
+        qbuf = cache.append(kv_a_out[:, :rank], kv_a_out[:, rank:], q, self.rope, self.norm_w, self.eps)
+        qbuf.view(T, H, -1)[:, :, :rank].copy_(q_abs.transpose(0, 1))
+        o = cache.attend(qbuf, self.scale)                                                               # (T, H*rank)
+        return torch.bmm(o.view(T, H, rank).transpose(0, 1), self.v_b.transpose(1, 2)).transpose(0, 1).reshape(T, H * self.v_dim)

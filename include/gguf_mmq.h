@@ -34,6 +34,7 @@
  *   gq_attn_decode_ex, gq_attn_prefill_ex  the same with a sliding window and a logit soft-cap (Gemma, Mistral, Phi-3)
  *   gq_kv_append                        the new tokens' k and v rows into that cache, on the device
  *   gq_rope_append                      per-head norm + RoPE of q and k, then that append, in one launch
+ *   gq_mla_decode, gq_mla_append        DeepSeek's latent attention (MLA) at decode and its latent cache's producer
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -703,6 +704,63 @@ int gq_rope_append(gq_kv_type kv, gq_rope_mode mode, const void *Q, int64_t ldq,
                    const float *inv_freq, int64_t n_rot, float mscale,
                    const float *q_norm_w, const float *k_norm_w, float eps,   /* both NULL: no norm */
                    int64_t B, int64_t N, int64_t n_head, int64_t n_kv_head, int64_t D, void *stream);
+
+/*
+ * Multi-head latent attention (DeepSeek-V2/V3/R1, Kimi-K2) at decode, in its absorbed form: ONE latent cache
+ * row per (sequence, position) serves every query head as key AND value.
+ *   C      : the latent cache, fp16.  The row of (sequence b, position t) starts at byte b*seq_stride +
+ *            t*tok_stride (multiples of 2) and holds rank + rope_dim = 576 values [c_kv (512) | k_pe (64)]:
+ *            the normalised compressed kv and the rotated shared rope key, as gq_mla_append writes them.
+ *   Q      : fp16 (B*N, n_head*576), rows ldq apart; head j's 576 are [q_abs (512) | q_pe (64)]: q_nope
+ *            already multiplied by the head's W_UK (the caller's matmul) and q_pe already rotated.
+ *   kv_len, capacity : as gq_attn_decode's (the lengths INCLUDE the N new tokens, device memory).
+ *   O      : fp16 (B*N, n_head*512), rows ldo apart: softmax(scale * q . row) weighted sum of the rows'
+ *            first 512 values, over positions 0 .. kv_len[b] - N + i for query token i.  The caller
+ *            multiplies head j's 512 by its W_UV.
+ * The arithmetic and the bound are gq_attn_decode's fp16 path's: fp32 scores, softmax and sums, fp16
+ * probabilities into the second product, one final rounding, |o - exact| <= 2^-9 * max|c_kv| over the
+ * attended positions.  Positions at or beyond kv_len[b] are never used, whatever bytes they hold; the length
+ * is clamped to [0, capacity]; a sequence's output depends neither on B nor on the other sequences.
+ * Two launches: B * ceil(N*n_head/64) * W workgroups (W from the compute units, B and the row groups, or
+ * the GQ_ATTN_W tuning -- never a length), then a combine of the W fp32 partials of every row.
+ * Shapes: 1 <= N <= 4, 1 <= n_head <= 128, (rank, rope_dim) == (512, 64), B <= 2^17, strides multiples of 2
+ * with tok_stride >= 1152, N <= capacity, capacity * tok_stride < 1 GiB; anything else: GQ_EUNSUPPORTED.
+ * Null pointers, negative sizes, ldq < n_head*576, ldo < n_head*512 and a workspace that is null, not
+ * 16-byte aligned or below gq_mla_decode_workspace_size(B, N, n_head, rank, rope_dim) (0 for a refused
+ * shape): GQ_EINVAL.  The checks come in gq_attn_decode's order.  B, N or n_head == 0: a no-op.  Every
+ * check precedes the launches.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by
+ * its symbol; gq_version() did not change with it.  No sliding window, no soft-cap, no Q8_0 cache.
+ */
+size_t gq_mla_decode_workspace_size(int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim);
+int gq_mla_decode(const void *Q, int64_t ldq, const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len,
+                  int64_t capacity, void *O, int64_t ldo, float scale, int64_t B, int64_t N, int64_t n_head, int64_t rank,
+                  int64_t rope_dim, void *workspace, size_t workspace_bytes, void *stream);
+/* The plan of that call: the keys per tile, the query rows per group and the workgroups W per (sequence,
+ * group); workgroup w takes tiles [T*w/W, T*(w+1)/W) of the T = ceil(kv_len / tile).  GQ_EUNSUPPORTED: no such shape. */
+int gq_debug_mla_plan(int64_t B, int64_t N, int64_t n_head, int *tile, int *rows_per_group, int *W);
+
+/*
+ * The latent cache's producer, ONE launch per step.  Token i of sequence b has position p = kv_len[b] - N + i,
+ * read on the device.  The cache row of (b, p) becomes [fp16(c * rsqrt(mean_512(c^2) + eps) * norm_w) |
+ * RoPE_p(k_pe)], and every head's q_pe, rotated by the same angle, goes to Qout + row*ldqo + head*576 + 512:
+ * the rope part of gq_mla_decode's Q, beside the absorbed part the caller writes.
+ *   Ckv    : fp16 (B*N, 512), rows ldc apart;  Kpe: fp16 (B*N, 64), rows ldk apart -- both may be column
+ *            slices of the attn_kv_a_mqa output.  norm_w: fp32 (512) in device memory (attn_kv_a_norm).
+ *   Qpe    : fp16, head h's 64 values of row t at element t*ldqp + h*q_head_stride: the last 64 columns
+ *            of every 192-wide q head, say (Qpe = q + 128, q_head_stride = 192).
+ *   mode, inv_freq (fp32 (32)), mscale : gq_rope_append's, with n_rot = 64; its fp64 angle and its bounds:
+ *            a rotated element within 2^-11 |exact| + 2^-25 + 2^-19 mscale (|y0| + |y1|), a c_kv element
+ *            within 2^-11 |y| + 2^-25 + 2^-16 |y| of the float64 formula.
+ * A position outside [0, capacity) is the caller's error: that token's cache row is skipped, its q_pe is
+ * still rotated.  Nothing else is written.  Checks as gq_mla_decode's, with any N <= capacity (B*N < 2^31);
+ * besides: a null pointer, ldc < 512, ldk < 64, q_head_stride < 64, ldqp < (n_head-1)*q_head_stride + 64,
+ * ldqo < n_head*576: GQ_EINVAL; an unknown mode: GQ_EUNSUPPORTED.  B, N or n_head == 0: a no-op.
+ * Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol.
+ */
+int gq_mla_append(gq_rope_mode mode, const void *Ckv, int64_t ldc, const void *Kpe, int64_t ldk, const void *Qpe, int64_t ldqp,
+                  int64_t q_head_stride, void *Qout, int64_t ldqo, void *C, int64_t tok_stride, int64_t seq_stride,
+                  const int32_t *kv_len, int64_t capacity, const float *inv_freq, float mscale, const float *norm_w, float eps,
+                  int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim, void *stream);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE

@@ -41,6 +41,15 @@ D 256) at decode over 32768 cached tokens and at a prefill of 8192; then, at Lla
 Gemma-2-9B heads (D 256), decode with window 1024 over 2048, 8192 and 32768 cached tokens beside the
 yardstick, the plain call over a cache of 1024 tokens.  torch SDPA is the base everywhere (the window as a
 boolean mask).  A windowed cell's bytes are the window's rows; its copies rotate like any other cell's.
+
+    python tools/attn_bench.py --mla [--out profiles/attn_mla_bench.json]
+
+DeepSeek's absorbed latent attention (kernels._lib.mla_decode: gq_mla_decode) over an fp16 latent cache of
+[c_kv (512) | k_pe (64)] rows, 128 heads (V3, R1) and 16 (V2-Lite), B in {1, 4}, N in {1, 4}, kv_len in {512,
+4096, 32768}, beside torch over the same cache sliced to the length: softmax(q C^T) C[:, :512] in fp16 (two
+matmuls and a masked softmax; MlaCase).  A cell is the median time of both forms, their spread, and the live
+cache bytes (read ONCE: 1152 per position) per second against the HBM figure; every 128-head cell also
+carries its time over the 16-head cell's: what the repeated stream of its row groups costs.
 """
 import argparse
 import json
@@ -145,6 +154,81 @@ class PrefillCase:
         return o
 
     check = Case.check
+
+
+class MlaCase:
+    def __init__(self, nh, N, B, L, dev, steps):
+        import kernels._lib as kl
+        self.kl, self.dev, self.dims = kl, dev, (nh, N, B, L)
+        self.live = {"f16": B * L * 1152}
+        ncopies, self.plans = bench.rotation_plan(self.live["f16"], steps)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        rnd = lambda *s: torch.randn(s, device=dev, generator=gen).to(torch.float16)  # noqa: E731
+        self.c = [rnd(B, L, 576) for _ in range(ncopies)]
+        self.q = rnd(B * N, nh * 576)
+        self.kv_len = torch.full((B,), L, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(kl.mla_workspace_size(B, N, nh), dtype=torch.uint8, device=dev)
+        self.out = torch.empty(B * N, nh * 512, dtype=torch.float16, device=dev)
+        self.mask = None if N == 1 else ~torch.ones(N, L, dtype=torch.bool, device=dev).tril(L - N)
+        self.scale = 192 ** -0.5
+
+    def step(self, form, c, i):
+        nh, N, B, L = self.dims
+        if form == "torch":
+            C = self.c[c]                                                       # (B, L, 576)
+            s = torch.matmul(self.q.view(B, N * nh, 576), C.transpose(1, 2)) * self.scale
+            if self.mask is not None:
+                s = s.view(B, N, nh, L).masked_fill(self.mask[None, :, None, :], float("-inf")).view(B, N * nh, L)
+            return torch.matmul(torch.softmax(s, dim=-1), C[:, :, :512]).reshape(B * N, nh * 512)
+        return self.kl.mla_decode(self.q, self.c[c], (1152, L * 1152), self.kv_len, L, B, N, nh, self.ws, self.scale, out=self.out)
+
+    def check(self):
+        a, b = self.step("torch", 0, 0).float(), self.step("f16", 0, 0).float()
+        torch.cuda.synchronize(self.dev)
+        d = float((a - b).abs().max() / a.abs().max())
+        assert d <= 1e-2, d
+        return d
+
+
+def main_mla(a, dev):
+    rows, forms, base = [], ("torch", "f16"), {}
+    for nh in (16, 128):
+        for L in (512, 4096, 32768):
+            for B in (1, 4):
+                for N in (1, 4):
+                    if L > a.max_len:
+                        continue
+                    case = MlaCase(nh, N, B, L, dev, a.steps)
+                    diff = case.check()
+                    gs = {f: graphs(case, f) for f in forms}
+                    ts = {f: [] for f in forms}
+                    for _ in range(a.repeats):  # interleaved: one pass over the forms per repeat
+                        for f in forms:
+                            ts[f].append(bench.timed_rotation(gs[f], dev) / a.steps * 1e6)
+                    tile, grows, W = case.kl.mla_plan(B, N, nh)
+                    row = {"heads": nh, "N": N, "B": B, "kv_len": L, "W": W, "row_groups": -(-N * nh // grows),
+                           "f16_vs_torch_max_rel_diff": round(diff, 5)}
+                    for f in forms:
+                        us = float(np.median(ts[f]))
+                        gbs = case.live["f16"] / us / 1e3
+                        row[f] = {"us": round(us, 2), "spread_us": round(max(ts[f]) - min(ts[f]), 2), "cache_GBs": round(gbs, 1),
+                                  "hbm_frac": round(gbs / bench.HBM_PEAK_GBS, 4)}
+                    if nh == 16:
+                        base[(N, B, L)] = row["f16"]["us"]
+                    else:
+                        row["f16_us_over_16_heads"] = round(row["f16"]["us"] / base[(N, B, L)], 2)
+                    rows.append(row)
+                    print(json.dumps(row), flush=True)
+                    del case, gs
+                    torch.cuda.empty_cache()
+                    if a.out:  # (after every cell: a run cut short keeps what it measured)
+                        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                        with open(a.out, "w") as f:
+                            json.dump({"steps": a.steps, "repeats": a.repeats, "hbm_peak_GBs": bench.HBM_PEAK_GBS,
+                                       "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count,
+                                       "not_measured": "two ring slots against three, blockIdx in plain order against the "
+                                                       "die-aware one, any profile (no counters were collected)",
+                                       "rows": rows}, f, indent=1)
 
 
 ROPE_HEADS = {"llama3_8b": (32, 8, 128, "norm", False), "qwen3_8b": (32, 8, 128, "neox", True)}
@@ -360,11 +444,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--prefill", action="store_true", help="prefill attention (attn_prefill) instead of decode")
     ap.add_argument("--gemma", action="store_true", help="head dim 256 and windowed decode (Gemma-2-9B heads; window 1024)")
+    ap.add_argument("--mla", action="store_true", help="DeepSeek's latent attention at decode (mla_decode) beside torch matmuls")
     ap.add_argument("--rope", action="store_true", help="the fused norm + RoPE + append (rope_append) beside torch RoPE + kv_append")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("attn_bench.py needs a ROCm device: there is no CPU timing path")
     dev = torch.device("cuda:0")
+    if a.mla:
+        return main_mla(a, dev)
     if a.prefill:
         return main_prefill(a, dev)
     if a.rope:
