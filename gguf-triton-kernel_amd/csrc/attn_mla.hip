@@ -67,22 +67,20 @@
 #include "gguf_blocks.hpp"
 #include "gguf_internal.hpp"
 #include "gguf_mfma.hpp"
+#include "gguf_mla.hpp"
 #include "gguf_rope.hpp"
 
 namespace gq {
 namespace {
 
-constexpr int kWaves = 4;
-constexpr int kRank = kMlaRank, kRope = kMlaRope, kDk = kRank + kRope;
-constexpr int kRowB = 2 * kDk;                             // 1152 bytes of a cache row
-constexpr int kPPR = kRowB / 16;                           // 72 16-byte pieces per row
-constexpr int kNI = kMlaTile * kPPR / (64 * kWaves);       // 9 DMAs per lane and tile
-constexpr int kTileB = kMlaTile * kRowB;                   // 36 KiB
-constexpr int kKS = kDk / 32, kNG = kRank / 16;            // k-steps of the first product, column groups of the second
+// the tile geometry, the swizzle and the DMA and fragment addressing are gguf_mla.hpp's (shared with attn_mla_prefill.hip)
+constexpr int kWaves = kMlaWaves;
+constexpr int kRank = kMlaRank, kRope = kMlaRope, kDk = kMlaDk;
+constexpr int kRowB = kMlaRowB, kNI = kMlaNI, kTileB = kMlaTileB, kKS = kMlaKS, kNG = kMlaNG;
 constexpr int kMlaXcd = 8;                                 // dies that take workgroup ids in turn
 constexpr float kNegInf = -__builtin_huge_valf();
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-static_assert(kMlaTile == 32 && kMlaRows == 16 * kWaves && kMlaTile * kPPR % (64 * kWaves) == 0 && kTileB % 256 == 0, "tile geometry");
+static_assert(kMlaRows == 16 * kWaves, "one 16-row MFMA tile per wave");
 
 struct MlaArgs {
     const uint16_t *Q;
@@ -97,9 +95,6 @@ struct MlaArgs {
 
 // floats of one workgroup's partial: o[64][512], then (m, l)[64]
 constexpr int64_t kSlotF = (int64_t)kMlaRows * kRank + 2 * kMlaRows;
-
-// LDS piece of source piece p of tile row r (an involution: the DMA uses it the other way round)
-__device__ __forceinline__ int mla_piece(int p, int r) { return p ^ ((r >> 1) & 7); }
 
 __global__ __launch_bounds__(256) void mla_decode_kernel(const MlaArgs a)
 {
@@ -148,11 +143,7 @@ __global__ __launch_bounds__(256) void mla_decode_kernel(const MlaArgs a)
     int drow[kNI];
     uint32_t doff[kNI];
 #pragma unroll
-    for (int k = 0; k < kNI; ++k) {
-        const int s = 256 * k + tid, row = s / kPPR, p = s - row * kPPR;
-        drow[k] = row;
-        doff[k] = (uint32_t)row * (uint32_t)a.tok_stride + 16u * (uint32_t)mla_piece(p, row);
-    }
+    for (int k = 0; k < kNI; ++k) mla_dma_piece(k, tid, a.tok_stride, drow[k], doff[k]);
     auto issue = [&](int t) { // tile t into slot (t - t0) % kMlaSlots; t >= t1: zeros, the same count
         uint8_t *dst = smem + ((t - t0) % kMlaSlots) * kTileB + 1024 * wave;
         const uint32_t tb = (uint32_t)t * kMlaTile * (uint32_t)a.tok_stride;
@@ -173,18 +164,13 @@ __global__ __launch_bounds__(256) void mla_decode_kernel(const MlaArgs a)
 #pragma unroll
     for (int jj = 0; jj < 8; ++jj) vrow[jj] = jj < 4 ? 4 * g + jj : 12 + 4 * g + jj;
 
-    // LDS offsets within a tile.  The swizzle's row term is the same for a lane's rows 16u + c, (c >> 1) & 7, and
-    // for its rows 16u + 4g + c / 4 of the transposing read, 2g + (c >> 3); it touches a piece's low 3 bits only,
-    // so pieces 8j + x of a row lie 128 j bytes apart whatever the lane: two bases serve the first product's 18
-    // k-steps and four the second's 32 column groups, everything else is an immediate offset.
+    // LDS offsets within a tile (gguf_mla.hpp): two bases serve the first product's 18 k-steps and four the
+    // second's 32 column groups, everything else is an immediate offset
     uint32_t kbase[2], vbase[4];
 #pragma unroll
-    for (int e = 0; e < 2; ++e) kbase[e] = (uint32_t)(c * kRowB + 16 * mla_piece(4 * e + g, c));
+    for (int e = 0; e < 2; ++e) kbase[e] = mla_kbase(e, g, c);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = 4 * g + (c >> 2);
-        vbase[i] = (uint32_t)(row * kRowB + 16 * mla_piece(2 * i + ((c >> 1) & 1), row) + 8 * (c & 1));
-    }
+    for (int i = 0; i < 4; ++i) vbase[i] = mla_vbase(i, g, c);
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // Q has arrived: from here vmcnt counts DMAs only
 #pragma unroll

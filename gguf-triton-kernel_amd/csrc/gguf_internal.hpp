@@ -185,6 +185,18 @@ struct MlaCall {
 };
 MlaPlan plan_mla(int64_t B, int64_t N, int64_t n_head);
 hipError_t launch_mla_decode(const MlaCall &c, const MlaPlan &p, hipStream_t s);
+// The same attention for any N, in attn_prefill.hip's split (attn_mla_prefill.hip; gq_mla_prefill): one launch
+// of B * nblk workgroups, each kMlaPrefillRows consecutive query rows of one sequence over the same ring of
+// kMlaSlots kMlaTile-key tiles; no workspace (c.workspace unused).  kMlaPrefillRows is one 16-row MFMA tile
+// per wave: the 32-row form does not fit the registers (attn_mla_prefill.hip).
+constexpr int kMlaPrefillRows = 64;
+struct MlaPrefillPlan {
+    bool ok = false;           // 1 <= n_head <= 128, B <= 2^17, B * N * n_head < 2^31
+    int nblk = 0;              // row blocks per sequence
+    int64_t grid = 0;
+};
+MlaPrefillPlan plan_mla_prefill(int64_t B, int64_t N, int64_t n_head);
+hipError_t launch_mla_prefill(const MlaCall &c, const MlaPrefillPlan &p, hipStream_t s);
 // The N new tokens' normalised c_kv and rotated k_pe into that cache, and every head's rotated q_pe into
 // the rope part of gq_mla_decode's Q (attn_mla.hip; gq_mla_append).  mode: gq_rope_mode.
 struct MlaAppendCall {

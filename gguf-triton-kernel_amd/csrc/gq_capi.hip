@@ -1688,9 +1688,9 @@ int gq_rope_append(gq_kv_type kv, gq_rope_mode mode, const void *Q, int64_t ldq,
 }
 
 // ---- multi-head latent attention (attn_mla.hip) ----
-// The checks gq_mla_decode and gq_mla_append share, in check_kv_cache's order with its wording where the
+// The checks gq_mla_decode, gq_mla_prefill and gq_mla_append share, in check_kv_cache's order with its wording where the
 // condition is the same: the sizes, then (not empty) the shape and the cache geometry.  decode: the call is
-// held to gq_mla_decode's N.
+// held to gq_mla_decode's N (gq_mla_prefill and gq_mla_append take any N the cache holds).
 static int check_mla_cache(int64_t tok_stride, int64_t seq_stride, int64_t capacity, int64_t B, int64_t N, int64_t n_head,
                            int64_t rank, int64_t rope_dim, bool decode, bool &empty)
 {
@@ -1752,6 +1752,38 @@ int gq_mla_decode(const void *Q, int64_t ldq, const void *C, int64_t tok_stride,
     if (((uintptr_t)workspace & 15) != 0) return fail(GQ_EINVAL, "the workspace must be 16-byte aligned");
     const gq::MlaCall c{Q, C, kv_len, O, workspace, ldq, ldo, tok_stride, seq_stride, capacity, B, N, n_head, scale};
     return hip_rc(gq::launch_mla_decode(c, p, (hipStream_t)stream), "mla_decode");
+}
+
+int gq_debug_mla_prefill_plan(int64_t B, int64_t N, int64_t n_head, int *tile, int *rows_per_block, int64_t *grid)
+{
+    g_err.clear();
+    const gq::MlaPrefillPlan p = gq::plan_mla_prefill(B, N, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "not an MLA prefill shape");
+    if (tile) *tile = gq::kMlaTile;
+    if (rows_per_block) *rows_per_block = gq::kMlaPrefillRows;
+    if (grid) *grid = p.grid;
+    return GQ_OK;
+}
+
+int gq_mla_prefill(const void *Q, int64_t ldq, const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len,
+                   int64_t capacity, void *O, int64_t ldo, float scale, int64_t B, int64_t N, int64_t n_head, int64_t rank,
+                   int64_t rope_dim, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    // (gq_mla_decode's checks in its order, without the workspace's and its bound on N)
+    if (B >= 0 && N >= 0 && n_head > 0 && rank >= 0 && rope_dim >= 0 && B * N > 0) {
+        if (!Q || !C || !kv_len || !O) return fail(GQ_EINVAL, "null pointer (Q=%p C=%p kv_len=%p O=%p)", Q, C, (const void *)kv_len, O);
+        if (ldq < n_head * (rank + rope_dim))
+            return fail(GQ_EINVAL, "ldq=%lld < n_head*(rank+rope_dim)=%lld", (long long)ldq, (long long)(n_head * (rank + rope_dim)));
+        if (ldo < n_head * rank) return fail(GQ_EINVAL, "ldo=%lld < n_head*rank=%lld", (long long)ldo, (long long)(n_head * rank));
+    }
+    const int rc = check_mla_cache(tok_stride, seq_stride, capacity, B, N, n_head, rank, rope_dim, false, empty);
+    if (rc != GQ_OK || empty) return rc;
+    const gq::MlaPrefillPlan p = gq::plan_mla_prefill(B, N, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "B * N * n_head = %lld query rows is 2^31 or more", (long long)(B * N * n_head));
+    const gq::MlaCall c{Q, C, kv_len, O, nullptr, ldq, ldo, tok_stride, seq_stride, capacity, B, N, n_head, scale};
+    return hip_rc(gq::launch_mla_prefill(c, p, (hipStream_t)stream), "mla_prefill");
 }
 
 int gq_mla_append(gq_rope_mode mode, const void *Ckv, int64_t ldc, const void *Kpe, int64_t ldk, const void *Qpe, int64_t ldqp,

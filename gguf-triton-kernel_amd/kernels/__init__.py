@@ -23,13 +23,14 @@ and the rotary embedding (with the per-head q/k norm) fused into the append:
 
     from kernels import RoPE, rope_append
 
-and DeepSeek's multi-head latent attention at decode over a latent cache (gq_mla_decode, gq_mla_append):
+and DeepSeek's multi-head latent attention over a latent cache, at decode and over a prompt (gq_mla_decode,
+gq_mla_prefill, gq_mla_append):
 
-    from kernels import MLACache, MLAttention, mla_decode, mla_append
+    from kernels import MLACache, MLAttention, mla_decode, mla_prefill, mla_append
 """
 _LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib", "RoPE": "attention",
          "rope_append": "_lib", "attn_options": "attention", "MLACache": "attention", "MLAttention": "attention",
-         "mla_decode": "_lib", "mla_append": "_lib"}
+         "mla_decode": "_lib", "mla_prefill": "_lib", "mla_append": "_lib"}
 __all__ = list(_LAZY)
 
 

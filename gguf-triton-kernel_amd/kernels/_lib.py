@@ -123,6 +123,9 @@ SIGNATURES = {
     "gq_mla_decode": ([_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P, _SZ, _P], _I),
     "gq_debug_mla_plan": ([_I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                            ctypes.POINTER(ctypes.c_int)], _I),
+    "gq_mla_prefill": ([_P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_debug_mla_prefill_plan": ([_I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                   ctypes.POINTER(ctypes.c_int64)], _I),
     "gq_mla_append": ([_I, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, ctypes.c_float, _P,
                        ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
@@ -1182,6 +1185,32 @@ def mla_decode(q: torch.Tensor, C: torch.Tensor, strides, kv_len: torch.Tensor, 
         _check(lib().gq_mla_decode(q.data_ptr(), ldq, C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(), capacity,
                                    out.data_ptr(), ldo, float(scale), B, N, n_head, rank, rope_dim, workspace.data_ptr(),
                                    workspace.numel(), _stream(dev)))
+    return out
+
+
+def mla_prefill_plan(B: int, N: int, n_head: int):
+    """(keys per tile, query rows per workgroup, workgroups) of an mla_prefill call (gq_debug_mla_prefill_plan)."""
+    tile, rows, grid = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _check(lib().gq_debug_mla_prefill_plan(B, N, n_head, ctypes.byref(tile), ctypes.byref(rows), ctypes.byref(grid)))
+    return tile.value, rows.value, grid.value
+
+
+def mla_prefill(q: torch.Tensor, C: torch.Tensor, strides, kv_len: torch.Tensor, capacity: int, B: int, N: int, n_head: int,
+                scale: float, out: torch.Tensor | None = None, rank: int = MLA_RANK, rope_dim: int = MLA_ROPE,
+                kv_offset: int = 0) -> torch.Tensor:
+    """mla_decode's attention for any N new tokens of B sequences -- a prompt, a chunk, a verification -- in one
+    launch without a workspace (gq_mla_prefill); the arguments are mla_decode's.  No host sync, no fallback."""
+    _require_device(q, "q")
+    dev = q.device
+    ldq = _kv_rows(q, "q", B * N, n_head * (rank + rope_dim), dev)
+    _kv_caches(C, C, kv_len, B, dev)
+    if out is None:
+        out = torch.empty((B * N, n_head * rank), dtype=torch.float16, device=dev)
+    ldo = _kv_rows(out, "out", B * N, n_head * rank, dev)
+    tok, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_mla_prefill(q.data_ptr(), ldq, C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(), capacity,
+                                    out.data_ptr(), ldo, float(scale), B, N, n_head, rank, rope_dim, _stream(dev)))
     return out
 
 

@@ -202,13 +202,17 @@ class KVCache:
                                 self.n_kv_head, self.D, ws, scale, out, window=window, softcap=softcap)
 
 
+MLA_DECODE_MAX_N = 4  # gq_mla_decode's limit on the new tokens of a step; more go to gq_mla_prefill
+
+
 class MLACache:
     """The latent cache of one DeepSeek-V2/V3 (multi-head latent attention) layer: ONE fp16 row of rank +
     rope_dim values [c_kv | k_pe] per (sequence, position), at byte (b*capacity + t) * 2 * (rank + rope_dim),
     shared by every query head as key and value.  kv_len: int32 (B) on the device.  append and attend are
-    gq_mla_append and gq_mla_decode: up to 4 new tokens a step and up to 128 heads; neither syncs the host,
-    and neither allocates after the first call at a given (N, n_head), so one captured graph of a step
-    serves every length up to the capacity.  No fallback: a shape the library refuses raises."""
+    gq_mla_append and, up to 4 new tokens, gq_mla_decode; beyond -- a prompt, a chunk of one, a speculative
+    verification -- gq_mla_prefill; up to 128 heads.  None syncs the host, and none allocates after the first
+    call at a given (N, n_head), so one captured graph of a step serves every length up to the capacity.  No
+    fallback: a shape the library refuses raises."""
 
     def __init__(self, B: int, capacity: int, rank: int = _lib.MLA_RANK, rope_dim: int = _lib.MLA_ROPE, device="cuda"):
         if (rank, rope_dim) != (_lib.MLA_RANK, _lib.MLA_ROPE):
@@ -220,7 +224,7 @@ class MLACache:
         self.strides = (rb, capacity * rb)  # (tok, seq) bytes
         self.c = torch.zeros(B * capacity * rb, dtype=torch.uint8, device=device)
         self.kv_len = torch.zeros(B, dtype=torch.int32, device=device)
-        self._bufs = {}  # (N, n_head) -> (q [q_abs | q_pe] rows, workspace, output)
+        self._bufs = {}  # (N, n_head) -> (q [q_abs | q_pe] rows, decode's workspace or None, output)
         self._n = 0      # the last append's token count: attend's N
 
     def reset(self):
@@ -231,9 +235,12 @@ class MLACache:
         bufs = self._bufs.get((N, n_head))
         if bufs is None:
             dev, T = self.c.device, self.B * N
-            need = _lib.mla_workspace_size(self.B, N, n_head, self.rank, self.rope_dim)
+            ws = None  # (the prefill route has no workspace)
+            if N <= MLA_DECODE_MAX_N:
+                need = _lib.mla_workspace_size(self.B, N, n_head, self.rank, self.rope_dim)
+                ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
             bufs = self._bufs[(N, n_head)] = (torch.zeros(T, n_head * (self.rank + self.rope_dim), dtype=torch.float16, device=dev),
-                                              torch.empty(max(need, 16), dtype=torch.uint8, device=dev),
+                                              ws,
                                               torch.empty(T, n_head * self.rank, dtype=torch.float16, device=dev))
         return bufs
 
@@ -265,13 +272,16 @@ class MLACache:
             raise ValueError(f"q has {q.shape[0]} rows; the last append wrote {self._n} tokens for each of {self.B} sequences")
         n_head = q.shape[1] // (self.rank + self.rope_dim)
         _, ws, out = self._for(N, n_head)
+        if N > MLA_DECODE_MAX_N:
+            return _lib.mla_prefill(q, self.c, self.strides, self.kv_len, self.capacity, self.B, N, n_head, scale, out,
+                                    self.rank, self.rope_dim)
         return _lib.mla_decode(q, self.c, self.strides, self.kv_len, self.capacity, self.B, N, n_head, ws, scale, out,
                                self.rank, self.rope_dim)
 
 
 class MLAttention:
-    """A DeepSeek-V2/V3 layer's attention core at decode, between the q / attn_kv_a_mqa projections and
-    attn_output: the absorption of W_UK into q (a torch bmm on dequantized weights), MLACache.append,
+    """A DeepSeek-V2/V3 layer's attention core, at decode and over a prompt alike, between the q / attn_kv_a_mqa
+    projections and attn_output: the absorption of W_UK into q (a torch bmm on dequantized weights), MLACache.append,
     MLACache.attend, and the product with W_UV (a second bmm).  The two bmm are the caller's matmuls in the
     C ABI; a HIP form of them is not part of the library yet.  k_b: fp16 (n_head, rank, nope), v_b: fp16
     (n_head, v_dim, rank)."""

@@ -35,6 +35,7 @@
  *   gq_kv_append                        the new tokens' k and v rows into that cache, on the device
  *   gq_rope_append                      per-head norm + RoPE of q and k, then that append, in one launch
  *   gq_mla_decode, gq_mla_append        DeepSeek's latent attention (MLA) at decode and its latent cache's producer
+ *   gq_mla_prefill                      the same attention for a prompt or a chunk of one: any number of new tokens, one launch
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -738,6 +739,32 @@ int gq_mla_decode(const void *Q, int64_t ldq, const void *C, int64_t tok_stride,
 /* The plan of that call: the keys per tile, the query rows per group and the workgroups W per (sequence,
  * group); workgroup w takes tiles [T*w/W, T*(w+1)/W) of the T = ceil(kv_len / tile).  GQ_EUNSUPPORTED: no such shape. */
 int gq_debug_mla_plan(int64_t B, int64_t N, int64_t n_head, int *tile, int *rows_per_group, int *W);
+
+/*
+ * gq_mla_decode's attention for ANY number of new tokens: a prompt, a chunk of one after a prefix, a speculative
+ * verification.  Q, C, tok_stride, seq_stride, kv_len, capacity, O, scale, rank and rope_dim mean what they mean
+ * there, and so do the row order, the positions (query token i attends 0 .. kv_len[b] - N + i), the arithmetic
+ * and the bound |o - exact| <= 2^-9 * max|c_kv| over the attended positions; the bits of an output row are not
+ * promised to be gq_mla_decode's.  Positions at or beyond kv_len[b] are never used, whatever bytes they hold;
+ * the length is clamped to [0, capacity]; a sequence's output depends neither on B nor on the other sequences.
+ * ONE launch, no workspace, nothing split along the keys: B * ceil(N*n_head/64) workgroups, each 64 consecutive
+ * query rows of one sequence, walking the 32-key tiles up to its last row's position and no further; the
+ * blocks with the most keys start first.  The grid depends on no length.  Few rows over a long cache (N = 8
+ * with 16 heads: two workgroups a sequence) underfill the chip: there gq_mla_decode's key split, N <= 4 at a
+ * time, is the other choice.
+ * Shapes: 1 <= N <= capacity (N <= 4 included), 1 <= n_head <= 128, (rank, rope_dim) == (512, 64), B <= 2^17,
+ * B*N*n_head < 2^31, strides multiples of 2 with tok_stride >= 1152, capacity * tok_stride < 1 GiB; anything
+ * else: GQ_EUNSUPPORTED.  Null pointers, negative sizes, ldq < n_head*576, ldo < n_head*512: GQ_EINVAL.  The
+ * checks come in gq_mla_decode's order with its messages.  B, N or n_head == 0: a no-op.  Every check precedes
+ * the launch.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected by its symbol;
+ * gq_version() did not change with it.  No sliding window, no soft-cap, no Q8_0 cache.
+ */
+int gq_mla_prefill(const void *Q, int64_t ldq, const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len,
+                   int64_t capacity, void *O, int64_t ldo, float scale, int64_t B, int64_t N, int64_t n_head, int64_t rank,
+                   int64_t rope_dim, void *stream);
+/* The plan of that call: the keys per tile, the query rows per workgroup and the grid B * ceil(N*n_head / rows);
+ * block k of a sequence holds rows [k*rows, (k+1)*rows).  GQ_EUNSUPPORTED: no such shape. */
+int gq_debug_mla_prefill_plan(int64_t B, int64_t N, int64_t n_head, int *tile, int *rows_per_block, int64_t *grid);
 
 /*
  * The latent cache's producer, ONE launch per step.  Token i of sequence b has position p = kv_len[b] - N + i,

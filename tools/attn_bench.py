@@ -50,6 +50,14 @@ DeepSeek's absorbed latent attention (kernels._lib.mla_decode: gq_mla_decode) ov
 matmuls and a masked softmax; MlaCase).  A cell is the median time of both forms, their spread, and the live
 cache bytes (read ONCE: 1152 per position) per second against the HBM figure; every 128-head cell also
 carries its time over the 16-head cell's: what the repeated stream of its row groups costs.
+
+    python tools/attn_bench.py --mla-prefill [--out profiles/attn_mla_prefill_bench.json]
+
+The same attention over a prompt or a chunk of one (kernels._lib.mla_prefill: gq_mla_prefill), 16 and 128 heads,
+N in {16, 512, 4096} without a prefix and N = 512 after a prefix of 4096, B in {1, 4}, beside two bases: torch
+fp16 softmax(mask(q C^T)) C[:, :512] over the same cache, and what the library offered before -- a loop of
+mla_decode at four tokens a step, each step at its own length -- all three as captured graphs (MlaPrefillCase).
+A cell is the median time of each form and the causal TFLOP/s at 2 * (576 + 512) flops per attended (row, key).
 """
 import argparse
 import json
@@ -231,6 +239,97 @@ def main_mla(a, dev):
                                        "rows": rows}, f, indent=1)
 
 
+class MlaPrefillCase:
+    """N new tokens after a prefix of P per sequence over a latent cache exactly P + N long.  The caches rotate as
+    in PrefillCase (every copy the same values), over at most 256 copies: a cache below 4 MiB is not the cost."""
+    forms = ("torch", "f16", "decode_x4")
+
+    def __init__(self, nh, N, B, P, dev, steps):
+        import kernels._lib as kl
+        L = P + N
+        self.kl, self.dev, self.dims, self.scale = kl, dev, (nh, N, B, L), 192 ** -0.5
+        ncopies, self.plans = bench.rotation_plan(max(B * L * 1152, bench.ROTATE_BYTES // 256), steps)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        rnd = lambda *s: torch.randn(s, device=dev, generator=gen).to(torch.float16)  # noqa: E731
+        self.c = rnd(B, L, 576).expand(ncopies, B, L, 576).contiguous().unbind(0)
+        self.q = rnd(B * N, nh * 576)
+        self.kv_len = torch.full((B,), L, dtype=torch.int32, device=dev)
+        self.out = torch.empty(B * N, nh * 512, dtype=torch.float16, device=dev)
+        self.mask = ~torch.ones(N, L, dtype=torch.bool, device=dev).tril(P)
+        self.flops = 2.0 * (576 + 512) * B * nh * (N * P + N * (N + 1) // 2)
+        # the loop of decode steps: step j's tokens 4j .. as rows of their own, at the length that ends with them
+        self.steps4 = [(self.q.view(B, N, -1)[:, j:j + 4].reshape(-1, nh * 576).contiguous(),
+                        torch.full((B,), P + min(j + 4, N), dtype=torch.int32, device=dev)) for j in range(0, N, 4)]
+        self.ws = torch.empty(kl.mla_workspace_size(B, 4, nh), dtype=torch.uint8, device=dev)
+        self.out4 = torch.empty(B * 4, nh * 512, dtype=torch.float16, device=dev)
+
+    def step(self, form, c, i):
+        nh, N, B, L = self.dims
+        C = self.c[c]
+        if form == "torch":
+            s = torch.matmul(self.q.view(B, N * nh, 576), C.transpose(1, 2)) * self.scale
+            s = s.view(B, N, nh, L).masked_fill_(self.mask[None, :, None, :], float("-inf")).view(B, N * nh, L)
+            return torch.matmul(torch.softmax(s, dim=-1), C[:, :, :512]).view(B, N, nh * 512).reshape(B * N, nh * 512)
+        if form == "f16":
+            return self.kl.mla_prefill(self.q, C, (1152, L * 1152), self.kv_len, L, B, N, nh, self.scale, out=self.out)
+        for q4, len4 in self.steps4:
+            n = q4.shape[0] // B
+            self.kl.mla_decode(q4, C, (1152, L * 1152), len4, L, B, n, nh, self.ws, self.scale, out=self.out4[:B * n])
+        return self.out4
+
+    check = MlaCase.check
+
+
+# (N, prefix)
+MLA_PREFILL_CELLS = [(16, 0), (512, 0), (4096, 0), (512, 4096)]
+
+
+def main_mla_prefill(a, dev):
+    rows, skipped = [], []
+    for nh in (16, 128):
+        for N, P in MLA_PREFILL_CELLS:
+            for B in (1, 4):
+                if P + N > a.max_len:
+                    continue
+                # torch's scores, their masked copy and the probabilities, fp16, beside q and its decode-step copy
+                need = 3 * 2 * B * N * nh * (P + N) + 2 * 2 * B * N * nh * 576
+                if need > 0.5 * torch.cuda.get_device_properties(dev).total_memory:
+                    skipped.append({"heads": nh, "N": N, "prefix": P, "B": B, "why": f"{need >> 30} GiB of torch scores and q"})
+                    continue
+                steps = a.steps if N <= 512 else max(2, a.steps // 5)  # (a 4096-token step is 1024 decode steps)
+                case = MlaPrefillCase(nh, N, B, P, dev, steps)
+                diff = case.check()
+                # (one pool a form: torch's 4 GiB of scores at 128 heads x 4096 tokens, not once per graph)
+                gs = {f: graphs(case, f, torch.cuda.graph_pool_handle()) for f in case.forms}
+                ts = {f: [] for f in case.forms}
+                for _ in range(a.repeats):  # interleaved: one pass over the forms per repeat
+                    for f in case.forms:
+                        ts[f].append(bench.timed_rotation(gs[f], dev) / steps * 1e6)
+                _, rows_wg, grid = case.kl.mla_prefill_plan(B, N, nh)
+                row = {"heads": nh, "B": B, "N": N, "prefix": P, "rows_per_workgroup": rows_wg, "workgroups": grid,
+                       "f16_vs_torch_max_rel_diff": round(diff, 5), "causal_gflop": round(case.flops / 1e9, 2)}
+                for f in case.forms:
+                    us = float(np.median(ts[f]))
+                    tf = case.flops / us / 1e6
+                    row[f] = {"us": round(us, 1), "spread_us": round(max(ts[f]) - min(ts[f]), 1), "causal_TFLOPs": round(tf, 1),
+                              "mfma_frac": round(tf / bench.MFMA_F16_PEAK_TF, 4)}
+                for base in ("torch", "decode_x4"):
+                    row[f"f16_slower_than_{base}"] = bool(row["f16"]["us"] - row[base]["us"] >
+                                                          max(row["f16"]["spread_us"], row[base]["spread_us"]))
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                del case, gs
+                torch.cuda.empty_cache()
+                if a.out:  # (after every cell: a run cut short keeps what it measured)
+                    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                    with open(a.out, "w") as f:
+                        json.dump({"steps": a.steps, "repeats": a.repeats, "mfma_f16_peak_TF": bench.MFMA_F16_PEAK_TF,
+                                   "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count,
+                                   "not_measured": "the die-aware workgroup order, two ring slots against three, a 32-row "
+                                                   "form (it spills), any profile (no counters were collected)",
+                                   "skipped": skipped, "rows": rows}, f, indent=1)
+
+
 ROPE_HEADS = {"llama3_8b": (32, 8, 128, "norm", False), "qwen3_8b": (32, 8, 128, "neox", True)}
 
 
@@ -409,11 +508,12 @@ def main_gemma(a, dev):
         save()
 
 
-def graphs(case, form):
+def graphs(case, form, pool=None):
+    """pool: one memory pool for all the graphs of a form (they replay one after another), or a pool per graph."""
     grs = []
     for plan in case.plans:
         gr = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr):
+        with torch.cuda.graph(gr, pool=pool):
             for i, c in enumerate(plan):
                 case.step(form, c, i)
         grs.append(gr)
@@ -445,6 +545,7 @@ def main():
     ap.add_argument("--prefill", action="store_true", help="prefill attention (attn_prefill) instead of decode")
     ap.add_argument("--gemma", action="store_true", help="head dim 256 and windowed decode (Gemma-2-9B heads; window 1024)")
     ap.add_argument("--mla", action="store_true", help="DeepSeek's latent attention at decode (mla_decode) beside torch matmuls")
+    ap.add_argument("--mla-prefill", action="store_true", help="the latent attention over a prompt (mla_prefill) beside torch and a decode loop")
     ap.add_argument("--rope", action="store_true", help="the fused norm + RoPE + append (rope_append) beside torch RoPE + kv_append")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -452,6 +553,8 @@ def main():
     dev = torch.device("cuda:0")
     if a.mla:
         return main_mla(a, dev)
+    if a.mla_prefill:
+        return main_mla_prefill(a, dev)
     if a.prefill:
         return main_prefill(a, dev)
     if a.rope:
