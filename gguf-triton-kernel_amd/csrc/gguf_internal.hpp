@@ -208,6 +208,27 @@ struct MlaAppendCall {
     float mscale, eps;
 };
 hipError_t launch_mla_append(int mode, const MlaAppendCall &c, hipStream_t s);
+// The per-head products around that attention, Y_h = X_h W_h^T (attn_mla_proj.hip; gq_mla_proj): dir 0 absorbs
+// W_UK (n_head, 512, 128) into q_nope, dir 1 expands the attention output by W_UV (n_head, 128, 512).  One launch
+// in one of two forms, chosen from T and n_head alone: form 0 up to kMlaProjFewRows tokens (one MFMA tile; W
+// streamed once into the A operand, tpw 16-row tiles of W per workgroup), form 1 beyond (a workgroup per head and
+// kMlaProjTileRows tokens, W through an LDS ring of kMlaProjSlots stages of kMlaProjStageB bytes).  Neither
+// constant was measured against another value.
+constexpr int kMlaProjDim = 128;          // nope (dir 0) and v_dim (dir 1): the one value that is instantiated
+constexpr int kMlaProjFewRows = 16, kMlaProjTileRows = 64;
+constexpr int kMlaProjStageB = 16384, kMlaProjSlots = 3;
+struct MlaProjPlan {
+    bool ok = false;           // dir 0 or 1, 1 <= n_head <= 128, T * n_head < 2^31
+    int form = 0, rows = 0, tpw = 0;
+    int64_t grid = 0;
+};
+struct MlaProjCall {
+    const void *W, *X;
+    void *Y;
+    int64_t ldx, x_head_stride, ldy, y_head_stride, T, n_head;
+};
+MlaProjPlan plan_mla_proj(int dir, int64_t T, int64_t n_head);
+hipError_t launch_mla_proj(int dir, const MlaProjCall &c, const MlaProjPlan &p, hipStream_t s);
 
 // Decode-shaped GEMV (mmq_gemv.hip): C[t][m] for t < N_tok <= 8 from SOA activations.
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,

@@ -1816,6 +1816,50 @@ int gq_mla_append(gq_rope_mode mode, const void *Ckv, int64_t ldc, const void *K
     return hip_rc(gq::launch_mla_append(mode == GQ_ROPE_NEOX, c, (hipStream_t)stream), "mla_append");
 }
 
+// ---- the latent projections around that attention (attn_mla_proj.hip) ----
+int gq_debug_mla_proj_plan(int dir, int64_t T, int64_t n_head, int *form, int *rows_per_block, int64_t *grid)
+{
+    g_err.clear();
+    const gq::MlaProjPlan p = gq::plan_mla_proj(dir, T, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "not an MLA projection shape");
+    if (form) *form = p.form;
+    if (rows_per_block) *rows_per_block = p.rows;
+    if (grid) *grid = p.grid;
+    return GQ_OK;
+}
+
+int gq_mla_proj(int dir, const void *W, const void *X, int64_t ldx, int64_t x_head_stride, void *Y, int64_t ldy,
+                int64_t y_head_stride, int64_t T, int64_t n_head, int64_t rank, int64_t dim, void *stream)
+{
+    g_err.clear();
+    if (T < 0 || n_head < 0 || rank < 0 || dim < 0)
+        return fail(GQ_EINVAL, "negative size T=%lld n_head=%lld rank=%lld dim=%lld", (long long)T, (long long)n_head,
+                    (long long)rank, (long long)dim);
+    if (T == 0 || n_head == 0) return GQ_OK;
+    if (!W || !X || !Y) return fail(GQ_EINVAL, "null pointer (W=%p X=%p Y=%p)", W, X, Y);
+    if (dir != 0 && dir != 1) return fail(GQ_EUNSUPPORTED, "unknown direction %d (0 absorb, 1 expand)", dir);
+    if (rank != gq::kMlaRank || dim != gq::kMlaProjDim)
+        return fail(GQ_EUNSUPPORTED, "(rank, dim) = (%lld, %lld) is not (512, 128)", (long long)rank, (long long)dim);
+    if (n_head > gq::kMlaMaxHeads) return fail(GQ_EUNSUPPORTED, "n_head=%lld heads, at most 128", (long long)n_head);
+    const gq::MlaProjPlan p = gq::plan_mla_proj(dir, T, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "T * n_head = %lld * %lld rows is 2^31 or more", (long long)T, (long long)n_head);
+    const int64_t kc = dir ? rank : dim, mo = dir ? dim : rank;
+    if (x_head_stride < kc) return fail(GQ_EINVAL, "x_head_stride=%lld < %lld", (long long)x_head_stride, (long long)kc);
+    if (y_head_stride < mo) return fail(GQ_EINVAL, "y_head_stride=%lld < %lld", (long long)y_head_stride, (long long)mo);
+    if (ldx < (n_head - 1) * x_head_stride + kc)
+        return fail(GQ_EINVAL, "ldx=%lld < (n_head-1)*x_head_stride+%lld=%lld", (long long)ldx, (long long)kc,
+                    (long long)((n_head - 1) * x_head_stride + kc));
+    if (ldy < (n_head - 1) * y_head_stride + mo)
+        return fail(GQ_EINVAL, "ldy=%lld < (n_head-1)*y_head_stride+%lld=%lld", (long long)ldy, (long long)mo,
+                    (long long)((n_head - 1) * y_head_stride + mo));
+    if ((((uintptr_t)W | (uintptr_t)X) & 15) != 0 || ((ldx | x_head_stride) & 7) != 0)
+        return fail(GQ_EINVAL, "W and X must be 16-byte aligned, ldx and x_head_stride multiples of 8 (16-byte loads)");
+    if (((uintptr_t)Y & 7) != 0 || ((ldy | y_head_stride) & 3) != 0)
+        return fail(GQ_EINVAL, "Y must be 8-byte aligned, ldy and y_head_stride multiples of 4 (8-byte stores)");
+    const gq::MlaProjCall c{W, X, Y, ldx, x_head_stride, ldy, y_head_stride, T, n_head};
+    return hip_rc(gq::launch_mla_proj(dir, c, p, (hipStream_t)stream), "mla_proj");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

@@ -27,10 +27,14 @@ and DeepSeek's multi-head latent attention over a latent cache, at decode and ov
 gq_mla_prefill, gq_mla_append):
 
     from kernels import MLACache, MLAttention, mla_decode, mla_prefill, mla_append
+
+with the per-head W_UK / W_UV products around it in HIP (gq_mla_proj; MLAttention(..., fused=True)):
+
+    from kernels import mla_proj
 """
 _LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib", "RoPE": "attention",
          "rope_append": "_lib", "attn_options": "attention", "MLACache": "attention", "MLAttention": "attention",
-         "mla_decode": "_lib", "mla_prefill": "_lib", "mla_append": "_lib"}
+         "mla_decode": "_lib", "mla_prefill": "_lib", "mla_append": "_lib", "mla_proj": "_lib"}
 __all__ = list(_LAZY)
 
 

@@ -128,6 +128,9 @@ SIGNATURES = {
                                    ctypes.POINTER(ctypes.c_int64)], _I),
     "gq_mla_append": ([_I, _P, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _P, _I64, _P, ctypes.c_float, _P,
                        ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_mla_proj": ([_I, _P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_debug_mla_proj_plan": ([_I, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                ctypes.POINTER(ctypes.c_int64)], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
@@ -1239,6 +1242,37 @@ def mla_append(mode: str, ckv: torch.Tensor, kpe: torch.Tensor, qpe: torch.Tenso
                                    q_head_stride, qout.data_ptr(), ldqo, C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(),
                                    capacity, inv_freq.data_ptr(), float(mscale), norm_w.data_ptr(), float(eps), B, N, n_head,
                                    rank, rope_dim, _stream(dev)))
+
+
+MLA_PROJ_DIM = 128  # nope (dir 0) and v_dim (dir 1): the one value gq_mla_proj is instantiated for
+
+
+def mla_proj_plan(dir: int, T: int, n_head: int):
+    """(form: 0 few-row or 1 tiled, token rows per workgroup, workgroups) of an mla_proj call (gq_debug_mla_proj_plan)."""
+    form, rows, grid = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _check(lib().gq_debug_mla_proj_plan(dir, T, n_head, ctypes.byref(form), ctypes.byref(rows), ctypes.byref(grid)))
+    return form.value, rows.value, grid.value
+
+
+def mla_proj(dir: int, W: torch.Tensor, X: torch.Tensor, x_head_stride: int, Y: torch.Tensor, y_head_stride: int, T: int,
+             n_head: int) -> torch.Tensor:
+    """The per-head products around the latent attention, Y_h = X_h W_h^T in one launch (gq_mla_proj).  dir 0
+    absorbs W = W_UK, fp16 (n_head, rank, nope) contiguous, into the first nope of every x_head_stride-wide head
+    of X (q: 192) and writes the first rank of every y_head_stride-wide head of Y (mla_decode's q: 576) and
+    nothing else; dir 1 expands X (the attention output: 512) by W = W_UV, fp16 (n_head, v_dim, rank), into Y
+    (128).  X, Y: fp16 (T, >= the last head's end) with unit column stride.  No host sync, no fallback."""
+    _require_device(W, "W")
+    dev = W.device
+    if W.dtype != torch.float16 or W.dim() != 3 or W.shape[0] != n_head or not W.is_contiguous():
+        raise RuntimeError(f"W must be a contiguous fp16 ({n_head}, Mo, Kc) tensor")
+    mo, kc = int(W.shape[1]), int(W.shape[2])
+    ldx = _kv_rows(X, "X", T, X.shape[1] if X.dim() == 2 and X.shape[1] >= (n_head - 1) * x_head_stride + kc else -1, dev)
+    ldy = _kv_rows(Y, "Y", T, Y.shape[1] if Y.dim() == 2 and Y.shape[1] >= (n_head - 1) * y_head_stride + mo else -1, dev)
+    rank, dim = (kc, mo) if dir else (mo, kc)
+    with torch.cuda.device(dev):
+        _check(lib().gq_mla_proj(dir, W.data_ptr(), X.data_ptr(), ldx, x_head_stride, Y.data_ptr(), ldy, y_head_stride, T,
+                                 n_head, rank, dim, _stream(dev)))
+    return Y
 
 
 def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N: int, K: int,

@@ -282,12 +282,14 @@ class MLACache:
 class MLAttention:
     """A DeepSeek-V2/V3 layer's attention core, at decode and over a prompt alike, between the q / attn_kv_a_mqa
     projections and attn_output: the absorption of W_UK into q (a torch bmm on dequantized weights), MLACache.append,
-    MLACache.attend, and the product with W_UV (a second bmm).  The two bmm are the caller's matmuls in the
-    C ABI; a HIP form of them is not part of the library yet.  k_b: fp16 (n_head, rank, nope), v_b: fp16
-    (n_head, v_dim, rank)."""
+    MLACache.attend, and the product with W_UV (a second bmm).  fused=True: the two products are gq_mla_proj
+    launches that write straight into the cache's q buffer and an output buffer kept per token count -- four
+    launches at decode (five with the combine), no torch op, no allocation after the first call at a given T, the
+    whole step capturable in one graph; (rank, nope, v_dim) must be (512, 128, 128), anything else raises.  The
+    default keeps the bmm form and its bits.  k_b: fp16 (n_head, rank, nope), v_b: fp16 (n_head, v_dim, rank)."""
 
     def __init__(self, k_b: torch.Tensor, v_b: torch.Tensor, norm_w: torch.Tensor, rope: RoPE, eps: float = 1e-6,
-                 scale: float | None = None):
+                 scale: float | None = None, fused: bool = False):
         self.k_b, self.v_b = k_b.to(torch.float16).contiguous(), v_b.to(torch.float16).contiguous()
         self.n_head, self.rank, self.nope = self.k_b.shape
         self.v_dim = self.v_b.shape[1]
@@ -297,9 +299,11 @@ class MLAttention:
         # llama.cpp's deepseek2 scale: mscale^2 / sqrt(the un-absorbed key length)
         self.scale = rope.mscale ** 2 / math.sqrt(self.nope + rope.n_rot) if scale is None else float(scale)
         self.cache = None
+        self.fused, self._out = bool(fused), {}  # T -> the fused form's output buffer
 
     @classmethod
-    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", scale: float | None = None) -> "MLAttention":
+    def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", scale: float | None = None,
+                  fused: bool = False) -> "MLAttention":
         """From read_gguf()'s metadata and tensors: {arch}.attention.kv_lora_rank, {arch}.rope.dimension_count
         and the rope.scaling.* keys (through RoPE.from_gguf), {arch}.attention.layer_norm_rms_epsilon,
         blk.<layer>.attn_kv_a_norm.weight, and blk.<layer>.attn_k_b.weight (GGUF dims (nope, rank, n_head)) with
@@ -329,7 +333,7 @@ class MLAttention:
             kv = kv.view(n_head, -1, rank)
             k_b, v_b = kv[:, :nope].transpose(1, 2), kv[:, nope:]
         norm_w = torch.from_numpy(_f32_values(tensors[f"blk.{layer}.attn_kv_a_norm.weight"]).astype(np.float32)).to(device)
-        return cls(k_b, v_b, norm_w, rope, float(meta.get(f"{arch}.attention.layer_norm_rms_epsilon", 1e-6)), scale)
+        return cls(k_b, v_b, norm_w, rope, float(meta.get(f"{arch}.attention.layer_norm_rms_epsilon", 1e-6)), scale, fused)
 
     def new_cache(self, B: int, capacity: int, device="cuda") -> MLACache:
         """The layer's latent cache, empty: forward appends to it and attends over it."""
@@ -339,11 +343,20 @@ class MLAttention:
     def forward(self, q: torch.Tensor, kv_a_out: torch.Tensor, cache: MLACache | None = None) -> torch.Tensor:
         """q fp16 (B*N, n_head*(nope + rope_dim)) and the attn_kv_a_mqa output (B*N, rank + rope_dim) of the N
         new tokens -> fp16 (B*N, n_head*v_dim), attn_output's input, over `cache` (new_cache's when None).
-        Four steps: q_nope absorbed by bmm, append, attend, bmm with W_UV."""
+        Four steps: q_nope absorbed by bmm, append, attend, bmm with W_UV; fused: append, gq_mla_proj into the
+        cache's q buffer, attend, gq_mla_proj into this layer's output buffer for T (returned: reused every step)."""
         cache = self.cache if cache is None else cache
         if cache is None:
             raise ValueError("no cache: call new_cache(B, capacity) first, or pass one")
         T, H, rank = q.shape[0], self.n_head, self.rank
+        if self.fused:
+            qbuf = cache.append(kv_a_out[:, :rank], kv_a_out[:, rank:], q, self.rope, self.norm_w, self.eps)
+            _lib.mla_proj(0, self.k_b, q, q.shape[1] // H, qbuf, qbuf.shape[1] // H, T, H)
+            o = cache.attend(qbuf, self.scale)
+            out = self._out.get(T)
+            if out is None or out.device != q.device:
+                out = self._out[T] = torch.empty(T, H * self.v_dim, dtype=torch.float16, device=q.device)
+            return _lib.mla_proj(1, self.v_b, o, rank, out, self.v_dim, T, H)
         q_abs = torch.bmm(q.view(T, H, -1)[:, :, :self.nope].transpose(0, 1), self.k_b.transpose(1, 2))  # (H, T, rank)
         qbuf = cache.append(kv_a_out[:, :rank], kv_a_out[:, rank:], q, self.rope, self.norm_w, self.eps)
         qbuf.view(T, H, -1)[:, :, :rank].copy_(q_abs.transpose(0, 1))

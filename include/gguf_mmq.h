@@ -36,6 +36,7 @@
  *   gq_rope_append                      per-head norm + RoPE of q and k, then that append, in one launch
  *   gq_mla_decode, gq_mla_append        DeepSeek's latent attention (MLA) at decode and its latent cache's producer
  *   gq_mla_prefill                      the same attention for a prompt or a chunk of one: any number of new tokens, one launch
+ *   gq_mla_proj                         the per-head W_UK and W_UV products before and after that attention, one launch each
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -713,11 +714,11 @@ int gq_rope_append(gq_kv_type kv, gq_rope_mode mode, const void *Q, int64_t ldq,
  *            t*tok_stride (multiples of 2) and holds rank + rope_dim = 576 values [c_kv (512) | k_pe (64)]:
  *            the normalised compressed kv and the rotated shared rope key, as gq_mla_append writes them.
  *   Q      : fp16 (B*N, n_head*576), rows ldq apart; head j's 576 are [q_abs (512) | q_pe (64)]: q_nope
- *            already multiplied by the head's W_UK (the caller's matmul) and q_pe already rotated.
+ *            already multiplied by the head's W_UK (gq_mla_proj, or the caller's matmul) and q_pe already rotated.
  *   kv_len, capacity : as gq_attn_decode's (the lengths INCLUDE the N new tokens, device memory).
  *   O      : fp16 (B*N, n_head*512), rows ldo apart: softmax(scale * q . row) weighted sum of the rows'
  *            first 512 values, over positions 0 .. kv_len[b] - N + i for query token i.  The caller
- *            multiplies head j's 512 by its W_UV.
+ *            multiplies head j's 512 by its W_UV (gq_mla_proj).
  * The arithmetic and the bound are gq_attn_decode's fp16 path's: fp32 scores, softmax and sums, fp16
  * probabilities into the second product, one final rounding, |o - exact| <= 2^-9 * max|c_kv| over the
  * attended positions.  Positions at or beyond kv_len[b] are never used, whatever bytes they hold; the length
@@ -788,6 +789,38 @@ int gq_mla_append(gq_rope_mode mode, const void *Ckv, int64_t ldc, const void *K
                   int64_t q_head_stride, void *Qout, int64_t ldqo, void *C, int64_t tok_stride, int64_t seq_stride,
                   const int32_t *kv_len, int64_t capacity, const float *inv_freq, float mscale, const float *norm_w, float eps,
                   int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim, void *stream);
+
+/*
+ * The two per-head products around that attention, ONE launch each: Y_h = X_h W_h^T for every head h of T = B*N
+ * token rows, W_h a row-major fp16 matrix whose contraction index is contiguous.
+ *   dir 0 (absorb): W = W_UK, fp16 (n_head, 512, 128) contiguous; X = q, head h's q_nope at element t*ldx +
+ *            h*x_head_stride (the first 128 of every 192-wide head: x_head_stride = 192); Y = gq_mla_decode's Q,
+ *            head h's 512 absorbed values at element t*ldy + h*y_head_stride (y_head_stride = 576).
+ *   dir 1 (expand): W = W_UV, fp16 (n_head, 128, 512) contiguous; X = gq_mla_decode's / gq_mla_prefill's O
+ *            (x_head_stride = 512); Y = attn_output's input, 128 per head (y_head_stride = 128).
+ *   Y[t*ldy + h*y_head_stride + m] = fp16(sum_k X[t*ldx + h*x_head_stride + k] * W[(h*Mo + m)*Kc + k]),
+ *            (Mo, Kc) = (rank, dim) for dir 0 and (dim, rank) for dir 1.
+ * fp16 products (exact in fp32), fp32 accumulation on the matrix cores in a fixed order, one rounding:
+ * |y - exact| <= 2^-11 |exact| + 2^-25 + Kc * 2^-23 * sum_k |x_k w_k|.  Nothing but those Mo values of every
+ * (t, h) is written: the q_pe gq_mla_append left in columns 512..575 of every head of Q survives dir 0.  A token's
+ * output depends on no other token's input.  Two forms, chosen from T and n_head alone (never from device data):
+ * up to 16 tokens W is streamed once into the matrix operand by n_head * Mo/16 (from 64 heads: Mo/32) workgroups;
+ * beyond, one workgroup per (head, 64 tokens) shares W_h's tiles through LDS, a head's workgroups neighbours.
+ * Shapes: dir 0 or 1, (rank, dim) == (512, 128), 1 <= n_head <= 128, T*n_head < 2^31; anything else:
+ * GQ_EUNSUPPORTED.  GQ_EINVAL: a negative size; a null pointer; x_head_stride < Kc, y_head_stride < Mo,
+ * ldx < (n_head-1)*x_head_stride + Kc, ldy < (n_head-1)*y_head_stride + Mo; W or X not 16-byte aligned, ldx or
+ * x_head_stride no multiple of 8 (16-byte loads); Y not 8-byte aligned, ldy or y_head_stride no multiple of 4
+ * (8-byte stores).  The checks come in that order: the sizes, (T or n_head == 0: a no-op), the pointers, the
+ * shape, the strides, the alignment.  Every check precedes the launch.  Asynchronous, no host sync, no
+ * allocation, no workspace, graph-capturable.  Detected by its symbol; gq_version() did not change with it.
+ * W is fp16 only: no quantized form.
+ */
+int gq_mla_proj(int dir, const void *W, const void *X, int64_t ldx, int64_t x_head_stride,
+                void *Y, int64_t ldy, int64_t y_head_stride,
+                int64_t T, int64_t n_head, int64_t rank, int64_t dim, void *stream);
+/* The plan of that call: the form (0 few-row, 1 tiled), the token rows per workgroup (16 or 64) and the grid.
+ * GQ_EUNSUPPORTED: no such shape. */
+int gq_debug_mla_proj_plan(int dir, int64_t T, int64_t n_head, int *form, int *rows_per_block, int64_t *grid);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE

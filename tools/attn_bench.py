@@ -58,6 +58,14 @@ N in {16, 512, 4096} without a prefix and N = 512 after a prefix of 4096, B in {
 fp16 softmax(mask(q C^T)) C[:, :512] over the same cache, and what the library offered before -- a loop of
 mla_decode at four tokens a step, each step at its own length -- all three as captured graphs (MlaPrefillCase).
 A cell is the median time of each form and the causal TFLOP/s at 2 * (576 + 512) flops per attended (row, key).
+
+    python tools/attn_bench.py --mla-proj [--out profiles/attn_mla_proj_bench.json]
+
+The per-head W_UK / W_UV products around that attention (kernels._lib.mla_proj: gq_mla_proj), 16 and 128 heads, T in
+{1, 4, 64, 4096} token rows of one sequence: each direction beside the lines MLAttention.forward runs without
+fused=True (a strided-batch torch.bmm, and for the absorb the copy into the q buffer), and the fused forward beside
+the unfused one over a cache of 4096 positions (MlaProjCase).  The weights rotate.  A few-row cell carries the weight
+bytes over the time against the HBM figure, a tiled cell the TFLOP/s of 2 * T * heads * 512 * 128 flops.
 """
 import argparse
 import json
@@ -330,6 +338,103 @@ def main_mla_prefill(a, dev):
                                    "skipped": skipped, "rows": rows}, f, indent=1)
 
 
+class MlaProjCase:
+    """T token rows of one sequence through a layer's two latent projections and through MLAttention.forward over a
+    latent cache of 4096 positions (the T new tokens its last).  The weights rotate (every copy the same values,
+    at most 256 copies); q, the q buffer, the attention output and the cache do not."""
+    forms = ("absorb_torch", "absorb_hip", "expand_torch", "expand_hip", "layer_torch", "layer_fused")
+    L = 4096
+
+    def __init__(self, nh, T, dev, steps):
+        import kernels._lib as kl
+        from kernels import MLAttention, RoPE
+        self.kl, self.dev, self.dims = kl, dev, (nh, T)
+        self.wbytes = 2 * nh * 512 * 128  # one direction's weights
+        ncopies, self.plans = bench.rotation_plan(max(2 * self.wbytes, bench.ROTATE_BYTES // 256), steps)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        rnd = lambda *s: torch.randn(s, device=dev, generator=gen).to(torch.float16)  # noqa: E731
+        self.kb = (rnd(nh, 512, 128) * 128 ** -0.5).expand(ncopies, nh, 512, 128).contiguous().unbind(0)
+        self.vb = (rnd(nh, 128, 512) * 512 ** -0.5).expand(ncopies, nh, 128, 512).contiguous().unbind(0)
+        self.q, self.kv, self.o = rnd(T, nh * 192), rnd(T, 576), rnd(T, nh * 512)
+        self.qbuf = torch.zeros(T, nh * 576, dtype=torch.float16, device=dev)
+        self.out = torch.empty(T, nh * 128, dtype=torch.float16, device=dev)
+        f, m = RoPE.table(64)
+        rope, w = RoPE(torch.from_numpy(f).float().to(dev), 64, "norm", m), torch.ones(512, device=dev)
+        self.layers = {fused: [MLAttention(k, v, w, rope, fused=fused) for k, v in zip(self.kb, self.vb)] for fused in (False, True)}
+        self.cache = self.layers[False][0].new_cache(1, self.L, dev)
+        self.cache.c.view(torch.float16).copy_(rnd(self.L * 576))
+        self.len0 = torch.full((1,), self.L - T, dtype=torch.int32, device=dev)
+        self.flops = 2.0 * T * nh * 512 * 128  # one direction
+
+    def step(self, form, c, i):
+        nh, T = self.dims
+        if form == "absorb_torch":  # MLAttention.forward's lines: a strided-batch bmm and the copy into the q buffer
+            q_abs = torch.bmm(self.q.view(T, nh, -1)[:, :, :128].transpose(0, 1), self.kb[c].transpose(1, 2))
+            return self.qbuf.view(T, nh, -1)[:, :, :512].copy_(q_abs.transpose(0, 1))
+        if form == "absorb_hip":
+            return self.kl.mla_proj(0, self.kb[c], self.q, 192, self.qbuf, 576, T, nh).view(T, nh, -1)[:, :, :512]
+        if form == "expand_torch":
+            return torch.bmm(self.o.view(T, nh, 512).transpose(0, 1), self.vb[c].transpose(1, 2)).transpose(0, 1).reshape(T, nh * 128)
+        if form == "expand_hip":
+            return self.kl.mla_proj(1, self.vb[c], self.o, 512, self.out, 128, T, nh)
+        self.cache.kv_len.copy_(self.len0)  # (both layer forms: every step appends the same T tokens at the cache's end)
+        return self.layers[form == "layer_fused"][c].forward(self.q, self.kv, self.cache)
+
+    def check(self):
+        d = {}
+        for what in ("absorb", "expand", "layer"):
+            a = self.step(f"{what}_torch", 0, 0).float().clone()
+            b = self.step(f"{what}_{'fused' if what == 'layer' else 'hip'}", 0, 0).float()
+            torch.cuda.synchronize(self.dev)
+            d[what] = float((a - b).abs().max() / a.abs().max())
+            assert d[what] <= 1e-2, d
+        return d
+
+
+def main_mla_proj(a, dev):
+    rows = []
+    for nh in (16, 128):
+        for T in (1, 4, 64, 4096):
+            steps = a.steps if T <= 4 else max(2, a.steps // 5)
+            case = MlaProjCase(nh, T, dev, steps)
+            diff = case.check()
+            gs = {f: graphs(case, f, torch.cuda.graph_pool_handle()) for f in case.forms}
+            ts = {f: [] for f in case.forms}
+            for _ in range(a.repeats):  # interleaved: one pass over the forms per repeat
+                for f in case.forms:
+                    ts[f].append(bench.timed_rotation(gs[f], dev) / steps * 1e6)
+            form, rows_wg, _ = case.kl.mla_proj_plan(0, T, nh)
+            row = {"heads": nh, "T": T, "form": "tiled" if form else "few-row", "rows_per_workgroup": rows_wg,
+                   "workgroups": {d: case.kl.mla_proj_plan(i, T, nh)[2] for i, d in enumerate(("absorb", "expand"))},
+                   "hip_vs_torch_max_rel_diff": {k: round(v, 5) for k, v in diff.items()}}
+            for f in case.forms:
+                us = float(np.median(ts[f]))
+                row[f] = {"us": round(us, 2), "spread_us": round(max(ts[f]) - min(ts[f]), 2)}
+                if not f.startswith("layer"):
+                    if form == 0:  # the weights, read once, over the time against the HBM figure
+                        row[f]["weight_GBs"] = round(case.wbytes / us / 1e3, 1)
+                        row[f]["hbm_frac"] = round(case.wbytes / us / 1e3 / bench.HBM_PEAK_GBS, 4)
+                    else:
+                        row[f]["TFLOPs"] = round(case.flops / us / 1e6, 1)
+                        row[f]["mfma_frac"] = round(case.flops / us / 1e6 / bench.MFMA_F16_PEAK_TF, 4)
+            for new, old in (("absorb_hip", "absorb_torch"), ("expand_hip", "expand_torch"), ("layer_fused", "layer_torch")):
+                row[f"{new}_slower"] = bool(row[new]["us"] - row[old]["us"] > max(row[new]["spread_us"], row[old]["spread_us"]))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del case, gs
+            torch.cuda.empty_cache()
+            if a.out:  # (after every cell: a run cut short keeps what it measured)
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "w") as f:
+                    json.dump({"steps": a.steps, "repeats": a.repeats, "hbm_peak_GBs": bench.HBM_PEAK_GBS,
+                               "mfma_f16_peak_TF": bench.MFMA_F16_PEAK_TF, "layer_kv_len": MlaProjCase.L,
+                               "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count,
+                               "not_measured": "the LDS-DMA ring for the few-row weight stream, other tiles-per-workgroup "
+                                               "counts, two token tiles per wave in the tiled form, any profile (no "
+                                               "counters were collected)",
+                               "rows": rows}, f, indent=1)
+
+
 ROPE_HEADS = {"llama3_8b": (32, 8, 128, "norm", False), "qwen3_8b": (32, 8, 128, "neox", True)}
 
 
@@ -547,6 +652,7 @@ def main():
     ap.add_argument("--mla", action="store_true", help="DeepSeek's latent attention at decode (mla_decode) beside torch matmuls")
     ap.add_argument("--mla-prefill", action="store_true", help="the latent attention over a prompt (mla_prefill) beside torch and a decode loop")
     ap.add_argument("--rope", action="store_true", help="the fused norm + RoPE + append (rope_append) beside torch RoPE + kv_append")
+    ap.add_argument("--mla-proj", action="store_true", help="the latent projections (mla_proj) and the fused MLAttention beside torch bmm")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("attn_bench.py needs a ROCm device: there is no CPU timing path")
@@ -555,6 +661,8 @@ def main():
         return main_mla(a, dev)
     if a.mla_prefill:
         return main_mla_prefill(a, dev)
+    if a.mla_proj:
+        return main_mla_proj(a, dev)
     if a.prefill:
         return main_prefill(a, dev)
     if a.rope:
