@@ -229,6 +229,36 @@ struct MlaProjCall {
 };
 MlaProjPlan plan_mla_proj(int dir, int64_t T, int64_t n_head);
 hipError_t launch_mla_proj(int dir, const MlaProjCall &c, const MlaProjPlan &p, hipStream_t s);
+// The un-absorbed prompt pass (attn_mla_mha.hip): gq_mla_kv_expand decompresses the N newest latent rows of every
+// sequence into kMlaKvWidth = [k_nope (128) | v (128)] values per head through W (n_head, 256, 512), one workgroup
+// per (sequence, rows-token block, hpw heads) with W in gq_mla_proj's ring; gq_mla_prefill_mha attends at head dims
+// 128 + 64 shared / 128, one workgroup per (sequence, head, rows tokens) over a two-slot ring of kMhaTile keys.
+// Both plans follow from B, N, n_head and the compute units alone.  kMhaTile and kMhaSlots were not measured
+// against other values: two 40 KiB slots let two workgroups share a compute unit's LDS.
+constexpr int kMlaKvWidth = 2 * kMlaProjDim;
+constexpr int kMhaTile = 64, kMhaSlots = 2;
+struct MlaExpandPlan {
+    bool ok = false;           // 1 <= n_head <= 128, B <= 2^17, B * N < 2^31
+    int rows = 0, ntb = 0, hpw = 0; // token rows per workgroup (64 or 128), token blocks per sequence, heads per workgroup
+    int64_t grid = 0;
+};
+struct MlaMhaPlan {
+    bool ok = false;           // 1 <= n_head <= 128, B <= 2^17, B * N * n_head < 2^31
+    int rows = 0, nblk = 0;    // query rows per workgroup (64 or 128), row blocks per (sequence, head)
+    int64_t grid = 0;
+};
+struct MlaMhaCall {            // (expand: W, C, KV; attention: Qn, Qp, KV, C, O)
+    const void *W, *Qn, *Qp, *C;
+    const int32_t *kv_len;
+    void *KV, *O;
+    int64_t ldqn, qn_head_stride, ldqp, qp_head_stride, ldo, tok_stride, seq_stride, capacity, kv_tok_stride, kv_seq_stride,
+        kv_capacity, B, N, n_head;
+    float scale;
+};
+MlaExpandPlan plan_mla_kv_expand(int64_t B, int64_t N, int64_t n_head);
+hipError_t launch_mla_kv_expand(const MlaMhaCall &c, const MlaExpandPlan &p, hipStream_t s);
+MlaMhaPlan plan_mla_prefill_mha(int64_t B, int64_t N, int64_t n_head);
+hipError_t launch_mla_prefill_mha(const MlaMhaCall &c, const MlaMhaPlan &p, hipStream_t s);
 
 // Decode-shaped GEMV (mmq_gemv.hip): C[t][m] for t < N_tok <= 8 from SOA activations.
 hipError_t launch_gemv(int fmt, const uint8_t *A, const int8_t *xq, const float *xd, const float *xs, uint16_t *C,

@@ -1860,6 +1860,100 @@ int gq_mla_proj(int dir, const void *W, const void *X, int64_t ldx, int64_t x_he
     return hip_rc(gq::launch_mla_proj(dir, c, p, (hipStream_t)stream), "mla_proj");
 }
 
+// ---- the un-absorbed prompt pass (attn_mla_mha.hip) ----
+// What gq_mla_kv_expand and gq_mla_prefill_mha ask of the expanded buffer, after check_mla_cache.
+static int check_mla_kv(int64_t kv_tok_stride, int64_t kv_seq_stride, int64_t kv_capacity, int64_t n_head)
+{
+    const int64_t rb = 2 * gq::kMlaKvWidth * n_head;
+    if (((kv_tok_stride | kv_seq_stride) & 15) != 0) return fail(GQ_EUNSUPPORTED, "the KV strides must be multiples of 16");
+    if (kv_tok_stride < rb || kv_seq_stride < 0)
+        return fail(GQ_EUNSUPPORTED, "kv_tok_stride=%lld is below a row's n_head*512=%lld bytes, or a negative stride",
+                    (long long)kv_tok_stride, (long long)rb);
+    if (kv_capacity < 1) return fail(GQ_EUNSUPPORTED, "kv_capacity=%lld holds no position", (long long)kv_capacity);
+    if (kv_capacity > (1 << 30) / kv_tok_stride) // (check_mla_cache's rule: 16384 positions at 128 heads)
+        return fail(GQ_EUNSUPPORTED, "one sequence spans kv_capacity * kv_tok_stride = more than 1 GiB (32-bit buffer offsets)");
+    return GQ_OK;
+}
+
+int gq_mla_kv_expand(const void *W, const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity,
+                     void *KV, int64_t kv_tok_stride, int64_t kv_seq_stride, int64_t kv_capacity, int64_t B, int64_t N,
+                     int64_t n_head, int64_t rank, int64_t dim, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    // (gq_mla_proj's order: the sizes, the empty problem, the pointers, the shape; then gq_mla_decode's cache checks)
+    if (B < 0 || N < 0 || n_head < 0 || rank < 0 || dim < 0 || capacity < 0 || kv_capacity < 0)
+        return fail(GQ_EINVAL, "negative size B=%lld N=%lld n_head=%lld rank=%lld dim=%lld capacity=%lld kv_capacity=%lld", (long long)B,
+                    (long long)N, (long long)n_head, (long long)rank, (long long)dim, (long long)capacity, (long long)kv_capacity);
+    if (B == 0 || N == 0 || n_head == 0) return GQ_OK;
+    if (!W || !C || !kv_len || !KV) return fail(GQ_EINVAL, "null pointer (W=%p C=%p kv_len=%p KV=%p)", W, C, (const void *)kv_len, KV);
+    if (rank != gq::kMlaRank || dim != gq::kMlaProjDim)
+        return fail(GQ_EUNSUPPORTED, "(rank, dim) = (%lld, %lld) is not (512, 128)", (long long)rank, (long long)dim);
+    const int rc = check_mla_cache(tok_stride, seq_stride, capacity, B, N, n_head, rank, gq::kMlaRope, false, empty);
+    if (rc != GQ_OK) return rc;
+    if (const int rk = check_mla_kv(kv_tok_stride, kv_seq_stride, kv_capacity, n_head)) return rk;
+    const gq::MlaExpandPlan p = gq::plan_mla_kv_expand(B, N, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "B * N = %lld tokens is 2^31 or more", (long long)(B * N));
+    if ((((uintptr_t)W | (uintptr_t)KV) & 15) != 0) return fail(GQ_EINVAL, "W and KV must be 16-byte aligned");
+    gq::MlaMhaCall c{};
+    c.W = W, c.C = C, c.kv_len = kv_len, c.KV = KV;
+    c.tok_stride = tok_stride, c.seq_stride = seq_stride, c.capacity = capacity;
+    c.kv_tok_stride = kv_tok_stride, c.kv_seq_stride = kv_seq_stride, c.kv_capacity = kv_capacity;
+    c.B = B, c.N = N, c.n_head = n_head;
+    return hip_rc(gq::launch_mla_kv_expand(c, p, (hipStream_t)stream), "mla_kv_expand");
+}
+
+int gq_debug_mla_prefill_mha_plan(int64_t B, int64_t N, int64_t n_head, int *rows_per_block, int *tile, int64_t *grid)
+{
+    g_err.clear();
+    const gq::MlaMhaPlan p = gq::plan_mla_prefill_mha(B, N, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "not an MLA MHA prefill shape");
+    if (rows_per_block) *rows_per_block = p.rows;
+    if (tile) *tile = gq::kMhaTile;
+    if (grid) *grid = p.grid;
+    return GQ_OK;
+}
+
+int gq_mla_prefill_mha(const void *Qn, int64_t ldqn, int64_t qn_head_stride, const void *Qp, int64_t ldqp, int64_t qp_head_stride,
+                       const void *KV, int64_t kv_tok_stride, int64_t kv_seq_stride, int64_t kv_capacity, const void *C,
+                       int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity, void *O, int64_t ldo,
+                       float scale, int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim, int64_t dim, void *stream)
+{
+    g_err.clear();
+    bool empty;
+    if (dim < 0 || kv_capacity < 0) return fail(GQ_EINVAL, "negative size dim=%lld kv_capacity=%lld", (long long)dim, (long long)kv_capacity);
+    if (B >= 0 && N >= 0 && n_head > 0 && rank >= 0 && rope_dim >= 0 && B * N > 0) {
+        if (!Qn || !Qp || !KV || !C || !kv_len || !O)
+            return fail(GQ_EINVAL, "null pointer (Qn=%p Qp=%p KV=%p C=%p kv_len=%p O=%p)", Qn, Qp, KV, C, (const void *)kv_len, O);
+        if (qn_head_stride < dim) return fail(GQ_EINVAL, "qn_head_stride=%lld < dim=%lld", (long long)qn_head_stride, (long long)dim);
+        if (qp_head_stride < rope_dim)
+            return fail(GQ_EINVAL, "qp_head_stride=%lld < rope_dim=%lld", (long long)qp_head_stride, (long long)rope_dim);
+        if (ldqn < (n_head - 1) * qn_head_stride + dim)
+            return fail(GQ_EINVAL, "ldqn=%lld < (n_head-1)*qn_head_stride+dim=%lld", (long long)ldqn,
+                        (long long)((n_head - 1) * qn_head_stride + dim));
+        if (ldqp < (n_head - 1) * qp_head_stride + rope_dim)
+            return fail(GQ_EINVAL, "ldqp=%lld < (n_head-1)*qp_head_stride+rope_dim=%lld", (long long)ldqp,
+                        (long long)((n_head - 1) * qp_head_stride + rope_dim));
+        if (ldo < n_head * dim) return fail(GQ_EINVAL, "ldo=%lld < n_head*dim=%lld", (long long)ldo, (long long)(n_head * dim));
+    }
+    const int rc = check_mla_cache(tok_stride, seq_stride, capacity, B, N, n_head, rank, rope_dim, false, empty);
+    if (rc != GQ_OK || empty) return rc;
+    if (dim != gq::kMlaProjDim) return fail(GQ_EUNSUPPORTED, "(rank, dim) = (%lld, %lld) is not (512, 128)", (long long)rank, (long long)dim);
+    if (const int rk = check_mla_kv(kv_tok_stride, kv_seq_stride, kv_capacity, n_head)) return rk;
+    const gq::MlaMhaPlan p = gq::plan_mla_prefill_mha(B, N, n_head);
+    if (!p.ok) return fail(GQ_EUNSUPPORTED, "B * N * n_head = %lld query rows is 2^31 or more", (long long)(B * N * n_head));
+    if ((((uintptr_t)Qn | (uintptr_t)Qp | (uintptr_t)KV) & 15) != 0 || ((ldqn | qn_head_stride | ldqp | qp_head_stride) & 7) != 0)
+        return fail(GQ_EINVAL, "Qn, Qp and KV must be 16-byte aligned, their leading dimensions and head strides multiples of 8 (16-byte loads)");
+    if (((uintptr_t)O & 7) != 0 || (ldo & 3) != 0) return fail(GQ_EINVAL, "O must be 8-byte aligned, ldo a multiple of 4 (8-byte stores)");
+    gq::MlaMhaCall c{};
+    c.Qn = Qn, c.Qp = Qp, c.C = C, c.kv_len = kv_len, c.KV = const_cast<void *>(KV), c.O = O;
+    c.ldqn = ldqn, c.qn_head_stride = qn_head_stride, c.ldqp = ldqp, c.qp_head_stride = qp_head_stride, c.ldo = ldo;
+    c.tok_stride = tok_stride, c.seq_stride = seq_stride, c.capacity = capacity;
+    c.kv_tok_stride = kv_tok_stride, c.kv_seq_stride = kv_seq_stride, c.kv_capacity = kv_capacity;
+    c.B = B, c.N = N, c.n_head = n_head, c.scale = scale;
+    return hip_rc(gq::launch_mla_prefill_mha(c, p, (hipStream_t)stream), "mla_prefill_mha");
+}
+
 // gq_mmq_id_sorted's shape limits (GQ_EUNSUPPORTED beyond them), or the plan
 static gq::SortedPlan sorted_plan(gq_type t, int64_t E, int64_t M, int64_t N, int64_t S, int64_t K)
 {

@@ -31,10 +31,15 @@ gq_mla_prefill, gq_mla_append):
 with the per-head W_UK / W_UV products around it in HIP (gq_mla_proj; MLAttention(..., fused=True)):
 
     from kernels import mla_proj
+
+and the un-absorbed prompt pass (gq_mla_kv_expand, gq_mla_prefill_mha; MLAttention(..., unabsorbed_from=n)):
+
+    from kernels import mla_kv_expand, mla_prefill_mha
 """
 _LAZY = {"KVCache": "attention", "attn_decode": "_lib", "attn_prefill": "_lib", "kv_append": "_lib", "RoPE": "attention",
          "rope_append": "_lib", "attn_options": "attention", "MLACache": "attention", "MLAttention": "attention",
-         "mla_decode": "_lib", "mla_prefill": "_lib", "mla_append": "_lib", "mla_proj": "_lib"}
+         "mla_decode": "_lib", "mla_prefill": "_lib", "mla_append": "_lib", "mla_proj": "_lib",
+         "mla_kv_expand": "_lib", "mla_prefill_mha": "_lib"}
 __all__ = list(_LAZY)
 
 

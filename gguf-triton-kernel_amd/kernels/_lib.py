@@ -131,6 +131,11 @@ SIGNATURES = {
     "gq_mla_proj": ([_I, _P, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
     "gq_debug_mla_proj_plan": ([_I, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                 ctypes.POINTER(ctypes.c_int64)], _I),
+    "gq_mla_kv_expand": ([_P, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_mla_prefill_mha": ([_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _P, _I64,
+                            ctypes.c_float, _I64, _I64, _I64, _I64, _I64, _I64, _P], _I),
+    "gq_debug_mla_prefill_mha_plan": ([_I64, _I64, _I64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int64)], _I),
     "gq_act_prepare_grouped": ([_I, ctypes.POINTER(PrepItem), _I, _P], _I),
     "gq_debug_route": ([_I, _I, _I64, _I64, _I64, _I], ctypes.c_char_p),
     "gq_debug_decode_plan": ([_I, _I, ctypes.POINTER(GroupItem), _I, _I64, ctypes.POINTER(DecodePlan), _I], _I),
@@ -1273,6 +1278,68 @@ def mla_proj(dir: int, W: torch.Tensor, X: torch.Tensor, x_head_stride: int, Y: 
         _check(lib().gq_mla_proj(dir, W.data_ptr(), X.data_ptr(), ldx, x_head_stride, Y.data_ptr(), ldy, y_head_stride, T,
                                  n_head, rank, dim, _stream(dev)))
     return Y
+
+
+MLA_KV_WIDTH = 2 * MLA_PROJ_DIM  # [k_nope | v] values per (position, head) of the expanded buffer
+
+
+def mla_prefill_mha_plan(B: int, N: int, n_head: int):
+    """(query rows per workgroup, keys per tile, workgroups) of an mla_prefill_mha call (gq_debug_mla_prefill_mha_plan)."""
+    rows, tile, grid = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _check(lib().gq_debug_mla_prefill_mha_plan(B, N, n_head, ctypes.byref(rows), ctypes.byref(tile), ctypes.byref(grid)))
+    return rows.value, tile.value, grid.value
+
+
+def _mla_kv(KV: torch.Tensor, n_head: int, dev):
+    """KV: fp16 (B, kv_capacity, >= n_head*256) with unit column stride -> (tok, seq) strides in bytes, kv_capacity."""
+    _require_device(KV, "KV")
+    if KV.device != dev or KV.dtype != torch.float16 or KV.dim() != 3 or KV.shape[2] < n_head * MLA_KV_WIDTH or KV.stride(2) != 1:
+        raise RuntimeError(f"KV must be an fp16 (B, kv_capacity, >= {n_head * MLA_KV_WIDTH}) tensor on {dev} with unit column stride")
+    return 2 * KV.stride(1), 2 * KV.stride(0), int(KV.shape[1])
+
+
+def mla_kv_expand(W: torch.Tensor, C: torch.Tensor, strides, kv_len: torch.Tensor, capacity: int, KV: torch.Tensor, B: int, N: int,
+                  n_head: int, kv_offset: int = 0) -> torch.Tensor:
+    """The N newest latent rows of each of B sequences decompressed into per-head [k_nope | v] (gq_mla_kv_expand,
+    one launch): W fp16 (n_head, 256, 512) contiguous -- head h's rows 0..127 its k_b transposed, 128..255 its v_b;
+    C, strides, kv_len, capacity: mla_decode's latent cache; KV fp16 (B, kv_capacity, >= n_head*256), written at
+    the positions kv_len[b] - N + i inside [0, min(capacity, kv_capacity)) and nowhere else.  No host sync, no fallback."""
+    _require_device(W, "W")
+    dev = W.device
+    if W.dtype != torch.float16 or tuple(W.shape) != (n_head, MLA_KV_WIDTH, MLA_RANK) or not W.is_contiguous():
+        raise RuntimeError(f"W must be a contiguous fp16 ({n_head}, {MLA_KV_WIDTH}, {MLA_RANK}) tensor")
+    _kv_caches(C, C, kv_len, B, dev)
+    ktok, kseq, kcap = _mla_kv(KV, n_head, dev)
+    tok, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_mla_kv_expand(W.data_ptr(), C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(), capacity, KV.data_ptr(),
+                                      ktok, kseq, kcap, B, N, n_head, MLA_RANK, MLA_PROJ_DIM, _stream(dev)))
+    return KV
+
+
+def mla_prefill_mha(qn: torch.Tensor, qn_head_stride: int, qp: torch.Tensor, qp_head_stride: int, KV: torch.Tensor, C: torch.Tensor,
+                    strides, kv_len: torch.Tensor, capacity: int, B: int, N: int, n_head: int, scale: float,
+                    out: torch.Tensor | None = None, kv_offset: int = 0) -> torch.Tensor:
+    """Un-absorbed causal latent attention of the N new tokens of B sequences (gq_mla_prefill_mha, one launch): qn
+    and qp are fp16 views with B*N rows whose head h starts qn_head_stride (q_nope, 128 values; the q projection's
+    output: 192) and qp_head_stride (the rotated q_pe, 64 values; mla_append's buffer from column 512: 576)
+    elements into a row; KV: mla_kv_expand's buffer; C: the latent cache (its k_pe columns are read) ->
+    fp16 (B*N, n_head*128).  No host sync, no fallback."""
+    _require_device(qn, "qn")
+    dev, T = qn.device, B * N
+    ldqn = _kv_rows(qn, "qn", T, qn.shape[1] if qn.dim() == 2 and qn.shape[1] >= (n_head - 1) * qn_head_stride + MLA_PROJ_DIM else -1, dev)
+    ldqp = _kv_rows(qp, "qp", T, qp.shape[1] if qp.dim() == 2 and qp.shape[1] >= (n_head - 1) * qp_head_stride + MLA_ROPE else -1, dev)
+    _kv_caches(C, C, kv_len, B, dev)
+    ktok, kseq, kcap = _mla_kv(KV, n_head, dev)
+    if out is None:
+        out = torch.empty(T, n_head * MLA_PROJ_DIM, dtype=torch.float16, device=dev)
+    ldo = _kv_rows(out, "out", T, n_head * MLA_PROJ_DIM, dev)
+    tok, seq = (int(s) for s in strides)
+    with torch.cuda.device(dev):
+        _check(lib().gq_mla_prefill_mha(qn.data_ptr(), ldqn, qn_head_stride, qp.data_ptr(), ldqp, qp_head_stride, KV.data_ptr(), ktok,
+                                        kseq, kcap, C.data_ptr() + kv_offset, tok, seq, kv_len.data_ptr(), capacity, out.data_ptr(),
+                                        ldo, float(scale), B, N, n_head, MLA_RANK, MLA_ROPE, MLA_PROJ_DIM, _stream(dev)))
+    return out
 
 
 def mmq_prepared(gtype: int, A: torch.Tensor, workspace: torch.Tensor, M: int, N: int, K: int,

@@ -212,9 +212,11 @@ class MLACache:
     gq_mla_append and, up to 4 new tokens, gq_mla_decode; beyond -- a prompt, a chunk of one, a speculative
     verification -- gq_mla_prefill; up to 128 heads.  None syncs the host, and none allocates after the first
     call at a given (N, n_head), so one captured graph of a step serves every length up to the capacity.  No
-    fallback: a shape the library refuses raises."""
+    fallback: a shape the library refuses raises.  expand and attend_mha are the un-absorbed prompt pass
+    (gq_mla_kv_expand, gq_mla_prefill_mha) over a second, per-head buffer of the first kv_capacity positions."""
 
-    def __init__(self, B: int, capacity: int, rank: int = _lib.MLA_RANK, rope_dim: int = _lib.MLA_ROPE, device="cuda"):
+    def __init__(self, B: int, capacity: int, rank: int = _lib.MLA_RANK, rope_dim: int = _lib.MLA_ROPE, device="cuda",
+                 kv_capacity: int | None = None):
         if (rank, rope_dim) != (_lib.MLA_RANK, _lib.MLA_ROPE):
             raise ValueError(f"(rank, rope_dim) = ({rank}, {rope_dim}) is not ({_lib.MLA_RANK}, {_lib.MLA_ROPE})")
         if min(B, capacity) < 1:
@@ -226,10 +228,14 @@ class MLACache:
         self.kv_len = torch.zeros(B, dtype=torch.int32, device=device)
         self._bufs = {}  # (N, n_head) -> (q [q_abs | q_pe] rows, decode's workspace or None, output)
         self._n = 0      # the last append's token count: attend's N
+        # the un-absorbed prompt pass (expand, attend_mha): per-head [k_nope | v] of the first kv_capacity positions,
+        # allocated at the first expand; host counts of the positions appended per sequence and of those expanded
+        self.kv_capacity = capacity if kv_capacity is None else min(int(kv_capacity), capacity)
+        self.kv, self._mha_out, self.appended, self.expanded = None, {}, 0, 0
 
     def reset(self):
         self.kv_len.zero_()
-        self._n = 0
+        self._n = self.appended = self.expanded = 0
 
     def _for(self, N: int, n_head: int):
         bufs = self._bufs.get((N, n_head))
@@ -262,6 +268,7 @@ class MLACache:
         _lib.mla_append(rope.mode, ckv, kpe, q[:, Dq - self.rope_dim:], Dq, qbuf, self.c, self.strides, self.kv_len, self.capacity,
                         rope.inv_freq, rope.mscale, norm_w, eps, self.B, N, n_head, self.rank, self.rope_dim)
         self._n = N
+        self.appended += N
         return qbuf
 
     def attend(self, q: torch.Tensor, scale: float) -> torch.Tensor:
@@ -278,6 +285,37 @@ class MLACache:
         return _lib.mla_decode(q, self.c, self.strides, self.kv_len, self.capacity, self.B, N, n_head, ws, scale, out,
                                self.rank, self.rope_dim)
 
+    def expand(self, W: torch.Tensor, N: int) -> torch.Tensor:
+        """Decompress the N newest positions of every sequence into the expanded buffer (gq_mla_kv_expand): W fp16
+        (n_head, 256, 512), head h's rows [k_b^T (128) | v_b (128)].  The buffer -- fp16 (B, kv_capacity, n_head*256),
+        [k_nope | v] per head -- is allocated at the first call and kept; positions at or beyond kv_capacity are
+        skipped.  The host count of expanded positions (`expanded`) becomes the host count of appended ones."""
+        n_head = int(W.shape[0])
+        if self.kv is None or self.kv.shape[2] != n_head * _lib.MLA_KV_WIDTH:
+            if self.kv_capacity * n_head * 2 * _lib.MLA_KV_WIDTH > 1 << 30:
+                raise ValueError(f"kv_capacity = {self.kv_capacity} positions of {n_head} heads span more than 1 GiB a sequence")
+            self.kv = torch.zeros(self.B, self.kv_capacity, n_head * _lib.MLA_KV_WIDTH, dtype=torch.float16, device=self.c.device)
+        _lib.mla_kv_expand(W, self.c, self.strides, self.kv_len, self.capacity, self.kv, self.B, N, n_head)
+        self.expanded = self.appended
+        return self.kv
+
+    def attend_mha(self, qn: torch.Tensor, qp: torch.Tensor, scale: float, qn_head_stride: int = 192,
+                   qp_head_stride: int | None = None) -> torch.Tensor:
+        """Un-absorbed attention of the N tokens last appended over the expanded buffer (gq_mla_prefill_mha): qn the
+        q projection's output (head h's q_nope at column h*qn_head_stride), qp the rotated q_pe (append's buffer from
+        column rank on: head stride rank + rope_dim) -> fp16 (B*N, n_head*128), the cache's own buffer for (N, n_head)."""
+        N = qn.shape[0] // self.B
+        if N < 1 or N * self.B != qn.shape[0] or N != self._n:
+            raise ValueError(f"qn has {qn.shape[0]} rows; the last append wrote {self._n} tokens for each of {self.B} sequences")
+        if self.kv is None:
+            raise ValueError("nothing is expanded: call expand(W, N) first")
+        n_head = self.kv.shape[2] // _lib.MLA_KV_WIDTH
+        out = self._mha_out.get((N, n_head))
+        if out is None:
+            out = self._mha_out[(N, n_head)] = torch.empty(self.B * N, n_head * _lib.MLA_PROJ_DIM, dtype=torch.float16, device=self.c.device)
+        return _lib.mla_prefill_mha(qn, qn_head_stride, qp, qp_head_stride or self.rank + self.rope_dim, self.kv, self.c, self.strides,
+                                    self.kv_len, self.capacity, self.B, N, n_head, scale, out)
+
 
 class MLAttention:
     """A DeepSeek-V2/V3 layer's attention core, at decode and over a prompt alike, between the q / attn_kv_a_mqa
@@ -289,7 +327,7 @@ class MLAttention:
     default keeps the bmm form and its bits.  k_b: fp16 (n_head, rank, nope), v_b: fp16 (n_head, v_dim, rank)."""
 
     def __init__(self, k_b: torch.Tensor, v_b: torch.Tensor, norm_w: torch.Tensor, rope: RoPE, eps: float = 1e-6,
-                 scale: float | None = None, fused: bool = False):
+                 scale: float | None = None, fused: bool = False, unabsorbed_from: int = 0):
         self.k_b, self.v_b = k_b.to(torch.float16).contiguous(), v_b.to(torch.float16).contiguous()
         self.n_head, self.rank, self.nope = self.k_b.shape
         self.v_dim = self.v_b.shape[1]
@@ -300,10 +338,16 @@ class MLAttention:
         self.scale = rope.mscale ** 2 / math.sqrt(self.nope + rope.n_rot) if scale is None else float(scale)
         self.cache = None
         self.fused, self._out = bool(fused), {}  # T -> the fused form's output buffer
+        # unabsorbed_from = n > 0: a forward of n or more new tokens takes the un-absorbed pass (append, expand, MHA)
+        self.unabsorbed_from, self.w_kv = int(unabsorbed_from), None
+        if self.unabsorbed_from > 0:
+            if (self.rank, self.nope, self.v_dim) != (_lib.MLA_RANK, _lib.MLA_PROJ_DIM, _lib.MLA_PROJ_DIM):
+                raise ValueError(f"(rank, nope, v_dim) = ({self.rank}, {self.nope}, {self.v_dim}) is not (512, 128, 128)")
+            self.w_kv = torch.cat([self.k_b.transpose(1, 2), self.v_b], dim=1).contiguous()  # (n_head, 256, 512)
 
     @classmethod
     def from_gguf(cls, meta: dict, tensors: dict, layer: int, device="cuda", scale: float | None = None,
-                  fused: bool = False) -> "MLAttention":
+                  fused: bool = False, unabsorbed_from: int = 0) -> "MLAttention":
         """From read_gguf()'s metadata and tensors: {arch}.attention.kv_lora_rank, {arch}.rope.dimension_count
         and the rope.scaling.* keys (through RoPE.from_gguf), {arch}.attention.layer_norm_rms_epsilon,
         blk.<layer>.attn_kv_a_norm.weight, and blk.<layer>.attn_k_b.weight (GGUF dims (nope, rank, n_head)) with
@@ -333,22 +377,35 @@ class MLAttention:
             kv = kv.view(n_head, -1, rank)
             k_b, v_b = kv[:, :nope].transpose(1, 2), kv[:, nope:]
         norm_w = torch.from_numpy(_f32_values(tensors[f"blk.{layer}.attn_kv_a_norm.weight"]).astype(np.float32)).to(device)
-        return cls(k_b, v_b, norm_w, rope, float(meta.get(f"{arch}.attention.layer_norm_rms_epsilon", 1e-6)), scale, fused)
+        return cls(k_b, v_b, norm_w, rope, float(meta.get(f"{arch}.attention.layer_norm_rms_epsilon", 1e-6)), scale, fused,
+                   unabsorbed_from)
 
-    def new_cache(self, B: int, capacity: int, device="cuda") -> MLACache:
-        """The layer's latent cache, empty: forward appends to it and attends over it."""
-        self.cache = MLACache(B, capacity, self.rank, self.rope.n_rot, device)
+    def new_cache(self, B: int, capacity: int, device="cuda", kv_capacity: int | None = None) -> MLACache:
+        """The layer's latent cache, empty: forward appends to it and attends over it.  kv_capacity: the positions the
+        un-absorbed pass may expand (default: the capacity, at most what 1 GiB a sequence holds -- 16384 at 128 heads)."""
+        if kv_capacity is None:
+            kv_capacity = min(capacity, (1 << 30) // (self.n_head * 2 * _lib.MLA_KV_WIDTH))
+        self.cache = MLACache(B, capacity, self.rank, self.rope.n_rot, device, kv_capacity)
         return self.cache
 
     def forward(self, q: torch.Tensor, kv_a_out: torch.Tensor, cache: MLACache | None = None) -> torch.Tensor:
         """q fp16 (B*N, n_head*(nope + rope_dim)) and the attn_kv_a_mqa output (B*N, rank + rope_dim) of the N
         new tokens -> fp16 (B*N, n_head*v_dim), attn_output's input, over `cache` (new_cache's when None).
         Four steps: q_nope absorbed by bmm, append, attend, bmm with W_UV; fused: append, gq_mla_proj into the
-        cache's q buffer, attend, gq_mla_proj into this layer's output buffer for T (returned: reused every step)."""
+        cache's q buffer, attend, gq_mla_proj into this layer's output buffer for T (returned: reused every step).
+        unabsorbed_from = n > 0 and n or more new tokens per sequence that the expanded buffer still holds: append,
+        gq_mla_kv_expand of every position not yet expanded, gq_mla_prefill_mha -- three launches, no torch op, no
+        allocation after the first call at a given shape; the cache's own output buffer for (N, n_head) is returned."""
         cache = self.cache if cache is None else cache
         if cache is None:
             raise ValueError("no cache: call new_cache(B, capacity) first, or pass one")
         T, H, rank = q.shape[0], self.n_head, self.rank
+        N = T // cache.B
+        if 0 < self.unabsorbed_from <= N and cache.appended + N <= cache.kv_capacity:
+            # (positions decode steps appended since the last expansion are expanded in the same launch)
+            qbuf = cache.append(kv_a_out[:, :rank], kv_a_out[:, rank:], q, self.rope, self.norm_w, self.eps)
+            cache.expand(self.w_kv, cache.appended - cache.expanded)
+            return cache.attend_mha(q, qbuf[:, rank:], self.scale, q.shape[1] // H, qbuf.shape[1] // H)
         if self.fused:
             qbuf = cache.append(kv_a_out[:, :rank], kv_a_out[:, rank:], q, self.rope, self.norm_w, self.eps)
             _lib.mla_proj(0, self.k_b, q, q.shape[1] // H, qbuf, qbuf.shape[1] // H, T, H)

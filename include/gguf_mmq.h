@@ -37,6 +37,7 @@
  *   gq_mla_decode, gq_mla_append        DeepSeek's latent attention (MLA) at decode and its latent cache's producer
  *   gq_mla_prefill                      the same attention for a prompt or a chunk of one: any number of new tokens, one launch
  *   gq_mla_proj                         the per-head W_UK and W_UV products before and after that attention, one launch each
+ *   gq_mla_kv_expand, gq_mla_prefill_mha  the un-absorbed prompt pass: per-head K and V from the latent rows, attention at 192 / 128
  */
 #ifndef GGUF_MMQ_H
 #define GGUF_MMQ_H
@@ -821,6 +822,61 @@ int gq_mla_proj(int dir, const void *W, const void *X, int64_t ldx, int64_t x_he
 /* The plan of that call: the form (0 few-row, 1 tiled), the token rows per workgroup (16 or 64) and the grid.
  * GQ_EUNSUPPORTED: no such shape. */
 int gq_debug_mla_proj_plan(int dir, int64_t T, int64_t n_head, int *form, int *rows_per_block, int64_t *grid);
+
+/*
+ * The UN-absorbed prompt pass of that attention, two launches: decompress the new latent rows into per-head keys
+ * and values once, then attend at head dims 192 / 128 -- 640 flops per attended (row, key) where gq_mla_prefill's
+ * absorbed form pays 2176.  The latent cache, gq_mla_append and gq_mla_decode are used unchanged beside it.
+ *
+ * gq_mla_kv_expand: KV[b, p, h, m] = fp16(sum_c C[b, p, c] * W[h, m, c]) for the N newest positions p = kv_len[b] -
+ * N + i of every sequence (gq_mla_append's rule, read on the device).
+ *   W      : fp16 (n_head, 256, 512) contiguous, contraction index contiguous: head h's rows 0..127 are the
+ *            transpose of its W_UK (k_b, (512, 128)), rows 128..255 its W_UV (v_b, (128, 512)).
+ *   C, tok_stride, seq_stride, kv_len, capacity : gq_mla_decode's latent cache; a row's first 512 values are read.
+ *   KV     : fp16.  The row of (b, t) starts at byte b*kv_seq_stride + t*kv_tok_stride and holds n_head*256 values,
+ *            head h's 256 being [k_nope (128) | v (128)]; kv_capacity positions per sequence.
+ * A position outside [0, min(capacity, kv_capacity)) is skipped; nothing else is written, so a persistent buffer
+ * is extended chunk by chunk, and N = the largest length expands a whole prefix.  fp16 products, fp32 accumulation
+ * on the matrix cores in a fixed order, one rounding: gq_mla_proj's bound with Kc = 512.  ONE launch, no workspace:
+ * a workgroup owns 64 or 128 positions of a sequence and a range of heads, keeps their c_kv in registers and
+ * streams the range's W through LDS; the split follows from B, N, n_head and the compute units alone.
+ * Checks in this order: a negative size: GQ_EINVAL; (B, N or n_head == 0: a no-op); a null pointer: GQ_EINVAL;
+ * (rank, dim) != (512, 128), then gq_mla_decode's cache checks with its messages (n_head <= 128, B <= 2^17, the
+ * strides, N <= capacity, capacity * tok_stride), then kv_tok_stride or kv_seq_stride no multiple of 16,
+ * kv_tok_stride < n_head*512, kv_capacity < 1, kv_capacity * kv_tok_stride above 1 GiB (32-bit buffer offsets:
+ * 16384 positions at 128 heads), B*N >= 2^31: GQ_EUNSUPPORTED; W or KV not 16-byte aligned: GQ_EINVAL.
+ *
+ * gq_mla_prefill_mha: o = softmax(scale * (q_nope . k_nope + q_pe . k_pe)) v over positions 0 .. kv_len[b] - N + i.
+ *   Qn     : fp16 q_nope, head h of row r at element r*ldqn + h*qn_head_stride (the q projection's output as it
+ *            stands: qn_head_stride = 192).  Qp: the rotated q_pe at element r*ldqp + h*qp_head_stride -- where
+ *            gq_mla_append wrote it (Qp = Qout + 512, qp_head_stride = 576).
+ *   KV     : gq_mla_kv_expand's buffer: k_nope and v of (b, t, h).  C: the latent cache, whose columns 512..575
+ *            are the rope key every head shares.
+ *   O      : fp16 (B*N, n_head*128), rows ldo apart: attn_output's input.
+ * The length is clamped to [0, min(capacity, kv_capacity)]; positions beyond it are never used, whatever bytes
+ * they hold; a row without a position gives zeros; a sequence's output depends neither on B nor on the other
+ * sequences.  gq_attn_prefill's arithmetic (fp32 scores in the exp2 domain, fp32 softmax and sums, fp16
+ * probabilities, one rounding) and bound: |o - exact| <= 2^-9 * max|v| over the attended positions.  ONE launch,
+ * no key split, no workspace: B * n_head * ceil(N / rows) workgroups of 64 or 128 query rows of one (sequence,
+ * head) over 64-key tiles; the causal triangle is skipped; the heads of a (row block, sequence) are neighbours.
+ * Checks: null pointers, qn_head_stride < 128, qp_head_stride < 64, ldqn < (n_head-1)*qn_head_stride + 128, ldqp <
+ * (n_head-1)*qp_head_stride + 64, ldo < n_head*128: GQ_EINVAL; gq_mla_decode's cache checks (any N <= capacity),
+ * dim != 128, the KV checks above, B*N*n_head >= 2^31: GQ_EUNSUPPORTED; Qn, Qp or KV not 16-byte aligned, a Q
+ * leading dimension or head stride no multiple of 8, O not 8-byte aligned or ldo no multiple of 4: GQ_EINVAL.
+ * Both: every check precedes the launch.  Asynchronous, no host sync, no allocation, graph-capturable.  Detected
+ * by their symbols; gq_version() did not change with them.  No sliding window, no soft-cap, no Q8_0 cache, W fp16.
+ */
+int gq_mla_kv_expand(const void *W, const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity,
+                     void *KV, int64_t kv_tok_stride, int64_t kv_seq_stride, int64_t kv_capacity,
+                     int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t dim, void *stream);
+int gq_mla_prefill_mha(const void *Qn, int64_t ldqn, int64_t qn_head_stride, const void *Qp, int64_t ldqp, int64_t qp_head_stride,
+                       const void *KV, int64_t kv_tok_stride, int64_t kv_seq_stride, int64_t kv_capacity,
+                       const void *C, int64_t tok_stride, int64_t seq_stride, const int32_t *kv_len, int64_t capacity,
+                       void *O, int64_t ldo, float scale, int64_t B, int64_t N, int64_t n_head, int64_t rank, int64_t rope_dim,
+                       int64_t dim, void *stream);
+/* The plan of that call: the query rows per workgroup (64 or 128), the keys per tile and the grid B * n_head *
+ * ceil(N / rows).  GQ_EUNSUPPORTED: no such shape. */
+int gq_debug_mla_prefill_mha_plan(int64_t B, int64_t N, int64_t n_head, int *rows_per_block, int *tile, int64_t *grid);
 
 /*
  * Grouped GEMM: several gq_mmq_prepared_ex calls with the same token count N (5 <= N) in ONE

@@ -66,6 +66,13 @@ The per-head W_UK / W_UV products around that attention (kernels._lib.mla_proj: 
 fused=True (a strided-batch torch.bmm, and for the absorb the copy into the q buffer), and the fused forward beside
 the unfused one over a cache of 4096 positions (MlaProjCase).  The weights rotate.  A few-row cell carries the weight
 bytes over the time against the HBM figure, a tiled cell the TFLOP/s of 2 * T * heads * 512 * 128 flops.
+
+    python tools/attn_bench.py --mla-mha [--out profiles/attn_mla_mha_bench.json]
+
+The un-absorbed prompt pass (kernels._lib.mla_kv_expand, mla_prefill_mha), 16 and 128 heads, one sequence: a fresh
+prompt of 512 and of 4096 and a chunk of 512 after a prefix of 4096 (MlaMhaCase).  Per cell the expansion of the new
+rows alone, the attention alone (causal TFLOP/s at 2 * (192 + 128) flops per attended (row, key)) and the layer step
+MLAttention(unabsorbed_from=1) beside the absorbed fused step MLAttention(fused=True), all as captured graphs.
 """
 import argparse
 import json
@@ -435,6 +442,92 @@ def main_mla_proj(a, dev):
                                "rows": rows}, f, indent=1)
 
 
+class MlaMhaCase:
+    """N new tokens of one sequence after a prefix of P through the un-absorbed prompt pass: the expansion of the N
+    new rows alone, the attention alone, and the layer step (append + expand + attention: MLAttention(unabsorbed_from=1))
+    beside the absorbed fused step (append + gq_mla_proj + gq_mla_prefill + gq_mla_proj: MLAttention(fused=True)).
+    The weights rotate (every copy the same values); q, the caches and the outputs do not."""
+    forms = ("expand", "mha", "layer_unabsorbed", "layer_absorbed")
+
+    def __init__(self, nh, N, P, dev, steps):
+        import kernels._lib as kl
+        from kernels import MLAttention, RoPE
+        self.kl, self.dev, self.dims, L = kl, dev, (nh, N, P), P + N
+        ncopies, self.plans = bench.rotation_plan(max(2 * nh * 256 * 512, bench.ROTATE_BYTES // 256), steps)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        rnd = lambda *s: torch.randn(s, device=dev, generator=gen).to(torch.float16)  # noqa: E731
+        kb = (rnd(nh, 512, 128) * 128 ** -0.5).expand(ncopies, nh, 512, 128).contiguous().unbind(0)
+        vb = (rnd(nh, 128, 512) * 512 ** -0.5).expand(ncopies, nh, 128, 512).contiguous().unbind(0)
+        self.q, self.kv = rnd(N, nh * 192), rnd(N, 576)
+        f, m = RoPE.table(64)
+        rope, w = RoPE(torch.from_numpy(f).float().to(dev), 64, "norm", m), torch.ones(512, device=dev)
+        self.layers = {u: [MLAttention(k, v, w, rope, fused=True, unabsorbed_from=u) for k, v in zip(kb, vb)] for u in (0, 1)}
+        self.cache = c = self.layers[1][0].new_cache(1, L, dev)
+        c.c.view(torch.float16).copy_(rnd(L * 576))
+        self.len0, self.len1 = (torch.full((1,), n, dtype=torch.int32, device=dev) for n in (P, L))
+        c.kv_len.copy_(self.len1)  # the prefix (and the rest) expanded once: every copy of the weights has the same values
+        c.expand(self.layers[1][0].w_kv, L)
+        self.qbuf, self.out = c._for(N, nh)[0], torch.empty(N, nh * 128, dtype=torch.float16, device=dev)
+        self.pairs = N * P + N * (N + 1) // 2  # attended (row, key) pairs per head
+
+    def step(self, form, c, i):
+        nh, N, P = self.dims
+        ch = self.cache
+        if form == "expand":
+            return self.kl.mla_kv_expand(self.layers[1][c].w_kv, ch.c, ch.strides, self.len1, ch.capacity, ch.kv, 1, N, nh)
+        if form == "mha":
+            return self.kl.mla_prefill_mha(self.q, 192, self.qbuf[:, 512:], 576, ch.kv, ch.c, ch.strides, self.len1, ch.capacity, 1, N, nh,
+                                           self.layers[1][c].scale, self.out)
+        ch.kv_len.copy_(self.len0)  # (both layer forms: every step appends the same N tokens after the prefix)
+        ch.appended = ch.expanded = P
+        return self.layers[form == "layer_unabsorbed"][c].forward(self.q, self.kv, ch)
+
+    def check(self):
+        a = self.step("layer_absorbed", 0, 0).float().clone()
+        b = self.step("layer_unabsorbed", 0, 0).float()
+        torch.cuda.synchronize(self.dev)
+        d = float((a - b).abs().max() / a.abs().max())
+        assert d <= 2e-2, d
+        return d
+
+
+def main_mla_mha(a, dev):
+    rows = []
+    for nh in (16, 128):
+        for N, P in ((512, 0), (4096, 0), (512, 4096)):
+            steps = max(2, a.steps // 5)
+            case = MlaMhaCase(nh, N, P, dev, steps)
+            diff = case.check()
+            gs = {f: graphs(case, f, torch.cuda.graph_pool_handle()) for f in case.forms}
+            ts = {f: [] for f in case.forms}
+            for _ in range(a.repeats):  # interleaved: one pass over the forms per repeat
+                for f in case.forms:
+                    ts[f].append(bench.timed_rotation(gs[f], dev) / steps * 1e6)
+            rows_wg, tile, grid = case.kl.mla_prefill_mha_plan(1, N, nh)
+            row = {"heads": nh, "N": N, "prefix": P, "rows_per_workgroup": rows_wg, "tile": tile, "workgroups": grid,
+                   "layers_max_rel_diff": round(diff, 5)}
+            for f in case.forms:
+                us = float(np.median(ts[f]))
+                row[f] = {"us": round(us, 2), "spread_us": round(max(ts[f]) - min(ts[f]), 2)}
+            tf = 640.0 * case.pairs * nh / row["mha"]["us"] / 1e6  # causal: the attended pairs at 2 (192 + 128) flops
+            row["mha"].update(TFLOPs=round(tf, 1), mfma_frac=round(tf / bench.MFMA_F16_PEAK_TF, 4))
+            tf = 2.0 * N * nh * 256 * 512 / row["expand"]["us"] / 1e6
+            row["expand"].update(TFLOPs=round(tf, 1), mfma_frac=round(tf / bench.MFMA_F16_PEAK_TF, 4))
+            row["unabsorbed_speedup"] = round(row["layer_absorbed"]["us"] / row["layer_unabsorbed"]["us"], 3)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del case, gs
+            torch.cuda.empty_cache()
+            if a.out:  # (after every cell: a run cut short keeps what it measured)
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "w") as f:
+                    json.dump({"steps": steps, "repeats": a.repeats, "mfma_f16_peak_TF": bench.MFMA_F16_PEAK_TF,
+                               "compute_units": torch.cuda.get_device_properties(dev).multi_processor_count,
+                               "not_measured": "another workgroup id order, a third ring slot, other tile lengths, any profile "
+                                               "(no counters were collected)",
+                               "rows": rows}, f, indent=1)
+
+
 ROPE_HEADS = {"llama3_8b": (32, 8, 128, "norm", False), "qwen3_8b": (32, 8, 128, "neox", True)}
 
 
@@ -653,7 +746,10 @@ def main():
     ap.add_argument("--mla-prefill", action="store_true", help="the latent attention over a prompt (mla_prefill) beside torch and a decode loop")
     ap.add_argument("--rope", action="store_true", help="the fused norm + RoPE + append (rope_append) beside torch RoPE + kv_append")
     ap.add_argument("--mla-proj", action="store_true", help="the latent projections (mla_proj) and the fused MLAttention beside torch bmm")
+    ap.add_argument("--mla-mha", action="store_true", help="the un-absorbed MLA prompt pass (mla_kv_expand, mla_prefill_mha) beside the absorbed fused step")
     a = ap.parse_args()
+    if a.mla_mha and not a.out:
+        a.out = "profiles/attn_mla_mha_bench.json"
     if not torch.cuda.is_available():
         sys.exit("attn_bench.py needs a ROCm device: there is no CPU timing path")
     dev = torch.device("cuda:0")
@@ -663,6 +759,8 @@ def main():
         return main_mla_prefill(a, dev)
     if a.mla_proj:
         return main_mla_proj(a, dev)
+    if a.mla_mha:
+        return main_mla_mha(a, dev)
     if a.prefill:
         return main_prefill(a, dev)
     if a.rope:
